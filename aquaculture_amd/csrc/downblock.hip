@@ -44,6 +44,7 @@ struct DownParams {
 
 constexpr int kNW = 12;                                  // waves per workgroup (3 per SIMD)
 constexpr int kTW = 16;                                  // output tile width; every wave owns 4 rows x 16 pixels
+constexpr int kNST = 2;                                  // output store instructions per wave and full tile (16-byte stores of row pairs)
 
 // CIN -> CMID by the 3x3/s2; FUSE: followed by a 1x1 CMID -> CMID; KT: last k-steps of the 3x3 weights kept in LDS.
 //   <48, 96, true, 0>:   yolov5m model.1 + model.2.cv1|cv2   (6 M blocks x 2 pixel groups, 8 x 16 tile)
@@ -235,8 +236,10 @@ __global__ __launch_bounds__(kNW * 64) void downblock_kernel(const DownParams p)
         const int y0 = ty0 * G::TH, x0 = tx0 * kTW;
         const char* s_x = smem + (STEM ? 0 : cur) * G::XPB;
         // this tile's patch has landed (own DMA: vmcnt; the other waves': barrier).  vmcnt is in-order: after a full tile the
-        // youngest DMA instruction is older than that tile's 4 output stores, which may stay in flight.
-        if (prev_full) wait_vmcnt<4>(); else wait_vmcnt<0>();
+        // youngest DMA instruction is older than that tile's kNST output stores, which may stay in flight.  (A larger count than the
+        // stores actually issued lets the last DMA instructions of the patch through the wait: the other waves then read rows that
+        // have not landed.)
+        if (prev_full) wait_vmcnt<kNST>(); else wait_vmcnt<0>();
         if constexpr (STEM) {
             // ---- 0. the x patch = SiLU(stem(raw patch)), zero outside the stem's output image (the 3x3 pads x, not the tile) ----
             convert_stage();                                 // own slots only: no barrier between the DMA and here
@@ -402,6 +405,7 @@ __global__ __launch_bounds__(kNW * 64) void downblock_kernel(const DownParams p)
             pk[j] = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
         }
         const int odd = g & 1;
+        static_assert(4 / 2 == kNST, "4 rows, 2 per store: the wait at the top of the tile loop counts these stores");
 #pragma unroll
         for (int j = 0; j < 4; j += 2) {
             const auto r0 = __builtin_amdgcn_permlane16_swap(pk[j].x, pk[j + 1].x, false, false);

@@ -67,7 +67,34 @@ def parse():
     p.add_argument("--launcher-selftest", action="store_true", help="run only the rank launch / rendezvous / reduction plumbing (no GPU work)")
     p.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "hbm_traffic_latest.json"),
                    help="optional PMC-derived HBM bytes per launch for the dominant kernel")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what rank 0's last timed step returned as DIR/<name>.npy (see dump_outputs): "
+                        "the same arguments give the same inputs, so two builds can be compared output for output")
     return p.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, dets: torch.Tensor, counts: torch.Tensor, pool_batch: int) -> dict:
+    """What `Engine.infer` hands its caller for one batch: `counts` [B] (boxes kept per tile) and `detections` [B, max_det, 6] (x1, y1,
+    x2, y2, conf, cls per box), written as float64 / float32.  Rows past a tile's count are unspecified in the engine's output and are
+    written as zeros.  A batch whose detections exceed DUMP_LIMIT_BYTES keeps a fixed, seeded sample of tiles; `tile_index` names them."""
+    counts = counts.cpu()
+    B, max_det, _ = dets.shape
+    keep = B
+    if counts.numel() * 8 + B * max_det * 6 * 4 + B * 8 > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - counts.numel() * 8) // (max_det * 6 * 4 + 8)
+    idx = np.arange(B) if keep == B else np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    d = dets[torch.from_numpy(idx).to(dets.device)].cpu()
+    d[torch.arange(max_det).view(1, -1) >= counts[idx].view(-1, 1)] = 0.0
+    arrays = {"detections": d.numpy().astype(np.float32), "counts": counts.numpy().astype(np.float64),
+              "tile_index": idx.astype(np.float64)}
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
+    return {"dir": directory, "pool_batch": pool_batch, "tiles": int(keep),
+            "arrays": {name: list(arr.shape) for name, arr in arrays.items()}}
 
 
 def host_threads() -> int:
@@ -349,6 +376,9 @@ def main() -> int:
     aqdist.barrier()
     elapsed = time.perf_counter() - t0
     n_dets_total = int(gathered[0])
+    dumped = None
+    if a.dump_outputs and rank == 0:      # before the roofline pass below writes its steps into dets[0:R]
+        dumped = dump_outputs(a.dump_outputs, dets[K - 1], counts[K - 1], (K - 1) % a.pool)
     ranks_info = None
     if aqdist.active():
         cdev = "cpu" if torch.distributed.get_backend() == "gloo" else dev
@@ -497,6 +527,7 @@ def main() -> int:
                    "batch_per_gpu": B, "tile_px": a.size, "parallelism": f"tile-sharded dp{world}", **({"collectives": torch.distributed.get_backend(), "ranks": ranks_info} if aqdist.active() else {}), "batches_in_flight": a.streams, **({"cu_split": a.cu_split} if a.cu_split else {}),
                    "detections_gathered": n_dets_total},
         "roofline": roof,
+        **({"dump_outputs": dumped} if dumped else {}),
     }
     # SURVEY 8d's second leg: the same build end to end from an image directory (tools/bench_e2e.py, a separate run on the same pool of
     # boxes): quoted only when it was measured on THIS library build; never part of `value`

@@ -180,3 +180,31 @@ def test_generated_planar_assembly_wide_stores(tmp_path):
                 for ahead in (1, 2):                     # gfx940+: two wait states between a store of more than 8 bytes and a VALU write of its data
                     nxt = re.match(r"v_\S+ (v\d+|v\[\d+:\d+\])", ins[i + ahead])
                     assert not nxt or not (_regs(nxt.group(1)) & data), f"{fam}: '{ins[i + ahead]}' rewrites the data of '{l}'"
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# downblock.hip: the persistent loop waits for the next tile's patch DMA with a hand-counted vmcnt after a full tile -- the number of
+# output store instructions that tile issued after its DMA.  A count larger than the stores lets the last DMA instructions of the patch
+# through the wait, and the other waves read patch rows that have not landed (results then change from run to run).
+@pytest.fixture(scope="module")
+def downblock_asm(tmp_path_factory):
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    out = tmp_path_factory.mktemp("isa") / "downblock.s"
+    src = os.path.join(ROOT, "aquaculture_amd", "csrc", "downblock.hip")
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT}/include", f"-I{os.path.dirname(src)}", "--cuda-device-only",
+                    "-S", src, "-o", str(out)], check=True, capture_output=True)
+    return out.read_text()
+
+
+def test_downblock_patch_wait_counts_the_output_stores(downblock_asm):
+    kernels = re.split(r"\n(?=_ZN\S*downblock_kernel\S*:\s*; @)", downblock_asm)[1:]
+    assert len(kernels) >= 3
+    for k in kernels:
+        name = k.split(":", 1)[0]
+        body = k.split(".Lfunc_end")[0].split("\n")
+        stores = sum(1 for l in body if l.strip().startswith("global_store"))
+        hand = {int(m.group(1)) for i, l in enumerate(body) if (m := re.search(r"s_waitcnt vmcnt\((\d+)\)", l)) and "ASMSTART" in body[i - 1]}
+        assert hand - {0}, f"{name}: no hand-counted wait for the patch DMA"
+        assert hand - {0} == {stores}, f"{name}: waits vmcnt{sorted(hand - {0})} behind {stores} output store instructions per tile"
