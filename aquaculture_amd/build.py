@@ -101,6 +101,15 @@ def _assemble_planar(verbose: bool, cc: str) -> None:
         os.replace(inc + ".tmp", inc)
 
 
+def generate_asm_includes(verbose: bool = False) -> None:
+    """Only the generated-assembly step of build(): writes the csrc/*_hsaco.inc files that bottleneck.hip, conv3x3_pl.hip and
+    conv1x1_asm.hip include, so that those sources compile on their own (tests/test_build_isa.py) in a tree build() has not run in."""
+    import fcntl
+    with open(os.path.join(CSRC, ".build.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        _assemble_planar(verbose, hipcc())
+
+
 def build_jpeg_lib() -> str:
     """libaqjpeg.so: csrc/jpeg_coef.c with the host C compiler (no GPU toolchain involved)."""
     cc = shutil.which("gcc") or shutil.which("cc") or shutil.which("clang")

@@ -483,6 +483,7 @@ __global__ __launch_bounds__(NW * 64) void bottleneck_kernel(const BtlParams p) 
                             }
                         }
                     }
+                    static_assert(G::NST == 4 * MBW, "4 pixel blocks x MBW stores per phase-C step: the wait at the top of the tile loop counts these");
 #pragma unroll
                     for (int m = 0; m < MBW; ++m) {
                         f32x4 v = silu4(acc[j][m] + b2v[m]);

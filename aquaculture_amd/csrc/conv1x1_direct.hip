@@ -43,6 +43,7 @@ template <int KS, int MBT, int MBW, int NBW> struct C1Geom {
     static constexpr int NQ = (TP * SPP + 63) / 64;
     static constexpr int XPB = NQ * 1024;
     static constexpr int LDS = 2 * XPB + COUT * 4;
+    static constexpr int NST = NBW;                          // output store instructions per wave and full tile (one per pixel block)
     static_assert(MBT % MBW == 0 && kNW % MG == 0 && LDS <= 160 * 1024, "shape");
 };
 
@@ -97,8 +98,9 @@ __global__ __launch_bounds__(kNW * 64) void conv1x1_direct_kernel(const C1Params
         const long long n0 = (long long)tile * G::TP;
         const char* s_x = smem + cur * G::XPB;
         // this tile has landed (own DMA: vmcnt; other waves': barrier), and every wave is done with the other buffer.  vmcnt is
-        // in-order: after a full tile the DMA is older than that tile's NBW output stores, which may stay in flight.
-        if (prev_full) wait_vmcnt<NBW>(); else wait_vmcnt<0>();
+        // in-order: after a full tile the DMA is older than that tile's G::NST output stores, which may stay in flight.  (A larger
+        // count than the stores actually issued lets the last DMA instructions of the tile through the wait.)
+        if (prev_full) wait_vmcnt<G::NST>(); else wait_vmcnt<0>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -108,7 +110,8 @@ __global__ __launch_bounds__(kNW * 64) void conv1x1_direct_kernel(const C1Params
         f32x4 bv[MBW];
 #pragma unroll
         for (int m = 0; m < MBW; ++m) bv[m] = *(const f32x4*)(s_b + cbase + m * 4);
-#pragma unroll 2
+        static_assert(G::NST == NBW * 1, "one 16-byte (8-byte with F8OUT) store per pixel block: the wait at the top of the tile loop counts these");
+        AQ_STORE_LOOP_UNROLL
         for (int j = 0; j < NBW; ++j) {
             const int px = (pg * NBW + j) * 16 + l15;
             const char* base = s_x + px * G::PXB + g * 16;

@@ -27,6 +27,15 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {   // one v
     return u;
 }
 
+// Unroll factor of a persistent kernel's output store loop whose stores a hand-counted vmcnt wait counts (conv1x1_direct.hip,
+// stem_conv.hip).  tests/test_build_isa.py compiles those files with AQ_ISA_FULL_UNROLL, so that the assembly holds every store
+// instruction of a full tile once and the test can compare their number with the wait.
+#ifdef AQ_ISA_FULL_UNROLL
+#define AQ_STORE_LOOP_UNROLL _Pragma("unroll")
+#else
+#define AQ_STORE_LOOP_UNROLL _Pragma("unroll 2")
+#endif
+
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     // all but the wave's N youngest vector-memory operations are done (loads, LDS-DMA, stores: in issue order)

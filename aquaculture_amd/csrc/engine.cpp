@@ -26,7 +26,7 @@ void aq_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* aq_last_error(void) { return g_err; }
-extern "C" int aq_version(void) { return 7; }   // 7: generated-assembly wide 1x1 (AQ_CONV_CFG_ASM1X1), assembly C = 48 Bottleneck; 6: planar 3x3/s2 and fp8 families, AQ_F16X3, fp8 pairs; 5: AQ_BF16_W8, aq_conv3x3_pl_w8; 2: fused stem / Bottleneck / down-block ops, direct 1x1 and 3x3/s2 candidates; 3: one-tile-per-workgroup grids
+extern "C" int aq_version(void) { return 8; }   // 8: aq_engine_run_ops; 7: generated-assembly wide 1x1 (AQ_CONV_CFG_ASM1X1), assembly C = 48 Bottleneck; 6: planar 3x3/s2 and fp8 families, AQ_F16X3, fp8 pairs; 5: AQ_BF16_W8, aq_conv3x3_pl_w8; 2: fused stem / Bottleneck / down-block ops, direct 1x1 and 3x3/s2 candidates; 3: one-tile-per-workgroup grids
 
 namespace {
 
@@ -352,9 +352,16 @@ int run_conv(aq_engine* e, int oi, void* ws, const uint8_t* tiles, int B, hipStr
     return aq_launch_conv(p, pw.x3 ? (int)AQ_F16X3 : prec, out_f32, cfg, stream);
 }
 
+// Runs plan ops [first, last) -- the whole plan for every entry point but aq_engine_run_ops, which steps through it in pieces.  Every
+// decision that spans ops (stem + down-block as one launch, fused heads, the counter memset before the first head and the gather behind
+// the third) is made from the whole plan, not from the range, so a plan run in pieces launches exactly what one call launches.
 int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, size_t ws_bytes,
-             float* pred_out, aq_det* dets, int32_t* counts, float conf, float iou, int max_det, hipStream_t stream) {
+             float* pred_out, aq_det* dets, int32_t* counts, float conf, float iou, int max_det, hipStream_t stream,
+             int first = 0, int last = -1) {
     AQ_REQUIRE(e && tiles && ws, "infer: null pointer");
+    const int n_ops = (int)e->ops.size();
+    if (last < 0) last = n_ops;
+    AQ_REQUIRE(0 <= first && first <= last && last <= n_ops, "run_ops: range [%d, %d) is not inside the plan's %d ops", first, last, n_ops);
     int rc = layout(e, B, H, W);
     if (rc) return rc;
     if (ws_bytes < e->total_bytes) {
@@ -363,9 +370,9 @@ int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, 
     }
     e->last_ws = ws; e->last_tiles = tiles;
     const int prec = e->desc.precision;
-    const int n_ops = (int)e->ops.size();
-    hipEvent_t* ev = nullptr;
-    if (e->prof && e->ring > 0) ev = e->ev.data() + (size_t)(e->prof_calls % e->ring) * (n_ops + 1);
+    const bool whole = first == 0 && last == n_ops;
+    hipEvent_t* ev = nullptr;                            // per-op timing covers whole calls only
+    if (whole && e->prof && e->ring > 0) ev = e->ev.data() + (size_t)(e->prof_calls % e->ring) * (n_ops + 1);
     float* pred = pred_out ? pred_out : (float*)((char*)ws + e->off_pred);
     int32_t* cand = (int32_t*)((char*)ws + e->off_cand);
     int32_t* cand_count = (int32_t*)((char*)ws + e->off_cand_count);
@@ -388,7 +395,12 @@ int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, 
             if (!e->packed[oi].w_head) fuse_heads = false;
         }
     if (n_heads != 3) fuse_heads = false;
-    for (int oi = 0; oi < n_ops; ++oi) {
+    for (int oi = 0; oi < first; ++oi)                   // heads an earlier piece of the plan already ran
+        if (fuse_heads && e->ops[oi].kind == AQ_OP_CONV && e->ops[oi].level >= 0) {
+            heads_started = true;
+            ++heads_done;
+        }
+    for (int oi = first; oi < last; ++oi) {
         const aq_op_desc& op = e->ops[oi];
         if (ev) AQ_CHECK_HIP(hipEventRecord(ev[oi], stream));
         const bool mark = g_roctx.on();
@@ -842,6 +854,15 @@ extern "C" int aq_engine_infer(aq_engine* e, const uint8_t* tiles_dev, int B, in
     return run_plan(e, tiles_dev, B, H, W, ws, ws_bytes, nullptr, dets_dev, counts_dev, conf, iou, max_det, (hipStream_t)stream);
 }
 
+extern "C" int aq_engine_run_ops(aq_engine* e, const uint8_t* tiles_dev, int B, int H, int W, void* ws, size_t ws_bytes, int first, int last,
+                                 float conf, float iou, int max_det, aq_det* dets_dev, int32_t* counts_dev, void* stream) {
+    AQ_REQUIRE(dets_dev && counts_dev, "run_ops: null output pointer");
+    AQ_REQUIRE(max_det > 0 && conf >= 0.f && conf <= 1.f && iou >= 0.f && iou <= 1.f,
+               "run_ops: bad thresholds conf=%g iou=%g max_det=%d", conf, iou, max_det);
+    AQ_REQUIRE(e && first >= 0 && first <= last && last <= (int)e->ops.size(), "run_ops: range [%d, %d) is not inside the plan", first, last);
+    return run_plan(e, tiles_dev, B, H, W, ws, ws_bytes, nullptr, dets_dev, counts_dev, conf, iou, max_det, (hipStream_t)stream, first, last);
+}
+
 extern "C" int aq_engine_forward_raw(aq_engine* e, const uint8_t* tiles_dev, int B, int H, int W, void* ws, size_t ws_bytes,
                                      float* pred_dev, void* stream) {
     AQ_REQUIRE(pred_dev, "forward_raw: null output pointer");
@@ -931,6 +952,16 @@ extern "C" int aq_engine_tensor_ptr(aq_engine* e, int tensor, void** ptr, int* c
     if (h) *h = e->place[tensor].h;
     if (w) *w = e->place[tensor].w;
     if (elem_bytes) *elem_bytes = e->place[tensor].elem;
+    return AQ_OK;
+}
+
+extern "C" int aq_engine_candidates(aq_engine* e, void** cand, void** rows, void** counts, int* cap) {
+    AQ_REQUIRE(e && cand && rows && counts && cap, "candidates: null pointer");
+    AQ_REQUIRE(e->last_ws, "candidates: no call has run yet");
+    *cand = (char*)e->last_ws + e->off_cand;
+    *rows = (char*)e->last_ws + e->off_cand_rows;
+    *counts = (char*)e->last_ws + e->off_cand_count;
+    *cap = e->N;
     return AQ_OK;
 }
 

@@ -215,7 +215,9 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const ConvParams p, c
             __syncthreads();
         }
         // ---- 8 blocks of 16 pixels per wave: rows 2*wave, 2*wave+1 x 4 column blocks ----
-#pragma unroll 2
+        static_assert(NST == 8 * (MB / 2 + (MB & 1)), "8 pixel blocks per wave, each MB / 2 16-byte stores and an 8-byte rest for odd MB: "
+                                                      "the DMA variant's wait below counts these");
+        AQ_STORE_LOOP_UNROLL
         for (int q = 0; q < 8; ++q) {
             const int ty = 2 * wave + (q >> 2), txb = (q & 3) * 16;
             const int y = y0 + ty;
@@ -284,7 +286,8 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const ConvParams p, c
             }
         }
         if constexpr (DMA) {
-            // the DMA of the next tile's raw dwords is older than this tile's output stores: a full tile issued exactly NST of them
+            // the DMA of the next tile's raw dwords is older than this tile's output stores: a full tile issued exactly NST of them (a larger
+            // count lets the last DMA instructions through the wait, and convert_stage reads dwords that have not landed)
             const bool full = y0 + kTH <= Ho && x0 + kTW <= Wo;
             if (full) wait_vmcnt<NST>(); else wait_vmcnt<0>();
             convert_stage(s_patch + (cur ^ 1) * G::PATCHB);   // next tile's patch (all zeros past the last tile)

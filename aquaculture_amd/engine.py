@@ -64,7 +64,7 @@ class aq_det(C.Structure):
 # every symbol include/aq_engine.h declares (tests check the library exports all of them)
 EXPORTS = (
     "aq_last_error", "aq_version", "aq_engine_create", "aq_engine_destroy", "aq_engine_workspace_bytes",
-    "aq_engine_infer", "aq_engine_forward_raw", "aq_engine_tensor_ptr", "aq_engine_profile",
+    "aq_engine_infer", "aq_engine_run_ops", "aq_engine_candidates", "aq_engine_forward_raw", "aq_engine_tensor_ptr", "aq_engine_profile",
     "aq_engine_op_times", "aq_engine_num_ops", "aq_engine_set_conv_config", "aq_engine_autotune", "aq_engine_set_tuned_table",
     "aq_engine_get_conv_config", "aq_conv_num_configs", "aq_debug_conv_stamp", "aq_debug_mfma_peak",
     "aq_conv_config_tiles", "aq_pack_conv_weights", "aq_pack_conv_weights_x3", "aq_conv2d", "aq_pack_stem_weights", "aq_stem_conv", "aq_pack_bottleneck_weights", "aq_bottleneck", "aq_pack_downblock_weights", "aq_downblock", "aq_stemdown_supported", "aq_stemdown", "aq_conv1x1_direct_supported", "aq_pack_conv1x1_direct", "aq_conv1x1_direct", "aq_conv1x1_asm_supported", "aq_pack_conv1x1_asm", "aq_conv1x1_asm", "aq_nms_opts", "aq_engine_set_nms_options",
@@ -94,6 +94,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_engine_destroy.restype = None
     lib.aq_engine_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
     lib.aq_engine_infer.argtypes = [vp, vp, i32, i32, i32, vp, sz, vp, vp, f32, f32, i32, vp]
+    lib.aq_engine_run_ops.argtypes = [vp, vp, i32, i32, i32, vp, sz, i32, i32, f32, f32, i32, vp, vp, vp]
+    lib.aq_engine_candidates.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
     lib.aq_engine_forward_raw.argtypes = [vp, vp, i32, i32, i32, vp, sz, vp, vp]
     lib.aq_engine_tensor_ptr.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.aq_engine_profile.argtypes = [vp, i32, i32]
@@ -358,6 +360,22 @@ class Engine:
                                         dets.data_ptr(), counts.data_ptr(), conf_thres, iou_thres, max_det, _stream_ptr()))
         return dets, counts
 
+    def run_ops(self, tiles: torch.Tensor, first: int, last: int, conf_thres: float = 0.25, iou_thres: float = 0.45, max_det: int = 1000,
+                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, slot: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Plan ops [first, last) of ``infer`` on the same arguments (tests only: layer-by-layer checks of the path ``infer`` takes).
+        Stepping through the plan in order on one workspace slot and stream launches exactly what one ``infer`` call launches; ``out``
+        holds the detections and counts once the last op (NMS) has run.  Between calls, ``tensor`` views the ops' inputs and outputs."""
+        B, H, W = self._check_tiles(tiles)
+        ws = self.workspace(B, H, W, slot)
+        if out is None:
+            dets = torch.empty((B, max_det, 6), dtype=torch.float32, device=self.device)
+            counts = torch.empty((B,), dtype=torch.int32, device=self.device)
+        else:
+            dets, counts = out
+        _check(self.lib.aq_engine_run_ops(self.handle, tiles.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(), first, last,
+                                          conf_thres, iou_thres, max_det, dets.data_ptr(), counts.data_ptr(), _stream_ptr()))
+        return dets, counts
+
     # ---- S1 ----
     def forward_raw(self, tiles: torch.Tensor) -> torch.Tensor:
         """uint8 [B,H,W,3] -> pred float32 [B, N, 5+nc] (what Detect.forward returns at inference)."""
@@ -386,6 +404,18 @@ class Engine:
         nbytes = B * h.value * w.value * c.value * eb.value
         dt = {1: torch.uint8, 2: torch.bfloat16, 4: torch.float32}[eb.value]
         return self._ws[off:off + nbytes].view(dt).view(B, h.value, w.value, c.value)
+
+    def candidates(self, B: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Views of the candidate list the NMS step reads, inside the workspace after a call (tests only): (cand int32 [B, N] candidate
+        indices, rows float32 [B, N, 5 + nc] decoded rows in the same order, counts int32 [B]); entries past counts[b] are unspecified."""
+        c, r, n, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int()
+        _check(self.lib.aq_engine_candidates(self.handle, C.byref(c), C.byref(r), C.byref(n), C.byref(cap)))
+        base, N = self._ws.data_ptr(), cap.value
+
+        def view(p, nbytes, dt, shape):
+            return self._ws[p - base:p - base + nbytes].view(dt).view(*shape)
+        return (view(c.value, B * N * 4, torch.int32, (B, N)), view(r.value, B * N * self.no * 4, torch.float32, (B, N, self.no)),
+                view(n.value, B * 4, torch.int32, (B,)))
 
     def tensor_by_name(self, name: str, B: int) -> torch.Tensor:
         ids = [i for i, t in enumerate(self.plan.tensors) if t.name == name]

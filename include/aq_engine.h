@@ -114,11 +114,20 @@ int aq_engine_infer(aq_engine* e, const uint8_t* tiles_dev, int B, int H, int W,
 /* S1 only: pred_dev float [B][N][5+nc] (xywh px, obj, cls) exactly as Detect.forward returns it. */
 int aq_engine_forward_raw(aq_engine* e, const uint8_t* tiles_dev, int B, int H, int W,
                           void* workspace_dev, size_t workspace_bytes, float* pred_dev, void* stream);
+/* Test hook: plan ops [first, last) of aq_engine_infer on the same arguments.  Stepping through the plan in pieces (first = 0 up to
+ * aq_engine_num_ops, each piece on the same workspace and stream, in order) launches exactly the kernels, tuned configurations and grids
+ * one aq_engine_infer call launches, and writes the same detections and counts once the last op has run. */
+int aq_engine_run_ops(aq_engine* e, const uint8_t* tiles_dev, int B, int H, int W, void* workspace_dev, size_t workspace_bytes,
+                      int first, int last, float conf_thres, float iou_thres, int max_det, aq_det* dets_dev, int32_t* counts_dev,
+                      void* stream);
 /* Test hook: device address + geometry of plan tensor `tensor` inside the workspace of the last call. */
 int aq_engine_tensor_ptr(aq_engine* e, int tensor, void** ptr, int* channels, int* h, int* w, int* elem_bytes);
 /* Per-op device timing with HIP events on the launch stream (bench.py roofline).  ring = number of
  * infer calls whose events are kept; aq_engine_op_times returns mean ms per op over recorded calls. */
 int aq_engine_profile(aq_engine* e, int enable, int ring);
+/* Test hook: the candidate list the NMS step reads, inside the workspace of the last call: cand int32 [B][cap] (candidate index,
+ * level-major as in pred), rows float [B][cap][5+nc] (decoded xywh px, obj, cls) in the same order, counts int32 [B]; cap = N. */
+int aq_engine_candidates(aq_engine* e, void** cand_dev, void** rows_dev, void** counts_dev, int* cap);
 int aq_engine_op_times(aq_engine* e, float* ms_out, int n_ops, int* calls_recorded);
 int aq_engine_num_ops(aq_engine* e);
 /* Tuning hook: force the tile configuration of one conv op (-1 = built-in heuristic). */

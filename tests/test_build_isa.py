@@ -16,6 +16,22 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _compile_isa(out_dir, name, *defines):
+    """gfx950 assembly of csrc/<name>.hip.  The generated-assembly includes some of these files embed (*_hsaco.inc) are build products,
+    git-ignored: produce them first (the generator step of build()), so that this runs in a tree that has never been built."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    from aquaculture_amd import build
+    build.generate_asm_includes()
+    out = out_dir / f"{name}.s"
+    src = os.path.join(ROOT, "aquaculture_amd", "csrc", f"{name}.hip")
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT}/include", f"-I{os.path.dirname(src)}", *defines,
+                        "--cuda-device-only", "-S", src, "-o", str(out)], capture_output=True, text=True)
+    assert r.returncode == 0, f"hipcc -S {name}.hip failed:\n{r.stderr[-4000:]}"
+    return out.read_text()
+
+
 def _regs(text):
     r = set()
     for m in re.finditer(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]", text):
@@ -25,14 +41,7 @@ def _regs(text):
 
 @pytest.fixture(scope="module")
 def bottleneck_asm(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("isa") / "bottleneck.s"
-    src = os.path.join(ROOT, "aquaculture_amd", "csrc", "bottleneck.hip")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT}/include", f"-I{os.path.dirname(src)}", "--cuda-device-only",
-                    "-S", src, "-o", str(out)], check=True, capture_output=True)
-    return out.read_text()
+    return _compile_isa(tmp_path_factory.mktemp("isa"), "bottleneck")
 
 
 def test_asm_loaded_shortcut_registers_are_untouched_until_the_wait(bottleneck_asm):
@@ -73,14 +82,7 @@ def test_asm_loaded_shortcut_registers_are_untouched_until_the_wait(bottleneck_a
 # (a copy or an AGPR spill there reads the old contents), (c) move accumulators around inside the MFMA stream.
 @pytest.fixture(scope="module")
 def planar_asm(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("isa") / "conv3x3_pl.s"
-    src = os.path.join(ROOT, "aquaculture_amd", "csrc", "conv3x3_pl.hip")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT}/include", f"-I{os.path.dirname(src)}", "--cuda-device-only",
-                    "-S", src, "-o", str(out)], check=True, capture_output=True)
-    return out.read_text()
+    return _compile_isa(tmp_path_factory.mktemp("isa"), "conv3x3_pl")
 
 
 def test_planar_kernel_hand_counted_memory_operations(planar_asm):
@@ -188,14 +190,7 @@ def test_generated_planar_assembly_wide_stores(tmp_path):
 # through the wait, and the other waves read patch rows that have not landed (results then change from run to run).
 @pytest.fixture(scope="module")
 def downblock_asm(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("isa") / "downblock.s"
-    src = os.path.join(ROOT, "aquaculture_amd", "csrc", "downblock.hip")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT}/include", f"-I{os.path.dirname(src)}", "--cuda-device-only",
-                    "-S", src, "-o", str(out)], check=True, capture_output=True)
-    return out.read_text()
+    return _compile_isa(tmp_path_factory.mktemp("isa"), "downblock")
 
 
 def test_downblock_patch_wait_counts_the_output_stores(downblock_asm):
@@ -208,3 +203,75 @@ def test_downblock_patch_wait_counts_the_output_stores(downblock_asm):
         hand = {int(m.group(1)) for i, l in enumerate(body) if (m := re.search(r"s_waitcnt vmcnt\((\d+)\)", l)) and "ASMSTART" in body[i - 1]}
         assert hand - {0}, f"{name}: no hand-counted wait for the patch DMA"
         assert hand - {0} == {stores}, f"{name}: waits vmcnt{sorted(hand - {0})} behind {stores} output store instructions per tile"
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# The same wait in the other persistent kernels: after a full tile, `prev_full ? vmcnt(N) : vmcnt(0)` lets N operations stay in flight,
+# where N is meant to be the output stores the tile issued after the next tile's DMA (vmcnt is in order).  An N above the stores a wave
+# really issues lets DMA instructions through the wait -- the down-block race.  Each kernel's N is a named constant tied to its store
+# loop by a static_assert; this checks it against the store instructions the compiler emitted.
+def _kernels(asm, stem):
+    for k in re.split(rf"\n(?=_ZN\S*{stem}\S*:\s*; @)", asm)[1:]:
+        body = k.split(".Lfunc_end")[0].split("\n")
+        stores = [l.strip() for l in body if l.strip().startswith("global_store")]
+        hand = {int(m.group(1)) for i, l in enumerate(body) if (m := re.search(r"s_waitcnt vmcnt\((\d+)\)", l)) and "ASMSTART" in body[i - 1]}
+        yield k.split(":", 1)[0], stores, hand - {0}
+
+
+def test_bottleneck_tile_wait_counts_the_output_stores(bottleneck_asm):
+    """bottleneck.hip (HIP-source kernels): the next tile's DMA is issued inside phase C's MFMA loop, ahead of the 4 x MBW stores of that
+    phase-C step; the step loop is not unrolled, so the assembly holds one step's stores."""
+    checked = 0
+    for name, stores, hand in _kernels(bottleneck_asm, "bottleneck_kernel"):
+        if name.endswith("ELb1EEEvNS_9BtlParamsE"):
+            continue                                        # stamped diagnostic builds: their timing probes store too
+        assert len(hand) == 1, f"{name}: hand-counted waits vmcnt{sorted(hand)}"
+        n = hand.pop()
+        assert 0 < n <= len(stores), f"{name}: waits vmcnt({n}) behind {len(stores)} output store instructions per phase-C step"
+        assert n == len(stores), f"{name}: vmcnt({n}) for {len(stores)} stores (NST and the store loop disagree)"
+        checked += 1
+    assert checked >= 7
+
+
+@pytest.fixture(scope="module")
+def conv1x1_direct_asm_unrolled(tmp_path_factory):
+    return _compile_isa(tmp_path_factory.mktemp("isa"), "conv1x1_direct", "-DAQ_ISA_FULL_UNROLL")
+
+
+def test_direct_conv1x1_tile_wait_counts_the_output_stores(conv1x1_direct_asm_unrolled):
+    """conv1x1_direct.hip: NBW pixel blocks per wave and tile, one store each (bf16: 16 bytes, F8OUT: 8 bytes).  The store loop is
+    `unroll 2` in the product; compiled fully unrolled here, so that the assembly holds a full tile's stores."""
+    checked = 0
+    for name, stores, hand in _kernels(conv1x1_direct_asm_unrolled, "conv1x1_direct_kernel"):
+        nbw = int(re.search(r"conv1x1_direct_kernelILi\d+ELi\d+ELi\d+ELi(\d+)E", name).group(1))
+        assert len(hand) == 1, f"{name}: hand-counted waits vmcnt{sorted(hand)}"
+        n = hand.pop()
+        assert len(stores) == nbw, f"{name}: {len(stores)} store instructions for NBW = {nbw} pixel blocks"
+        assert 0 < n <= len(stores), f"{name}: waits vmcnt({n}) behind {len(stores)} output store instructions per tile"
+        assert n == len(stores), f"{name}: vmcnt({n}) for {len(stores)} stores (NST and the store loop disagree)"
+        checked += 1
+    assert checked >= 6
+
+
+@pytest.fixture(scope="module")
+def stem_asm_unrolled(tmp_path_factory):
+    return _compile_isa(tmp_path_factory.mktemp("isa"), "stem_conv", "-DAQ_ISA_FULL_UNROLL")
+
+
+def test_stem_dma_tile_wait_counts_the_output_stores(stem_asm_unrolled):
+    """stem_conv.hip, LDS-DMA variant (bf16): 8 blocks of 16 pixels per wave and tile, each MB / 2 stores of 16 bytes and, for odd MB,
+    one of 8.  The other variants wait for nothing by hand."""
+    checked = 0
+    for name, stores, hand in _kernels(stem_asm_unrolled, "stem_conv_kernel"):
+        f32, mb, dma = re.search(r"stem_conv_kernelILb([01])ELi(\d+)ELb([01])E", name).groups()
+        if dma == "0":
+            assert not hand, f"{name}: a hand-counted wait in a variant without DMA"
+            continue
+        mb = int(mb)
+        assert len(hand) == 1, f"{name}: hand-counted waits vmcnt{sorted(hand)}"
+        n = hand.pop()
+        assert len(stores) == 8 * (mb // 2 + mb % 2), f"{name}: {len(stores)} store instructions for MB = {mb}"
+        assert 0 < n <= len(stores), f"{name}: waits vmcnt({n}) behind {len(stores)} output store instructions per tile"
+        assert n == len(stores), f"{name}: vmcnt({n}) for {len(stores)} stores (NST and the store loop disagree)"
+        checked += 1
+    assert checked >= 4
