@@ -31,6 +31,7 @@ SOURCES = [
     ("pointwise.hip", []),
     ("detect_nms.hip", ["-ffp-contract=off"]),   # bit-level parity with the oracle's fp32 op order
     ("head_decode.hip", ["-ffp-contract=off"]),  # the same decode arithmetic, fused behind the Detect head convs
+    ("augment.hip", ["-ffp-contract=off"]),      # --augment: pass geometry, bilinear taps in PyTorch's CPU fp32 order, scaled preprocess
     ("jpeg_idct.hip", []),                       # device half of the split JPEG decode (IDCT, chroma upsampling, colour conversion)
     ("jpeg_huff.hip", []),                       # GPU entropy decode (round 4): the Huffman stage, one lane per restart segment
     ("engine.cpp", ["-x", "hip"]),

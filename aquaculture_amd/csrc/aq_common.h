@@ -40,6 +40,27 @@ __host__ __device__ static inline float aq_bf2f(bf16_t h) {
     union { float f; uint32_t u; } v; v.u = ((uint32_t)h) << 16; return v.f;
 }
 
+// ---- test-time augmentation (augment.hip, stem_conv.hip) ----
+// Channel c of pixel (y, x) of the network input of a scaled pass: scale_img(flip(u8 / 255)) [UPSTREAM utils/torch_utils.py scale_img] --
+// the bilinear sample inside h x w, 0.447 in the padding up to hp x wp, 0 (the conv's own zero padding) outside.  img: one uint8 RGB tile
+// of width W0.  Every rounding is explicit (no contraction): h0 (w0 x00 + w1 x01) + h1 (w0 x10 + w1 x11), as PyTorch's CPU kernel.
+__device__ static inline float aq_aug_value(const uint8_t* img, int W0, const aq_tap* ytab, const aq_tap* xtab, int h, int w, int hp, int wp,
+                                            int y, int x, int c) {
+    if (y < 0 || y >= hp || x < 0 || x >= wp) return 0.0f;
+    if (y >= h || x >= w) return 0.447f;
+    const aq_tap ty = ytab[y], tx = xtab[x];
+    const uint8_t* r0 = img + (size_t)ty.i0 * W0 * 3;
+    const uint8_t* r1 = img + (size_t)ty.i1 * W0 * 3;
+    const float x00 = (float)r0[tx.i0 * 3 + c] / 255.0f, x01 = (float)r0[tx.i1 * 3 + c] / 255.0f;
+    const float x10 = (float)r1[tx.i0 * 3 + c] / 255.0f, x11 = (float)r1[tx.i1 * 3 + c] / 255.0f;
+    const float t0 = __fadd_rn(__fmul_rn(tx.l0, x00), __fmul_rn(tx.l1, x01));
+    const float t1 = __fadd_rn(__fmul_rn(tx.l0, x10), __fmul_rn(tx.l1, x11));
+    return __fadd_rn(__fmul_rn(ty.l0, t0), __fmul_rn(ty.l1, t1));
+}
+// Launches the fill of `out` taps (aq_augment_taps's arithmetic, on the device: the engine's augmented call writes its tables into its
+// workspace instead of copying them from host memory).
+int aq_augment_fill_taps(aq_tap* taps_dev, int in, int out, int flip, hipStream_t stream);
+
 // ---- conv kernel parameter block (conv_igemm.hip) ----
 struct ConvParams {
     const char* in;      // input tensor base + first-channel offset (bytes)

@@ -29,21 +29,34 @@ struct DecodeParams {
     float* cand_rows;      // [B][cap][no] decoded rows of the candidates (same order as cand) or null
     int32_t* cand_count;   // [B]
     int cap;
+    // AUG (one pass of an --augment call): levels outside lmask are skipped, pass row n is row base + n of the concatenated prediction
+    // (pred pitch pred_rows), xywh are divided by scale and x = flip_w - x when flip_w != 0
+    int lmask, base, pred_rows;
+    float scale, flip_w;
 };
 
 __device__ __forceinline__ float sigmoidf_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+template <bool AUG = false>
 __device__ __forceinline__ void decode_row(const DecodeParams& p, const float* src, int lvl, int a, int x, int y,
                                            float obj, float* dst) {
     // xy = (xy * 2 + grid) * stride, grid = index - 0.5 ; wh = (wh * 2) ** 2 * anchor_grid
     const float s0 = sigmoidf_ref(src[0]), s1 = sigmoidf_ref(src[1]);
     const float s2 = sigmoidf_ref(src[2]), s3 = sigmoidf_ref(src[3]);
     const float gx = (float)x - 0.5f, gy = (float)y - 0.5f;
-    dst[0] = (s0 * 2.0f + gx) * p.stride[lvl];
-    dst[1] = (s1 * 2.0f + gy) * p.stride[lvl];
+    float bx = (s0 * 2.0f + gx) * p.stride[lvl];
+    float by = (s1 * 2.0f + gy) * p.stride[lvl];
     const float tw = s2 * 2.0f, th = s3 * 2.0f;
-    dst[2] = (tw * tw) * p.anchor[lvl][a][0];
-    dst[3] = (th * th) * p.anchor[lvl][a][1];
+    float bw = (tw * tw) * p.anchor[lvl][a][0];
+    float bh = (th * th) * p.anchor[lvl][a][1];
+    if constexpr (AUG) {                                 // [UPSTREAM models/yolo.py _descale_pred]: p[..., :4] /= scale; x = img_size[1] - x
+        bx = bx / p.scale; by = by / p.scale; bw = bw / p.scale; bh = bh / p.scale;
+        if (p.flip_w != 0.0f) bx = p.flip_w - bx;
+    }
+    dst[0] = bx;
+    dst[1] = by;
+    dst[2] = bw;
+    dst[3] = bh;
     dst[4] = obj;
     for (int c = 0; c < p.nc; ++c) dst[5 + c] = sigmoidf_ref(src[5 + c]);
 }
@@ -54,6 +67,7 @@ __device__ __forceinline__ void decode_row(const DecodeParams& p, const float* s
 // to the compact candidate list that NMS reads.
 constexpr int kDecPerLane = 4;                               // candidates per lane: their head-map loads are issued together
 
+template <bool AUG = false>
 __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
     // grid = (ceil(N / (256 * kDecPerLane)), B).  Passing candidates take a slot from an LDS counter; ONE global atomic per block
     // reserves the block's range in the image's compact list (same-address global atomics serialise).
@@ -74,6 +88,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
             int m = w;                                     // position in the pixel-major walk of this image
             const int na = p.na;
             lvl[k] = m >= p.off[2] ? 2 : (m >= p.off[1] ? 1 : 0);
+            if (AUG && !((p.lmask >> lvl[k]) & 1)) continue;   // a level _clip_augmented drops
             m -= p.off[lvl[k]];
             const int ny = p.ny[lvl[k]], nx = p.nx[lvl[k]];
             const int pix = (int)((unsigned)m / (unsigned)na);
@@ -91,7 +106,9 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
         obj[k] = 0.f;
         if (src[k]) {
             obj[k] = sigmoidf_ref(raw[k]);
-            if (p.pred) decode_row(p, src[k], lvl[k], a[k], x[k], y[k], obj[k], p.pred + ((long long)b * N + n[k]) * p.no);
+            if (p.pred)
+                decode_row<AUG>(p, src[k], lvl[k], a[k], x[k], y[k], obj[k],
+                                p.pred + (AUG ? (long long)b * p.pred_rows + p.base + n[k] : (long long)b * N + n[k]) * p.no);
             pass[k] = p.cand && obj[k] > p.conf_thres;
             if (pass[k]) local[k] = atomicAdd(&s_cnt, 1);
         }
@@ -104,9 +121,9 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
         if (pass[k]) {
             const int pos = s_base + local[k];
             if (pos < p.cap) {
-                p.cand[(long long)b * p.cap + pos] = n[k];
+                p.cand[(long long)b * p.cap + pos] = AUG ? p.base + n[k] : n[k];
                 if (p.cand_rows)
-                    decode_row(p, src[k], lvl[k], a[k], x[k], y[k], obj[k], p.cand_rows + ((long long)b * p.cap + pos) * p.no);
+                    decode_row<AUG>(p, src[k], lvl[k], a[k], x[k], y[k], obj[k], p.cand_rows + ((long long)b * p.cap + pos) * p.no);
             }
         }
     }
@@ -422,9 +439,11 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
-extern "C" int aq_detect_decode(const float* const head_dev[3], int head_ld, int B, int H, int W, int nc, int na,
-                                const float* anchors_px, const float* stride, float* pred_dev, float conf_thres,
-                                int32_t* cand_dev, float* cand_rows_dev, int32_t* cand_count_dev, int cand_cap, void* stream) {
+namespace {
+int detect_decode_launch(const float* const head_dev[3], int head_ld, int B, int H, int W, int nc, int na,
+                         const float* anchors_px, const float* stride, float* pred_dev, float conf_thres,
+                         int32_t* cand_dev, float* cand_rows_dev, int32_t* cand_count_dev, int cand_cap, bool aug, int level_mask,
+                         int cand_base, int rows_per_image, float scale, float flip_w, void* stream) {
     AQ_REQUIRE(head_dev && head_dev[0] && head_dev[1] && head_dev[2], "decode: null head pointer");
     AQ_REQUIRE(na >= 1 && na <= 8 && nc >= 1 && head_ld >= na * (nc + 5), "decode: bad na=%d nc=%d head_ld=%d", na, nc, head_ld);
     AQ_REQUIRE(pred_dev || cand_dev, "decode: nothing to write");
@@ -446,12 +465,41 @@ extern "C" int aq_detect_decode(const float* const head_dev[3], int head_ld, int
     p.off[3] = off;
     p.pred = pred_dev; p.conf_thres = conf_thres; p.cand = cand_dev; p.cand_rows = cand_rows_dev;
     p.cand_count = cand_count_dev; p.cap = cand_cap;
+    p.lmask = level_mask; p.base = cand_base; p.pred_rows = rows_per_image; p.scale = scale; p.flip_w = flip_w;
+    if (aug) {
+        AQ_REQUIRE(scale > 0.0f && flip_w >= 0.0f && (level_mask & ~7) == 0, "decode_aug: scale %g flip_w %g level mask %d", scale, flip_w, level_mask);
+        for (int l = 0; l < 3; ++l)                      // every row written lands inside [0, rows_per_image) and [0, cand_cap)
+            AQ_REQUIRE(!((level_mask >> l) & 1) || (cand_base + p.off[l] >= 0 && cand_base + p.off[l + 1] <= rows_per_image && cand_base + p.off[l + 1] <= (cand_dev ? cand_cap : rows_per_image)),
+                       "decode_aug: level %d rows [%d, %d) fall outside the %d rows per image", l, cand_base + p.off[l], cand_base + p.off[l + 1], rows_per_image);
+        AQ_REQUIRE(B <= 65535, "decode: batch too large for the grid");
+        hipLaunchKernelGGL(decode_kernel<true>, dim3((unsigned)((off + 256 * kDecPerLane - 1) / (256 * kDecPerLane)), (unsigned)B), dim3(256), 0,
+                           (hipStream_t)stream, p);
+        AQ_CHECK_HIP(hipGetLastError());
+        return AQ_OK;
+    }
     if (cand_dev) AQ_CHECK_HIP(hipMemsetAsync(cand_count_dev, 0, sizeof(int32_t) * B, (hipStream_t)stream));
     AQ_REQUIRE(B <= 65535, "decode: batch too large for the grid");
-    hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((off + 256 * kDecPerLane - 1) / (256 * kDecPerLane)), (unsigned)B), dim3(256), 0,
+    hipLaunchKernelGGL(decode_kernel<false>, dim3((unsigned)((off + 256 * kDecPerLane - 1) / (256 * kDecPerLane)), (unsigned)B), dim3(256), 0,
                        (hipStream_t)stream, p);
     AQ_CHECK_HIP(hipGetLastError());
     return AQ_OK;
+}
+}  // namespace
+
+extern "C" int aq_detect_decode(const float* const head_dev[3], int head_ld, int B, int H, int W, int nc, int na,
+                                const float* anchors_px, const float* stride, float* pred_dev, float conf_thres,
+                                int32_t* cand_dev, float* cand_rows_dev, int32_t* cand_count_dev, int cand_cap, void* stream) {
+    return detect_decode_launch(head_dev, head_ld, B, H, W, nc, na, anchors_px, stride, pred_dev, conf_thres, cand_dev, cand_rows_dev, cand_count_dev,
+                                cand_cap, false, 7, 0, 0, 1.0f, 0.0f, stream);
+}
+
+// One pass of an --augment call (see aq_engine.h): the levels of level_mask, rows at cand_base + n, de-scaled; appends to cand_count_dev.
+extern "C" int aq_detect_decode_aug(const float* const head_dev[3], int head_ld, int B, int H, int W, int nc, int na, const float* anchors_px,
+                                    const float* stride, int level_mask, int cand_base, int rows_per_image, float scale, float flip_w,
+                                    float* pred_dev, float conf_thres, int32_t* cand_dev, float* cand_rows_dev, int32_t* cand_count_dev,
+                                    int cand_cap, void* stream) {
+    return detect_decode_launch(head_dev, head_ld, B, H, W, nc, na, anchors_px, stride, pred_dev, conf_thres, cand_dev, cand_rows_dev, cand_count_dev,
+                                cand_cap, true, level_mask, cand_base, rows_per_image, scale, flip_w, stream);
 }
 
 extern "C" size_t aq_nms_scratch_bytes(int B, int N) {

@@ -165,14 +165,22 @@ struct aq_engine {
     std::vector<int> conv_cfg;          // per op override, -1 = heuristic
     int nms_agnostic = 0;               // aq_engine_set_nms_options
     unsigned long long nms_cls_lo = ~0ULL, nms_cls_hi = ~0ULL;
-    std::vector<int> tuned_cfg;         // per op result of aq_engine_autotune for (tuned_B, tuned_H, tuned_W)
-    int tuned_B = 0, tuned_H = 0, tuned_W = 0;
+    // Tuned tables, one per tile geometry (H, W): per op results of aq_engine_autotune / aq_engine_set_tuned_table, which replace the
+    // entry of their geometry.  A launch uses the entry of the geometry it runs at (each pass of an augmented call its own), else the heuristic.
+    struct Tuned { int B = 0, H = 0, W = 0; std::vector<int> cfg; };
+    std::vector<Tuned> tuned;
+    int tuned_cur = -1;                 // entry of the most recent autotune / set_tuned_table (aq_engine_get_conv_config reports it)
+    bool tuning = false;                // aq_engine_autotune's reference pass runs on the heuristic
     void* zero_page = nullptr;
     // workspace layout of the last sizing / call
     int lay_B = 0, lay_H = 0, lay_W = 0;
+    bool lay_aug = false;               // the augmented layout (aq_engine_*_augment): activations for the largest pass, candidates for N_aug
+    int run_H = 0, run_W = 0;           // network-input geometry of the plan being launched (the pass's, in an augmented call)
     std::vector<TensorPlace> place;
-    size_t off_pred = 0, off_cand = 0, off_cand_rows = 0, off_cand_count = 0, off_cand_wide = 0, off_nms = 0, total_bytes = 0;
-    int N = 0;
+    size_t off_pred = 0, off_cand = 0, off_cand_rows = 0, off_cand_count = 0, off_cand_wide = 0, off_nms = 0, off_taps = 0, total_bytes = 0;
+    int N = 0;                          // rows per image of the prediction (N_aug in the augmented layout)
+    aq_augment_pass aug[3] = {};        // augmented layout: the three passes
+    std::vector<int> aug_family[3], aug_cfg[3];   // per pass of the last augmented call: aq_engine_last_launch's records
     void* last_ws = nullptr;
     const uint8_t* last_tiles = nullptr;
     float* calib_amax = nullptr;        // device float[n_ops] while aq_engine_calibrate_amax runs: max |output| of every bf16 conv op
@@ -186,10 +194,38 @@ struct aq_engine {
 
 namespace {
 
-int layout(aq_engine* e, int B, int H, int W) {
+// The tensors' spatial sizes for a network input of H x W (their offsets and bytes stay those of the layout).
+void set_dims(aq_engine* e, int H, int W) {
+    for (size_t t = 0; t < e->tensors.size(); ++t) {
+        e->place[t].h = H / e->tensors[t].down;
+        e->place[t].w = W / e->tensors[t].down;
+    }
+    e->run_H = H; e->run_W = W;
+}
+
+constexpr int kNmsRowLimit = 1 << 17;   // aq_nms: N < 2^17 rows per image
+
+// aug: the augmented layout -- activation tensors placed for the largest pass (pass 0, H x W) and reused by each pass in turn, the
+// prediction / candidate / NMS areas sized for N_aug, then the tap tables of the two scaled passes.
+int layout(aq_engine* e, int B, int H, int W, bool aug = false) {
     AQ_REQUIRE(B > 0 && H >= 32 && W >= 32 && H % 32 == 0 && W % 32 == 0,
                "tile size must be a positive multiple of the max stride 32 (got B=%d H=%d W=%d)", B, H, W);
-    if (e->lay_B == B && e->lay_H == H && e->lay_W == W) return AQ_OK;
+    if (e->lay_B == B && e->lay_H == H && e->lay_W == W && e->lay_aug == aug) {
+        if (e->run_H != H || e->run_W != W) set_dims(e, H, W);   // (only after a pass of an augmented call ran at its own size)
+        return AQ_OK;
+    }
+    // A refused geometry leaves the engine's layout as it was: the passes are derived into a local copy and only installed, together with
+    // the layout they belong to, once every check has passed (a cached layout must never meet another geometry's passes).
+    int n_aug = 0;
+    aq_augment_pass passes[3] = {};
+    if (aug) {
+        const int rc = aq_augment_geometry(H, W, e->desc.na, passes, &n_aug);
+        if (rc) return rc;
+        AQ_REQUIRE(n_aug < kNmsRowLimit, "augment: %d x %d tiles give %d prediction rows per image; the NMS kernel takes fewer than %d",
+                   H, W, n_aug, kNmsRowLimit);
+    }
+    e->lay_B = 0;                                        // (invalid until the layout below is complete)
+    if (aug) memcpy(e->aug, passes, sizeof(passes));
     const int eb = aq_elem_bytes(e->desc.precision);
     size_t off = 0;
     e->place.assign(e->tensors.size(), TensorPlace());
@@ -208,6 +244,7 @@ int layout(aq_engine* e, int B, int H, int W) {
         const int s = (int)e->desc.stride[l];
         N += e->desc.na * (H / s) * (W / s);
     }
+    if (aug) N = n_aug;
     e->N = N;
     e->off_pred = off; off += align_up((size_t)B * N * (e->desc.nc + 5) * sizeof(float), kAlign);
     e->off_cand = off; off += align_up((size_t)B * N * sizeof(int32_t), kAlign);
@@ -215,9 +252,29 @@ int layout(aq_engine* e, int B, int H, int W) {
     e->off_cand_count = off; off += align_up((size_t)B * sizeof(int32_t), kAlign);
     e->off_cand_wide = off; off += align_up((size_t)B * kCountStride * sizeof(int32_t), kAlign);   // fused heads: counters 4 KB apart
     e->off_nms = off; off += align_up(aq_nms_scratch_bytes(B, N), kAlign);
+    e->off_taps = off;
+    if (aug) off += align_up(sizeof(aq_tap) * (e->aug[1].h + e->aug[1].w + e->aug[2].h + e->aug[2].w), kAlign);
     e->total_bytes = off;
-    e->lay_B = B; e->lay_H = H; e->lay_W = W;
+    e->lay_B = B; e->lay_H = H; e->lay_W = W; e->lay_aug = aug;
+    e->run_H = H; e->run_W = W;
     return AQ_OK;
+}
+
+// The tuned table of the geometry being launched, if any.
+const aq_engine::Tuned* tuned_for(const aq_engine* e) {
+    if (e->tuning) return nullptr;
+    for (const aq_engine::Tuned& t : e->tuned)
+        if (t.H == e->run_H && t.W == e->run_W) return &t;
+    return nullptr;
+}
+
+// Stores a table for (B, H, W): replaces the entry of that geometry, else adds one.
+void store_tuned(aq_engine* e, int B, int H, int W, const std::vector<int>& cfg) {
+    int i = 0;
+    while (i < (int)e->tuned.size() && !(e->tuned[i].H == H && e->tuned[i].W == W)) ++i;
+    if (i == (int)e->tuned.size()) e->tuned.emplace_back();
+    e->tuned[i].B = B; e->tuned[i].H = H; e->tuned[i].W = W; e->tuned[i].cfg = cfg;
+    e->tuned_cur = i;
 }
 
 inline char* tptr(aq_engine* e, void* ws, const uint8_t* tiles, int t) {
@@ -262,11 +319,11 @@ int run_conv(aq_engine* e, int oi, void* ws, const uint8_t* tiles, int B, hipStr
                                     pw.w_f8, pw.sb_f8, B, ps.h, ps.w, op.act, stream);
         }
     }
-    if (force_cfg < 0 && !no_table && e->conv_cfg[oi] < 0 && e->tuned_B > 0 && B != e->tuned_B && e->tuned_H == e->lay_H && e->tuned_W == e->lay_W &&
-        e->tuned_cfg[oi] >= 0) {
+    const aq_engine::Tuned* tt = no_table ? nullptr : tuned_for(e);
+    if (force_cfg < 0 && !no_table && e->conv_cfg[oi] < 0 && tt && B != tt->B && tt->cfg[oi] >= 0) {
         // A table entry was validated (and timed) at tuned_B only.  Should it reject another batch size -- the ragged last batch of a
         // sweep, a rank with fewer tiles -- that batch runs on the heuristic shape instead of ending the sweep.
-        const int rc = run_conv(e, oi, ws, tiles, B, stream, e->tuned_cfg[oi]);
+        const int rc = run_conv(e, oi, ws, tiles, B, stream, tt->cfg[oi]);
         if (rc != AQ_ERR_INVALID) return rc;
         return run_conv(e, oi, ws, tiles, B, stream, -1, true);
     }
@@ -297,7 +354,7 @@ int run_conv(aq_engine* e, int oi, void* ws, const uint8_t* tiles, int B, hipStr
     // The tuned table serves EVERY batch size of its tile geometry (a sweep's ragged last batch, a rank with fewer tiles): a kernel's
     // accumulation order per output element does not depend on the batch, so a tile's result no longer depends on which batch it
     // landed in (before, batches of another size fell back to the heuristic kernels and could round differently in bf16).
-    if (cfg < 0 && !no_table && e->tuned_B > 0 && e->tuned_H == e->lay_H && e->tuned_W == e->lay_W) cfg = e->tuned_cfg[oi];
+    if (cfg < 0 && tt) cfg = tt->cfg[oi];
     if (cfg == AQ_CONV_CFG_DIRECT3X3S2) {
         if (pw.direct_cfg != cfg) { aq_set_error("conv op %d has no direct 3x3/s2 form", oi); return AQ_ERR_INVALID; }
         note_launch(e, oi, AQ_FAM_DIRECT3X3S2, cfg);
@@ -352,27 +409,55 @@ int run_conv(aq_engine* e, int oi, void* ws, const uint8_t* tiles, int B, hipStr
     return aq_launch_conv(p, pw.x3 ? (int)AQ_F16X3 : prec, out_f32, cfg, stream);
 }
 
+// Do the three Detect head convs run fused with their decode (bf16 engines whose heads all have a fused form) on the NMS path?
+bool heads_fused(const aq_engine* e) {
+    int n_heads = 0;
+    for (size_t oi = 0; oi < e->ops.size(); ++oi)
+        if (e->ops[oi].kind == AQ_OP_CONV && e->ops[oi].level >= 0) {
+            ++n_heads;
+            if (!e->packed[oi].w_head) return false;
+        }
+    return n_heads == 3;
+}
+
+// One pass of an augmented call (run_augment): its geometry, the u8 tiles' size and the pass's tap tables in the workspace.
+struct AugRun {
+    int pass;
+    const aq_augment_pass* ps;
+    int H0, W0;
+    const aq_tap* ytab;
+    const aq_tap* xtab;
+};
+
 // Runs plan ops [first, last) -- the whole plan for every entry point but aq_engine_run_ops, which steps through it in pieces.  Every
 // decision that spans ops (stem + down-block as one launch, fused heads, the counter memset before the first head and the gather behind
 // the third) is made from the whole plan, not from the range, so a plan run in pieces launches exactly what one call launches.
+// ar != nullptr: one pass of an augmented call at the pass's network input H x W -- run_augment has laid out the workspace, zeroed the
+// candidate counters and runs the gather and NMS after the last pass; a scaled pass samples its input from the u8 tiles.
 int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, size_t ws_bytes,
              float* pred_out, aq_det* dets, int32_t* counts, float conf, float iou, int max_det, hipStream_t stream,
-             int first = 0, int last = -1) {
+             int first = 0, int last = -1, const AugRun* ar = nullptr) {
     AQ_REQUIRE(e && tiles && ws, "infer: null pointer");
     const int n_ops = (int)e->ops.size();
     if (last < 0) last = n_ops;
     AQ_REQUIRE(0 <= first && first <= last && last <= n_ops, "run_ops: range [%d, %d) is not inside the plan's %d ops", first, last, n_ops);
-    int rc = layout(e, B, H, W);
-    if (rc) return rc;
-    if (ws_bytes < e->total_bytes) {
-        aq_set_error("workspace too small: need %zu bytes, got %zu", e->total_bytes, ws_bytes);
-        return AQ_ERR_WORKSPACE;
+    int rc = AQ_OK;
+    if (!ar) {
+        rc = layout(e, B, H, W);
+        if (rc) return rc;
+        if (ws_bytes < e->total_bytes) {
+            aq_set_error("workspace too small: need %zu bytes, got %zu", e->total_bytes, ws_bytes);
+            return AQ_ERR_WORKSPACE;
+        }
     }
+    const bool scaled = ar && ar->pass > 0;
+    const int aug_base = ar ? ar->ps->out_first - ar->ps->keep_first : 0;   // pass row n -> row aug_base + n of the concatenation
+    const float aug_scale = ar ? ar->ps->scale : 1.0f, aug_flip_w = ar && ar->ps->flip ? (float)ar->W0 : 0.0f;
     e->last_ws = ws; e->last_tiles = tiles;
     const int prec = e->desc.precision;
     const bool whole = first == 0 && last == n_ops;
     hipEvent_t* ev = nullptr;                            // per-op timing covers whole calls only
-    if (whole && e->prof && e->ring > 0) ev = e->ev.data() + (size_t)(e->prof_calls % e->ring) * (n_ops + 1);
+    if (whole && !ar && e->prof && e->ring > 0) ev = e->ev.data() + (size_t)(e->prof_calls % e->ring) * (n_ops + 1);
     float* pred = pred_out ? pred_out : (float*)((char*)ws + e->off_pred);
     int32_t* cand = (int32_t*)((char*)ws + e->off_cand);
     int32_t* cand_count = (int32_t*)((char*)ws + e->off_cand_count);
@@ -385,16 +470,11 @@ int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, 
     const char* use_sd = getenv("AQ_STEMDOWN");
     const bool stemdown = use_sd && *use_sd == '1' && prec == AQ_BF16 && n_ops > 2 && e->ops[0].kind == AQ_OP_STEM && e->ops[1].kind == AQ_OP_DOWNBLOCK &&
                           e->ops[0].dst.channels == 48 && e->ops[1].src.tensor == e->ops[0].dst.tensor && e->ops[1].src.ch_off == e->ops[0].dst.ch_off &&
-                          aq_stemdown_supported(H, W) && ((uintptr_t)tiles & 3) == 0;
+                          aq_stemdown_supported(H, W) && ((uintptr_t)tiles & 3) == 0 && !scaled;
     // the NMS path of a bf16 engine whose three head convs all have a fused form skips the fp32 head maps
-    bool fuse_heads = dets != nullptr, heads_started = false;
-    int n_heads = 0, heads_done = 0;
-    for (int oi = 0; oi < n_ops; ++oi)
-        if (e->ops[oi].kind == AQ_OP_CONV && e->ops[oi].level >= 0) {
-            ++n_heads;
-            if (!e->packed[oi].w_head) fuse_heads = false;
-        }
-    if (n_heads != 3) fuse_heads = false;
+    const bool fuse_heads = dets != nullptr && heads_fused(e);
+    bool heads_started = ar != nullptr;                  // (an augmented call zeroes the counters once, before its first pass)
+    int heads_done = 0;
     for (int oi = 0; oi < first; ++oi)                   // heads an earlier piece of the plan already ran
         if (fuse_heads && e->ops[oi].kind == AQ_OP_CONV && e->ops[oi].level >= 0) {
             heads_started = true;
@@ -412,9 +492,17 @@ int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, 
         }
         switch (op.kind) {
         case AQ_OP_PREPROCESS:
-            rc = aq_preprocess_s2d(tiles, tptr(e, ws, tiles, op.dst.tensor), B, H, W, prec, stream);
+            if (scaled)
+                rc = aq_preprocess_s2d_scaled(tiles, ar->H0, ar->W0, ar->ytab, ar->xtab, ar->ps->h, ar->ps->w, tptr(e, ws, tiles, op.dst.tensor), B, H, W,
+                                              prec, stream);
+            else
+                rc = aq_preprocess_s2d(tiles, tptr(e, ws, tiles, op.dst.tensor), B, H, W, prec, stream);
             break;
         case AQ_OP_CONV:
+            if (ar && op.level >= 0 && !((ar->ps->level_mask >> op.level) & 1)) {
+                note_launch(e, oi, AQ_FAM_NONE);         // a level _clip_augmented drops: neither its head conv nor its decode runs
+                break;
+            }
             if (fuse_heads && op.level >= 0) {
                 // Detect level fused with its decode (csrc/head_decode.hip): candidates go straight to the compact list NMS reads
                 int32_t* wide = (int32_t*)((char*)ws + e->off_cand_wide);
@@ -431,6 +519,12 @@ int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, 
                     anchors[2 * a + 1] = e->desc.anchors_px[op.level][a][1];
                 }
                 note_launch(e, oi, AQ_FAM_HEAD_DECODE);
+                if (ar) {
+                    rc = aq_head_decode_aug(tptr(e, ws, tiles, op.src.tensor), e->tensors[op.src.tensor].channels, op.src.ch_off, op.src.channels,
+                                            e->packed[oi].w_head, B, pl.h, pl.w, aug_base + off, e->desc.stride[op.level], anchors, e->desc.nc, e->desc.na,
+                                            conf, aug_scale, aug_flip_w, cand, cand_rows, wide, kCountStride, e->N, stream);
+                    break;                               // (run_augment gathers the counters after the last pass)
+                }
                 rc = aq_head_decode(tptr(e, ws, tiles, op.src.tensor), e->tensors[op.src.tensor].channels, op.src.ch_off, op.src.channels,
                                     e->packed[oi].w_head, B, pl.h, pl.w, off, e->desc.stride[op.level], anchors, e->desc.nc, e->desc.na, conf,
                                     cand, cand_rows, wide, kCountStride, e->N, stream);
@@ -447,6 +541,12 @@ int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, 
         case AQ_OP_STEM:
             note_launch(e, oi, AQ_FAM_STEM);
             if (stemdown) break;                         // computed inside the down-block launch below
+            if (scaled) {
+                rc = aq_stem_conv_scaled(tiles, ar->H0, ar->W0, ar->ytab, ar->xtab, ar->ps->h, ar->ps->w, tptr(e, ws, tiles, op.dst.tensor),
+                                         e->tensors[op.dst.tensor].channels, op.dst.ch_off, op.dst.channels, e->packed[oi].w, e->packed[oi].bias,
+                                         B, H, W, op.act, prec, stream);
+                break;
+            }
             rc = aq_stem_conv(tiles, tptr(e, ws, tiles, op.dst.tensor), e->tensors[op.dst.tensor].channels, op.dst.ch_off,
                               op.dst.channels, e->packed[oi].w, e->packed[oi].bias, B, H, W, op.act, prec, stream);
             break;
@@ -495,13 +595,20 @@ int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, 
                     anchors[(l * e->desc.na + a) * 2 + 1] = e->desc.anchors_px[l][a][1];
                 }
             const bool want_nms = dets != nullptr;
+            if (ar) {
+                rc = aq_detect_decode_aug(heads, e->tensors[e->desc.head_tensor[0]].channels, B, H, W, e->desc.nc, e->desc.na, anchors,
+                                          e->desc.stride, ar->ps->level_mask, aug_base, e->N, aug_scale, aug_flip_w, want_nms ? nullptr : pred,
+                                          conf, want_nms ? cand : nullptr, want_nms ? cand_rows : nullptr, want_nms ? cand_count : nullptr,
+                                          e->N, stream);
+                break;
+            }
             rc = aq_detect_decode(heads, e->tensors[e->desc.head_tensor[0]].channels, B, H, W, e->desc.nc, e->desc.na,
                                   anchors, e->desc.stride, want_nms ? nullptr : pred, conf, want_nms ? cand : nullptr,
                                   want_nms ? cand_rows : nullptr, want_nms ? cand_count : nullptr, e->N, stream);
             break;
         }
         case AQ_OP_NMS:
-            if (dets)
+            if (dets && !ar)                             // (an augmented call runs NMS once, over the three passes' candidates)
                 rc = aq_nms_opts(cand_rows, e->N, B, e->N, e->desc.nc, conf, iou, max_det, cand, cand_count, e->N,
                                  (char*)ws + e->off_nms, dets, counts, e->nms_agnostic, e->nms_cls_lo, e->nms_cls_hi, stream);
             break;
@@ -517,6 +624,60 @@ int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, 
         e->prof_calls++;
     }
     return AQ_OK;
+}
+
+// Test-time augmentation [UPSTREAM models/yolo.py DetectionModel._forward_augment]: the three passes of aq_augment_geometry on one stream,
+// each through the plan at its own network input (pass 0 is the plain pass; passes 1, 2 sample scale_img(flip(x)) inside the stem or
+// preprocess), their candidates appended to one list in the rows of the concatenated, clipped prediction, then one NMS over all of them.
+int run_augment(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, size_t ws_bytes, float* pred_out, aq_det* dets,
+                int32_t* counts, float conf, float iou, int max_det, hipStream_t stream) {
+    AQ_REQUIRE(e && tiles && ws, "augment: null pointer");
+    for (const PackedW& pw : e->packed)
+        AQ_REQUIRE(!pw.w_f8, "augment: this engine has fp8 activation scales installed; they were calibrated at one geometry, and the "
+                             "augmented passes run at three");
+    int rc = layout(e, B, H, W, true);
+    if (rc) return rc;
+    AQ_REQUIRE(e->aug[0].hp == H && e->aug[0].wp == W, "augment: internal error, the passes do not belong to the %d x %d layout", H, W);
+    if (ws_bytes < e->total_bytes) {
+        aq_set_error("workspace too small: need %zu bytes, got %zu (aq_engine_workspace_bytes_augment)", e->total_bytes, ws_bytes);
+        return AQ_ERR_WORKSPACE;
+    }
+    aq_tap* taps = (aq_tap*)((char*)ws + e->off_taps);
+    aq_tap* ytab[3] = {nullptr, nullptr, nullptr};
+    aq_tap* xtab[3] = {nullptr, nullptr, nullptr};
+    for (int i = 1; i < 3; ++i) {                        // [UPSTREAM scale_img]: F.interpolate(x.flip(3) if flip else x, (h, w), bilinear)
+        const aq_augment_pass& ps = e->aug[i];
+        ytab[i] = taps;
+        xtab[i] = taps + ps.h;
+        taps += ps.h + ps.w;
+        rc = aq_augment_fill_taps(ytab[i], H, ps.h, 0, stream);
+        if (!rc) rc = aq_augment_fill_taps(xtab[i], W, ps.w, ps.flip, stream);
+        if (rc) return rc;
+    }
+    int32_t* cand_count = (int32_t*)((char*)ws + e->off_cand_count);
+    int32_t* wide = (int32_t*)((char*)ws + e->off_cand_wide);
+    const bool fuse = dets && heads_fused(e);
+    if (dets) {                                          // the three passes append to one candidate list
+        AQ_CHECK_HIP(hipMemsetAsync(fuse ? wide : cand_count, 0, sizeof(int32_t) * B * (fuse ? kCountStride : 1), stream));
+    }
+    float* pred = pred_out ? pred_out : (float*)((char*)ws + e->off_pred);
+    for (int i = 0; i < 3 && !rc; ++i) {
+        const aq_augment_pass& ps = e->aug[i];
+        const AugRun ar{i, &ps, H, W, ytab[i], xtab[i]};
+        set_dims(e, ps.hp, ps.wp);
+        if (e->last_family.size() == e->ops.size()) { e->last_family.assign(e->ops.size(), AQ_FAM_NONE); e->last_cfg.assign(e->ops.size(), -1); }
+        rc = run_plan(e, tiles, B, ps.hp, ps.wp, ws, ws_bytes, pred, dets, counts, conf, iou, max_det, stream, 0, -1, &ar);
+        e->aug_family[i] = e->last_family;
+        e->aug_cfg[i] = e->last_cfg;
+    }
+    set_dims(e, H, W);
+    if (rc || !dets) return rc;
+    if (fuse) {
+        rc = aq_head_counts_gather(wide, kCountStride, cand_count, B, stream);
+        if (rc) return rc;
+    }
+    return aq_nms_opts((float*)((char*)ws + e->off_cand_rows), e->N, B, e->N, e->desc.nc, conf, iou, max_det, (int32_t*)((char*)ws + e->off_cand),
+                       cand_count, e->N, (char*)ws + e->off_nms, dets, counts, e->nms_agnostic, e->nms_cls_lo, e->nms_cls_hi, stream);
 }
 
 }  // namespace
@@ -619,7 +780,6 @@ extern "C" int aq_engine_create(const aq_model_desc* d, int device, aq_engine** 
     e->desc.ops = e->ops.data();
     e->packed.resize(e->ops.size());
     e->conv_cfg.assign(e->ops.size(), -1);
-    e->tuned_cfg.assign(e->ops.size(), -1);
     const int eb = aq_elem_bytes(d->precision);
     auto fail = [&](int rc) { aq_engine_destroy(e); return rc; };
     if (hipMalloc(&e->zero_page, 4096) != hipSuccess || hipMemset(e->zero_page, 0, 4096) != hipSuccess) {
@@ -854,6 +1014,36 @@ extern "C" int aq_engine_infer(aq_engine* e, const uint8_t* tiles_dev, int B, in
     return run_plan(e, tiles_dev, B, H, W, ws, ws_bytes, nullptr, dets_dev, counts_dev, conf, iou, max_det, (hipStream_t)stream);
 }
 
+extern "C" int aq_engine_workspace_bytes_augment(aq_engine* e, int max_batch, int H, int W, size_t* bytes) {
+    AQ_REQUIRE(e && bytes, "workspace_bytes_augment: null pointer");
+    int rc = layout(e, max_batch, H, W, true);
+    if (rc) return rc;
+    *bytes = e->total_bytes;
+    return AQ_OK;
+}
+
+extern "C" int aq_engine_infer_augment(aq_engine* e, const uint8_t* tiles_dev, int B, int H, int W, void* ws, size_t ws_bytes,
+                                       aq_det* dets_dev, int32_t* counts_dev, float conf, float iou, int max_det, void* stream) {
+    AQ_REQUIRE(dets_dev && counts_dev, "infer_augment: null output pointer");
+    AQ_REQUIRE(max_det > 0 && conf >= 0.f && conf <= 1.f && iou >= 0.f && iou <= 1.f,
+               "infer_augment: bad thresholds conf=%g iou=%g max_det=%d", conf, iou, max_det);
+    return run_augment(e, tiles_dev, B, H, W, ws, ws_bytes, nullptr, dets_dev, counts_dev, conf, iou, max_det, (hipStream_t)stream);
+}
+
+extern "C" int aq_engine_forward_raw_augment(aq_engine* e, const uint8_t* tiles_dev, int B, int H, int W, void* ws, size_t ws_bytes,
+                                             float* pred_dev, void* stream) {
+    AQ_REQUIRE(pred_dev, "forward_raw_augment: null output pointer");
+    return run_augment(e, tiles_dev, B, H, W, ws, ws_bytes, pred_dev, nullptr, nullptr, 0.f, 0.f, 1, (hipStream_t)stream);
+}
+
+extern "C" int aq_engine_last_launch_augment(aq_engine* e, int pass, int op, int* family, int* cfg) {
+    AQ_REQUIRE(e && family && pass >= 0 && pass < 3 && op >= 0 && op < (int)e->ops.size(), "last_launch_augment: bad argument");
+    const bool have = e->aug_family[pass].size() == e->ops.size();
+    *family = have ? e->aug_family[pass][op] : AQ_FAM_NONE;
+    if (cfg) *cfg = have ? e->aug_cfg[pass][op] : -1;
+    return AQ_OK;
+}
+
 extern "C" int aq_engine_run_ops(aq_engine* e, const uint8_t* tiles_dev, int B, int H, int W, void* ws, size_t ws_bytes, int first, int last,
                                  float conf, float iou, int max_det, aq_det* dets_dev, int32_t* counts_dev, void* stream) {
     AQ_REQUIRE(dets_dev && counts_dev, "run_ops: null output pointer");
@@ -994,9 +1184,10 @@ extern "C" int aq_engine_autotune(aq_engine* e, const uint8_t* tiles_dev, int B,
     int rc = layout(e, B, H, W);
     if (rc) return rc;
     if (ws_bytes < e->total_bytes) { aq_set_error("autotune: workspace too small"); return AQ_ERR_WORKSPACE; }
-    std::vector<int> saved = e->tuned_cfg;
-    e->tuned_B = 0;
+    std::vector<int> saved(e->ops.size(), -1);
+    e->tuning = true;
     rc = run_plan(e, tiles_dev, B, H, W, ws, ws_bytes, (float*)((char*)ws + e->off_pred), nullptr, nullptr, 0.f, 0.f, 1, stream);
+    e->tuning = false;
     if (rc) return rc;
     hipEvent_t ev0, ev1;
     AQ_CHECK_HIP(hipEventCreate(&ev0));
@@ -1026,8 +1217,7 @@ extern "C" int aq_engine_autotune(aq_engine* e, const uint8_t* tiles_dev, int B,
     (void)hipEventDestroy(ev0);
     (void)hipEventDestroy(ev1);
     if (rc) return rc;
-    e->tuned_cfg = saved;
-    e->tuned_B = B; e->tuned_H = H; e->tuned_W = W;
+    store_tuned(e, B, H, W, saved);
     return AQ_OK;
 }
 
@@ -1042,10 +1232,10 @@ extern "C" int aq_engine_set_tuned_table(aq_engine* e, int B, int H, int W, cons
     }
     int rc = layout(e, B, H, W);      // (H, W) as the engine lays them out: the table is matched against those
     if (rc) return rc;
-    e->tuned_cfg.assign(cfgs, cfgs + n_ops);
+    std::vector<int> cfg(cfgs, cfgs + n_ops);
     for (int i = 0; i < n_ops; ++i)
-        if (e->ops[i].kind != AQ_OP_CONV) e->tuned_cfg[i] = -1;
-    e->tuned_B = B; e->tuned_H = e->lay_H; e->tuned_W = e->lay_W;
+        if (e->ops[i].kind != AQ_OP_CONV) cfg[i] = -1;
+    store_tuned(e, B, e->lay_H, e->lay_W, cfg);
     return AQ_OK;
 }
 
@@ -1063,7 +1253,7 @@ extern "C" int aq_engine_last_launch(aq_engine* e, int op, int* family, int* cfg
 extern "C" int aq_engine_get_conv_config(aq_engine* e, int op) {
     if (!e || op < 0 || op >= (int)e->ops.size()) return -1;
     if (e->conv_cfg[op] >= 0) return e->conv_cfg[op];
-    return e->tuned_B ? e->tuned_cfg[op] : -1;
+    return e->tuned_cur >= 0 ? e->tuned[e->tuned_cur].cfg[op] : -1;
 }
 
 extern "C" int aq_engine_profile(aq_engine* e, int enable, int ring) {

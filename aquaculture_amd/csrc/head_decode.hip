@@ -37,6 +37,7 @@ struct HeadDecParams {
     int count_stride;        // the engine keeps these counters 4 KB apart: 64 adjacent ints share an L2 channel, whose atomic unit then
                              // serialises every workgroup of the launch (measured: 73 us for the 80 x 80 level against 49.5 spread out)
     int cap;
+    float scale, flip_w;     // AUG: xywh / scale, then x = flip_w - x when flip_w != 0 (one pass of an --augment call)
 };
 
 __global__ void head_counts_gather_kernel(const int32_t* wide, int stride, int32_t* compact, int B) {
@@ -50,7 +51,7 @@ __device__ __forceinline__ float head_sigmoid(float x) { return 1.0f / (1.0f + e
 // KSW = k-steps (of 32 channels) per wave, KSPLIT = waves that share a 16-pixel block, each multiplying its own K range (K = 32 KSW
 // KSPLIT): the wide levels (K = 384, 768) would otherwise hold 100-200 weight registers per wave and run one or two waves per SIMD with
 // a handful of blocks each; split this way every level has the registers (and the loads in flight) of the K = 192 one.
-template <int KSW, int KSPLIT, int OCC = 4>
+template <int KSW, int KSPLIT, int OCC = 4, bool AUG = false>
 __global__ __launch_bounds__(256, OCC) void head_decode_kernel(const HeadDecParams p) {
     constexpr int KS = KSW * KSPLIT, NG = 4 / KSPLIT, PXI = 16 * NG;      // pixel groups and pixels per workgroup iteration
     __shared__ __attribute__((aligned(16))) float s_tile[4][16][32];
@@ -142,11 +143,19 @@ __global__ __launch_bounds__(256, OCC) void head_decode_kernel(const HeadDecPara
             const float s0 = head_sigmoid(raw[0]), s1 = head_sigmoid(raw[1]);
             const float s2 = head_sigmoid(raw[2]), s3 = head_sigmoid(raw[3]);
             const float gx = (float)x - 0.5f, gy = (float)y - 0.5f;
-            dst[0] = (s0 * 2.0f + gx) * p.stride;
-            dst[1] = (s1 * 2.0f + gy) * p.stride;
+            float bx = (s0 * 2.0f + gx) * p.stride;
+            float by = (s1 * 2.0f + gy) * p.stride;
             const float tw = s2 * 2.0f, th = s3 * 2.0f;
-            dst[2] = (tw * tw) * p.anchor[q][0];
-            dst[3] = (th * th) * p.anchor[q][1];
+            float bw = (tw * tw) * p.anchor[q][0];
+            float bh = (th * th) * p.anchor[q][1];
+            if constexpr (AUG) {                         // [UPSTREAM models/yolo.py _descale_pred]: p[..., :4] /= scale; x = img_size[1] - x
+                bx = bx / p.scale; by = by / p.scale; bw = bw / p.scale; bh = bh / p.scale;
+                if (p.flip_w != 0.0f) bx = p.flip_w - bx;
+            }
+            dst[0] = bx;
+            dst[1] = by;
+            dst[2] = bw;
+            dst[3] = bh;
             dst[4] = obj;
             for (int c = 0; c < p.nc && c < 11; ++c) dst[5 + c] = head_sigmoid(raw[5 + c]);
         }
@@ -154,12 +163,13 @@ __global__ __launch_bounds__(256, OCC) void head_decode_kernel(const HeadDecPara
     }
 }
 
-struct HeadKernel { int ks, split; void (*fn)(const HeadDecParams); };
+struct HeadKernel { int ks, split; void (*fn)(const HeadDecParams); void (*fn_aug)(const HeadDecParams); };
 const HeadKernel kHead[] = {
-    {4, 1, head_decode_kernel<4, 1>},  {6, 1, head_decode_kernel<6, 1>},  {8, 1, head_decode_kernel<8, 1>},
-    {10, 2, head_decode_kernel<5, 2>}, {12, 2, head_decode_kernel<6, 2>}, {16, 2, head_decode_kernel<8, 2>},
-    {20, 4, head_decode_kernel<5, 4>}, {24, 4, head_decode_kernel<6, 4>}, {32, 4, head_decode_kernel<8, 4>},
-    {40, 4, head_decode_kernel<10, 4, 2>},
+    {4, 1, head_decode_kernel<4, 1>, head_decode_kernel<4, 1, 4, true>},     {6, 1, head_decode_kernel<6, 1>, head_decode_kernel<6, 1, 4, true>},
+    {8, 1, head_decode_kernel<8, 1>, head_decode_kernel<8, 1, 4, true>},     {10, 2, head_decode_kernel<5, 2>, head_decode_kernel<5, 2, 4, true>},
+    {12, 2, head_decode_kernel<6, 2>, head_decode_kernel<6, 2, 4, true>},    {16, 2, head_decode_kernel<8, 2>, head_decode_kernel<8, 2, 4, true>},
+    {20, 4, head_decode_kernel<5, 4>, head_decode_kernel<5, 4, 4, true>},    {24, 4, head_decode_kernel<6, 4>, head_decode_kernel<6, 4, 4, true>},
+    {32, 4, head_decode_kernel<8, 4>, head_decode_kernel<8, 4, 4, true>},    {40, 4, head_decode_kernel<10, 4, 2>, head_decode_kernel<10, 4, 2, true>},
 };
 int g_head_cus[64];
 
@@ -196,12 +206,10 @@ extern "C" int aq_pack_head_weights(const float* w_host, const float* bias_host,
     return AQ_OK;
 }
 
-// One Detect level: in = bf16 NHWC feature map slice (`cin` channels from in_choff of rows of in_ld elements), ny x nx pixels per image.
-// Appends to cand / cand_rows exactly as aq_detect_decode does; image b's counter is cand_count_dev[b * count_stride] (zeroed by the
-// caller before the first level; aq_head_counts_gather copies strided counters into the compact array aq_nms reads).
-extern "C" int aq_head_decode(const void* in_dev, int in_ld, int in_choff, int cin, const void* packed_dev, int B, int ny, int nx,
-                              int cand_off, float stride, const float* anchors_px, int nc, int na, float conf_thres,
-                              int32_t* cand_dev, float* cand_rows_dev, int32_t* cand_count_dev, int count_stride, int cand_cap, void* stream) {
+namespace {
+int head_decode_launch(const void* in_dev, int in_ld, int in_choff, int cin, const void* packed_dev, int B, int ny, int nx,
+                       int cand_off, float stride, const float* anchors_px, int nc, int na, float conf_thres, bool aug, float scale, float flip_w,
+                       int32_t* cand_dev, float* cand_rows_dev, int32_t* cand_count_dev, int count_stride, int cand_cap, void* stream) {
     AQ_REQUIRE(count_stride >= 1, "head_decode: counter stride");
     AQ_REQUIRE(in_dev && packed_dev && cand_dev && cand_rows_dev && cand_count_dev && anchors_px, "head_decode: null pointer");
     AQ_REQUIRE(aq_head_decode_supported(cin, na, nc), "head_decode: unsupported cin=%d na=%d nc=%d", cin, na, nc);
@@ -221,7 +229,7 @@ extern "C" int aq_head_decode(const void* in_dev, int in_ld, int in_choff, int c
     p.npix = B * ny * nx; p.ny = ny; p.nx = nx; p.off = cand_off; p.nc = nc; p.na = na; p.no = nc + 5;
     p.stride = stride;
     for (int a = 0; a < na; ++a) { p.anchor[a][0] = anchors_px[2 * a]; p.anchor[a][1] = anchors_px[2 * a + 1]; }
-    p.conf_thres = conf_thres; p.cand = cand_dev; p.cand_rows = cand_rows_dev; p.cand_count = cand_count_dev; p.count_stride = count_stride; p.cap = cand_cap;
+    p.conf_thres = conf_thres; p.scale = scale; p.flip_w = flip_w; p.cand = cand_dev; p.cand_rows = cand_rows_dev; p.cand_count = cand_count_dev; p.count_stride = count_stride; p.cap = cand_cap;
     const HeadKernel* k = nullptr;
     for (const HeadKernel& c : kHead)
         if (c.ks == cin / 32) k = &c;
@@ -229,9 +237,30 @@ extern "C" int aq_head_decode(const void* in_dev, int in_ld, int in_choff, int c
     const int nit = (p.npix + pxi - 1) / pxi;
     long long grid = (long long)g_head_cus[dev] * 4;                      // persistent (four workgroups per CU): the weights are loaded once per wave
     if (grid > nit) grid = nit;
-    hipLaunchKernelGGL(k->fn, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(aug ? k->fn_aug : k->fn, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
     AQ_CHECK_HIP(hipGetLastError());
     return AQ_OK;
+}
+}  // namespace
+
+// One Detect level: in = bf16 NHWC feature map slice (`cin` channels from in_choff of rows of in_ld elements), ny x nx pixels per image.
+// Appends to cand / cand_rows exactly as aq_detect_decode does; image b's counter is cand_count_dev[b * count_stride] (zeroed by the
+// caller before the first level; aq_head_counts_gather copies strided counters into the compact array aq_nms reads).
+extern "C" int aq_head_decode(const void* in_dev, int in_ld, int in_choff, int cin, const void* packed_dev, int B, int ny, int nx,
+                              int cand_off, float stride, const float* anchors_px, int nc, int na, float conf_thres,
+                              int32_t* cand_dev, float* cand_rows_dev, int32_t* cand_count_dev, int count_stride, int cand_cap, void* stream) {
+    return head_decode_launch(in_dev, in_ld, in_choff, cin, packed_dev, B, ny, nx, cand_off, stride, anchors_px, nc, na, conf_thres, false, 1.0f, 0.0f,
+                              cand_dev, cand_rows_dev, cand_count_dev, count_stride, cand_cap, stream);
+}
+
+// One level of one --augment pass: aq_head_decode's arithmetic, then the de-scale of [UPSTREAM _descale_pred]; cand_off is the row of the
+// concatenated prediction that the level's first candidate becomes.  Appends to the counters (zeroed once by the caller for all passes).
+extern "C" int aq_head_decode_aug(const void* in_dev, int in_ld, int in_choff, int cin, const void* packed_dev, int B, int ny, int nx,
+                                  int cand_off, float stride, const float* anchors_px, int nc, int na, float conf_thres, float scale, float flip_w,
+                                  int32_t* cand_dev, float* cand_rows_dev, int32_t* cand_count_dev, int count_stride, int cand_cap, void* stream) {
+    AQ_REQUIRE(scale > 0.0f && flip_w >= 0.0f, "head_decode_aug: scale %g, flip_w %g", scale, flip_w);
+    return head_decode_launch(in_dev, in_ld, in_choff, cin, packed_dev, B, ny, nx, cand_off, stride, anchors_px, nc, na, conf_thres, true, scale, flip_w,
+                              cand_dev, cand_rows_dev, cand_count_dev, count_stride, cand_cap, stream);
 }
 
 

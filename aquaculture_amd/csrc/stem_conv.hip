@@ -324,6 +324,150 @@ int launch_stem(const ConvParams& p, const uint8_t* tiles, int tiles_x, int tile
     return AQ_OK;
 }
 
+// ---- scaled-input stem (test-time augmentation, aq_stem_conv_scaled) ----
+// The source of a scaled pass: uint8 tiles H0 x W0, the bilinear taps of its h x w interpolated area ([UPSTREAM scale_img]); p.H x p.W of
+// the ConvParams is the padded network input.
+struct StemAugSrc { const aq_tap* ytab; const aq_tap* xtab; int H0, W0, h, w; };
+
+// stem_conv_kernel's tiling, weight fragments, MFMA body and epilogue; only the patch fill differs: each patch element is the sample of
+// the scaled network input (aq_aug_value) rounded once to the activation type, computed straight into LDS (one patch buffer; the fill of
+// a tile is not overlapped with the previous tile's MFMAs -- the scaled passes are two of the three passes of an --augment call).
+template <bool F32, int MB>
+__global__ __launch_bounds__(256, 2) void stem_conv_scaled_kernel(const ConvParams p, const uint8_t* __restrict__ tiles, const StemAugSrc src,
+                                                                  int tiles_x, int tiles_y) {
+    using G = StemGeom<F32>;
+    using afrag_t = typename std::conditional<F32, float, bf16x8>::type;
+    constexpr int EB = G::EB, PROWB = G::PROWB, KS = G::KS;
+    constexpr int kRowElems = kPRowDw * 4;               // patch elements per patch row (= image-row bytes covered)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* patch = smem;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, l15 = lane & 15;
+    const int Ho = p.Ho, Wo = p.Wo;
+
+    afrag_t a[KS][MB];
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+        for (int m = 0; m < MB; ++m) a[s][m] = ((const afrag_t*)p.w)[(s * MB + m) * 64 + lane];
+    f32x4 bias[MB];
+#pragma unroll
+    for (int m = 0; m < MB; ++m) bias[m] = *(const f32x4*)(p.bias + (4 * MB) * g + 4 * m);
+    int koff[F32 ? 1 : KS];
+    if constexpr (F32) koff[0] = g * 4;
+    else {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const int blk = 4 * s + g;
+            const int ky = blk / 3 < 6 ? blk / 3 : 5;
+            koff[s] = ky * PROWB + (blk - 3 * (blk / 3)) * 16;
+        }
+    }
+
+    const int tiles_per_img = tiles_y * tiles_x;
+    for (int tile = blockIdx.x; tile < p.n_tiles_n; tile += gridDim.x) {
+        const int b = tile / tiles_per_img, tr = tile - b * tiles_per_img;
+        const int ty0 = tr / tiles_x, tx0 = tr - ty0 * tiles_x;
+        const int y0 = ty0 * kTH, x0 = tx0 * kTW;
+        const uint8_t* img = tiles + (size_t)b * src.H0 * src.W0 * 3;
+        __syncthreads();                                 // the previous tile's fragment reads are done
+        // element k of patch row r = byte 6 x0 - 8 + k of network-input row 2 y0 - 2 + r (as stem_conv_kernel's raw dwords)
+        for (int i = tid; i < kPH * kRowElems; i += 256) {
+            const int r = i / kRowElems, k = i - r * kRowElems;
+            const int byte = 6 * x0 - 8 + k;             // >= -8
+            const int px = (byte + 9) / 3 - 3;           // floor(byte / 3)
+            const float v = aq_aug_value(img, src.W0, src.ytab, src.xtab, src.h, src.w, p.H, p.W, 2 * y0 - 2 + r, px, byte - 3 * px);
+            if constexpr (F32) *(float*)(patch + r * PROWB + k * 4) = v;
+            else *(bf16_t*)(patch + r * PROWB + k * 2) = aq_f2bf(v);
+        }
+        __syncthreads();
+        for (int q = 0; q < 8; ++q) {
+            const int ty = 2 * wave + (q >> 2), txb = (q & 3) * 16;
+            const int y = y0 + ty;
+            if (y >= Ho || x0 + txb >= Wo) continue;     // wave-uniform
+            const char* base = patch + (2 * ty) * PROWB + (2 + 6 * (txb + l15)) * EB;
+            f32x4 acc[MB];
+#pragma unroll
+            for (int m = 0; m < MB; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (!F32) {
+                bf16x8 bf[KS];
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const uint32_t* s32 = (const uint32_t*)(base + koff[s]);
+                    const uint4 u = make_uint4(s32[0], s32[1], s32[2], s32[3]);
+                    __builtin_memcpy(&bf[s], &u, 16);
+                }
+#pragma unroll
+                for (int s = 0; s < KS; ++s)
+#pragma unroll
+                    for (int m = 0; m < MB; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s][m], bf[s], acc[m], 0, 0, 0);
+            } else {
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const float bv = *(const float*)(base + koff[0] + (s / 6) * PROWB + (s % 6) * 16);
+#pragma unroll
+                    for (int m = 0; m < MB; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s][m], bv, acc[m], 0, 0, 0);
+                }
+            }
+            const int x = x0 + txb + l15;
+            char* orow = p.out + (long long)((b * Ho + y) * Wo + x) * p.out_ld_b + (4 * MB) * g * EB;
+            uint2 pk[MB];
+#pragma unroll
+            for (int m = 0; m < MB; ++m) {
+                f32x4 v = acc[m] + bias[m];
+                if (p.act) {
+                    if constexpr (F32) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = silu<true>(v[e]);
+                    } else {
+                        const f32x4 t = v * -1.44269504f;
+                        f32x4 d = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1]), __builtin_amdgcn_exp2f(t[2]),
+                                   __builtin_amdgcn_exp2f(t[3])};
+                        d = d + 1.0f;
+                        const f32x4 r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1]), __builtin_amdgcn_rcpf(d[2]),
+                                         __builtin_amdgcn_rcpf(d[3])};
+                        v = v * r;
+                    }
+                }
+                if constexpr (F32) {
+                    if (x < Wo && (4 * MB) * g + 4 * m < p.cout) *(f32x4*)(orow + m * 16) = v;
+                } else pk[m] = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+            }
+            if constexpr (!F32) {
+                struct __attribute__((packed, aligned(8))) U16 { uint32_t v[4]; };
+                if (x < Wo) {
+#pragma unroll
+                    for (int m = 0; m + 1 < MB; m += 2)
+                        if ((4 * MB) * g + 4 * m < p.cout) *(U16*)(orow + m * 8) = U16{{pk[m].x, pk[m].y, pk[m + 1].x, pk[m + 1].y}};
+                    if constexpr (MB & 1)
+                        if ((4 * MB) * g + 4 * (MB - 1) < p.cout) *(uint2*)(orow + (MB - 1) * 8) = pk[MB - 1];
+                }
+            }
+        }
+    }
+}
+
+int g_stem_scaled_occ[2][kMaxMB + 1];
+
+template <bool F32, int MB>
+int launch_stem_scaled(const ConvParams& p, const uint8_t* tiles, const StemAugSrc& src, int tiles_x, int tiles_y, hipStream_t stream) {
+    auto fn = stem_conv_scaled_kernel<F32, MB>;
+    constexpr size_t lds = StemGeom<F32>::PATCHB;
+    if (!g_stem_scaled_occ[F32][MB]) {
+        AQ_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int occ = 0;
+        AQ_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)fn, 256, lds));
+        g_stem_scaled_occ[F32][MB] = occ > 0 ? occ : 1;
+    }
+    long long grid = (long long)g_stem_cus * g_stem_scaled_occ[F32][MB];
+    if (grid > p.n_tiles_n) grid = p.n_tiles_n;
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(256), lds, stream, p, tiles, src, tiles_x, tiles_y);
+    AQ_CHECK_HIP(hipGetLastError());
+    return AQ_OK;
+}
+
 }  // namespace
 
 // Packs fused fp32 stem weights KRSC (cout, 6, 6, 3) into the A-fragment image the kernel loads once per workgroup
@@ -401,5 +545,45 @@ extern "C" int aq_stem_conv(const uint8_t* tiles_dev, void* out_dev, int out_ld,
     }
 #undef AQ_STEM_CASE
     AQ_REQUIRE(false, "stem_conv: unsupported cout %d", cout);
+    return AQ_OK;
+}
+
+// aq_stem_conv on the scaled network input of one --augment pass (hp x wp, see aq_aug_value): same weight image, output layout and
+// epilogue.  The tap tables are trusted (aq_augment_taps builds them: every index inside the H0 x W0 tile).
+extern "C" int aq_stem_conv_scaled(const uint8_t* tiles_dev, int H0, int W0, const aq_tap* ytab_dev, const aq_tap* xtab_dev, int h, int w,
+                                   void* out_dev, int out_ld, int out_choff, int cout, const void* packed_w_dev, const float* bias_dev,
+                                   int B, int hp, int wp, int act, int precision, void* stream) {
+    AQ_REQUIRE(tiles_dev && ytab_dev && xtab_dev && out_dev && packed_w_dev && bias_dev, "stem_conv_scaled: null pointer");
+    AQ_REQUIRE(B > 0 && H0 > 0 && W0 > 0 && hp > 0 && wp > 0 && hp % 4 == 0 && wp % 2 == 0 && h > 0 && w > 0 && h <= hp && w <= wp,
+               "stem_conv_scaled: bad geometry %dx%d -> %dx%d in %dx%d (hp %% 4 == 0, wp even)", H0, W0, h, w, hp, wp);
+    AQ_REQUIRE(cout > 0 && cout <= 16 * kMaxMB && cout % 8 == 0 && out_choff % 8 == 0 && out_ld % 8 == 0, "stem_conv_scaled: bad channel layout");
+    AQ_REQUIRE(precision == AQ_FP32 || precision == AQ_BF16, "stem_conv_scaled: precision %d (the engine's fp32 or bf16 stem)", precision);
+    const bool f32 = precision == AQ_FP32;
+    const int eb = aq_elem_bytes(precision);
+    ConvParams p{};
+    p.out = (char*)out_dev + (size_t)out_choff * eb; p.out_ld_b = out_ld * eb;
+    p.w = (const char*)packed_w_dev; p.bias = bias_dev;
+    p.B = B; p.H = hp; p.W = wp; p.Ho = hp / 2; p.Wo = wp / 2;
+    p.cout = cout; p.act = act; p.npix = B * p.Ho * p.Wo;
+    AQ_REQUIRE((long long)B * H0 * W0 * 3 < (1LL << 40) && (long long)B * p.Ho * p.Wo < (1LL << 31), "stem_conv_scaled: batch too large");
+    const int tiles_x = (p.Wo + kTW - 1) / kTW, tiles_y = (p.Ho + kTH - 1) / kTH;
+    AQ_REQUIRE((long long)B * tiles_x * tiles_y < (1LL << 31), "stem_conv_scaled: batch too large");
+    p.n_tiles_n = B * tiles_y * tiles_x;
+    p.n_tiles_m = 1;
+    if (g_stem_cus == 0) {
+        int dev = 0, cus = 256;
+        AQ_CHECK_HIP(hipGetDevice(&dev));
+        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
+        g_stem_cus = cus;
+    }
+    const StemAugSrc src{ytab_dev, xtab_dev, H0, W0, h, w};
+    const hipStream_t st = (hipStream_t)stream;
+    switch ((cout + 15) / 16) {
+        case 1: return f32 ? launch_stem_scaled<true, 1>(p, tiles_dev, src, tiles_x, tiles_y, st) : launch_stem_scaled<false, 1>(p, tiles_dev, src, tiles_x, tiles_y, st);
+        case 2: return f32 ? launch_stem_scaled<true, 2>(p, tiles_dev, src, tiles_x, tiles_y, st) : launch_stem_scaled<false, 2>(p, tiles_dev, src, tiles_x, tiles_y, st);
+        case 3: return f32 ? launch_stem_scaled<true, 3>(p, tiles_dev, src, tiles_x, tiles_y, st) : launch_stem_scaled<false, 3>(p, tiles_dev, src, tiles_x, tiles_y, st);
+        case 4: return f32 ? launch_stem_scaled<true, 4>(p, tiles_dev, src, tiles_x, tiles_y, st) : launch_stem_scaled<false, 4>(p, tiles_dev, src, tiles_x, tiles_y, st);
+    }
+    AQ_REQUIRE(false, "stem_conv_scaled: unsupported cout %d", cout);
     return AQ_OK;
 }

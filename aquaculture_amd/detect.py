@@ -30,7 +30,7 @@ from . import postprocess
 from .checkpoint import load_checkpoint
 from .dataloader import LoadImages, check_img_size
 
-UNSUPPORTED = ("view_img", "save_crop", "augment", "visualize", "update", "dnn")
+UNSUPPORTED = ("view_img", "save_crop", "visualize", "update", "dnn")
 
 
 def increment_path(path, exist_ok=False, sep="", mkdir=False) -> Path:
@@ -66,7 +66,8 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--nosave", action="store_true", help="do not save images/videos")
     p.add_argument("--classes", nargs="+", type=int, help="filter by class: --classes 0, or --classes 0 2 3")
     p.add_argument("--agnostic-nms", action="store_true")
-    p.add_argument("--augment", action="store_true")
+    p.add_argument("--augment", action="store_true",
+                   help="augmented inference [UPSTREAM _forward_augment]: three passes (scale 1, 0.83 flipped left-right, 0.67), one NMS over all")
     p.add_argument("--visualize", action="store_true")
     p.add_argument("--update", action="store_true")
     p.add_argument("--project", default=str(root / "runs/detect"), help="save results to project/name")
@@ -111,11 +112,21 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
     return opt
 
 
+def run_params(weights_id, conf_thres, iou_thres, max_det, imgsz, precision, save_conf, classes=None, agnostic_nms=False, augment=False) -> dict:
+    """What the label bytes depend on (run_params.json; --resume refuses a directory written with anything else).  The optional settings are
+    recorded only when set, so that the record of a run without them stays what it always was."""
+    return {"weights_sha256": weights_id, "conf_thres": float(conf_thres), "iou_thres": float(iou_thres), "max_det": int(max_det),
+            "imgsz": [int(v) for v in imgsz], "precision": precision, "save_conf": bool(save_conf),
+            **({"classes": sorted(int(c) for c in classes)} if classes is not None else {}),
+            **({"agnostic_nms": True} if agnostic_nms else {}),
+            **({"augment": True} if augment else {})}
+
+
 def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_det=1000, device="",
         save_txt=False, save_conf=False, nosave=False, classes=None, agnostic_nms=False,
         project="runs/detect", name="exp", exist_ok=False, half=False, batch_size=64, precision=None,
         workers=8, decode_threads=False, quiet=False, geocode_bboxes=None, geocode_out=None, tile_scenes=0, autotune="auto", resume=False,
-        jpeg_decode="auto", log=print, **unsupported):
+        jpeg_decode="auto", augment=False, log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb, jpeg_slots_to_rgb, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     for k in UNSUPPORTED:
@@ -125,6 +136,10 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         log("note: annotated images are never written (the reference runs with --nosave)")
     weights = weights[0] if isinstance(weights, (list, tuple)) else weights
     precision = precision or ("bf16" if half else "fp32")
+    if augment and precision == "fp8":
+        # the e4m3 activation scales are calibrated at one geometry; the augmented passes run at three (aq_engine_infer_augment refuses them)
+        raise ValueError("--augment does not run with --precision fp8: its activation scales are calibrated at the tile size, and the "
+                         "augmented passes run at three sizes; use --precision bf16 (or fp8w) with --augment")
 
     # (yolov5/detect.py has set OMP_NUM_THREADS / OPENBLAS_NUM_THREADS / MKL_NUM_THREADS to 1 before numpy and torch were loaded: the CPU
     # side of the sweep wants no thread teams; here the same for a caller that imported torch first)
@@ -152,11 +167,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
     # what the label bytes depend on; --resume refuses to continue a directory written with anything else.  Collective: nobody processes
     # a tile before rank 0 has accepted the directory, and a refusal reaches every rank.
     aqdist.on_rank0(lambda: None if tile_scenes else check_run_params(
-        str(save_dir), {"weights_sha256": file_digest(weights) if os.path.isfile(str(weights)) else str(weights),
-                        "conf_thres": float(conf_thres), "iou_thres": float(iou_thres), "max_det": int(max_det),
-                        "imgsz": [int(v) for v in imgsz], "precision": precision, "save_conf": bool(save_conf),
-                        **({"classes": sorted(int(c) for c in classes)} if classes is not None else {}),
-                        **({"agnostic_nms": True} if agnostic_nms else {})}, resume))
+        str(save_dir), run_params(file_digest(weights) if os.path.isfile(str(weights)) else str(weights), conf_thres, iou_thres, max_det, imgsz,
+                                  precision, save_conf, classes, agnostic_nms, augment), resume))
     done_before = DoneManifest.load(str(save_dir)) if resume else set()
     manifest = DoneManifest(str(save_dir), rank)
     if not tile_scenes:
@@ -548,16 +560,21 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     tune = False
                     geom = [int(tiles.shape[0]), int(tiles.shape[1]), int(tiles.shape[2])]
                     t_tune = time.perf_counter()
-                    box = [geom, eng.autotune(tiles, cache=tune_cache) if rank == 0 else None]
+                    # (--augment: the tables of the three passes' geometries, [((B, Hp, Wp), cfgs)]; the plain table last, as get_conv_config reports it)
+                    box = [geom, (eng.autotune(tiles, cache=tune_cache, augment=True) if augment else eng.autotune(tiles, cache=tune_cache))
+                           if rank == 0 else None]
                     if multi:
                         torch.distributed.broadcast_object_list(box, src=0)
                         if rank != 0 and box[0] == geom:
-                            eng.set_tuned_table(*geom, box[1])
+                            for g_, cfgs_ in (box[1] if augment else [(geom, box[1])])[::-1]:
+                                eng.set_tuned_table(*g_, cfgs_)
                     if rank == 0:
-                        log(f"autotuned {sum(1 for c in box[1] if c >= 0)} conv layers for batch {geom[0]} x {geom[1]}x{geom[2]} in "
+                        n_tuned = sum(1 for c in (box[1][0][1] if augment else box[1]) if c >= 0)
+                        log(f"autotuned {n_tuned} conv layers for batch {geom[0]} x {geom[1]}x{geom[2]}"
+                            f"{' and the augmented passes ' + ', '.join(f'{g_[1]}x{g_[2]}' for g_, _ in box[1][1:]) if augment else ''} in "
                             f"{time.perf_counter() - t_tune:.1f}s (table: {tune_cache})")
                 t1 = time.perf_counter()
-                dets, counts = eng.infer(tiles, conf_thres, iou_thres, max_det, slot=slot)
+                dets, counts = eng.infer(tiles, conf_thres, iou_thres, max_det, slot=slot, augment=augment)
                 B = tiles.shape[0]
                 if pinned[slot] is None or pinned[slot][0].shape[0] < B:
                     pinned[slot] = (torch.empty((max(B, batch_size),), dtype=torch.int32).pin_memory(),

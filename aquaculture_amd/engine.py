@@ -71,6 +71,8 @@ EXPORTS = (
     "aq_conv3x3s2_direct_supported", "aq_pack_conv3x3s2_direct", "aq_conv3x3s2_direct",
     "aq_conv3x3_pl_supported", "aq_conv3x3_pl_asm_family", "aq_pack_conv3x3_pl", "aq_conv3x3_pl", "aq_conv3x3_pl_s2_supported", "aq_pack_conv3x3_pl_s2", "aq_conv3x3_pl_s2", "aq_jpeg_scratch_bytes", "aq_jpeg_idct_rgb", "aq_f32_to_e4m3", "aq_conv1x1_direct_f8out", "aq_absmax_bf16", "aq_engine_calibrate_amax", "aq_engine_set_fp8_scales", "aq_engine_last_launch", "aq_conv3x3_pl_f8_supported", "aq_pack_conv3x3_pl_f8", "aq_conv3x3_pl_f8", "aq_conv3x3_pl_w8_supported", "aq_pack_conv3x3_pl_w8", "aq_conv3x3_pl_w8", "aq_head_decode_supported", "aq_pack_head_weights", "aq_head_decode", "aq_head_counts_gather", "aq_preprocess_s2d", "aq_sppf_pool",
     "aq_upsample2x", "aq_letterbox_u8", "aq_letterbox_tiles_u8", "aq_format_label_rows", "aq_detect_decode", "aq_nms_scratch_bytes", "aq_nms", "aq_jpeg_huffman_decode", "aq_write_label_files",
+    "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
+    "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
 
 _lib = None
@@ -167,6 +169,17 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_nms_scratch_bytes.argtypes = [i32, i32]
     lib.aq_nms_scratch_bytes.restype = sz
     lib.aq_nms.argtypes = [vp, i32, i32, i32, i32, f32, f32, i32, vp, vp, i32, vp, vp, vp, vp]
+    lib.aq_augment_geometry.argtypes = [i32, i32, i32, vp, C.POINTER(i32)]
+    lib.aq_augment_taps.argtypes = [i32, i32, i32, vp]
+    lib.aq_stem_conv_scaled.argtypes = [vp, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.aq_preprocess_s2d_scaled.argtypes = [vp, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, vp]
+    lib.aq_head_decode_aug.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, i32, f32, C.POINTER(f32), i32, i32, f32, f32, f32, vp, vp, vp, i32, i32, vp]
+    lib.aq_detect_decode_aug.argtypes = [C.POINTER(vp), i32, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), i32, i32, i32, f32, f32,
+                                         vp, f32, vp, vp, vp, i32, vp]
+    lib.aq_engine_workspace_bytes_augment.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
+    lib.aq_engine_infer_augment.argtypes = lib.aq_engine_infer.argtypes
+    lib.aq_engine_forward_raw_augment.argtypes = lib.aq_engine_forward_raw.argtypes
+    lib.aq_engine_last_launch_augment.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     _lib = lib
     return lib
 
@@ -323,10 +336,10 @@ class Engine:
             pass
 
     # ---- workspace ----
-    def workspace(self, B: int, H: int, W: int, slot: int = 0) -> torch.Tensor:
+    def workspace(self, B: int, H: int, W: int, slot: int = 0, augment: bool = False) -> torch.Tensor:
         """Workspace of in-flight batch ``slot``: batches issued on different streams must not share one."""
         n = C.c_size_t()
-        _check(self.lib.aq_engine_workspace_bytes(self.handle, B, H, W, C.byref(n)))
+        _check((self.lib.aq_engine_workspace_bytes_augment if augment else self.lib.aq_engine_workspace_bytes)(self.handle, B, H, W, C.byref(n)))
         ws = self._slots.get(slot)
         if ws is None or ws.numel() < n.value:
             self._slots.pop(slot, None)
@@ -334,7 +347,11 @@ class Engine:
         self._ws = ws
         return ws
 
-    def num_candidates(self, H: int, W: int) -> int:
+    def num_candidates(self, H: int, W: int, augment: bool = False) -> int:
+        """Rows per image of the prediction: one pass, or the three clipped passes of --augment (augment.geometry)."""
+        if augment:
+            from . import augment as _aug
+            return _aug.geometry(H, W, self.ck.na)[1]
         return _spec.num_candidates(H, W, self.ck.na)
 
     @staticmethod
@@ -345,19 +362,20 @@ class Engine:
 
     # ---- S1 + S2 ----
     def infer(self, tiles: torch.Tensor, conf_thres: float = 0.25, iou_thres: float = 0.45, max_det: int = 1000,
-              out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, slot: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+              out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, slot: int = 0, augment: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """uint8 [B,H,W,3] -> (dets float32 [B,max_det,6] = x1,y1,x2,y2,conf,cls ; counts int32 [B]).
         Work is enqueued on torch's current stream; ``slot`` selects the workspace (use one slot per stream when
-        several batches are in flight)."""
+        several batches are in flight).  ``augment``: upstream's test-time augmentation (three passes, one NMS; augment.py)."""
         B, H, W = self._check_tiles(tiles)
-        ws = self.workspace(B, H, W, slot)
+        ws = self.workspace(B, H, W, slot, augment)
         if out is None:
             dets = torch.empty((B, max_det, 6), dtype=torch.float32, device=self.device)
             counts = torch.empty((B,), dtype=torch.int32, device=self.device)
         else:
             dets, counts = out
-        _check(self.lib.aq_engine_infer(self.handle, tiles.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(),
-                                        dets.data_ptr(), counts.data_ptr(), conf_thres, iou_thres, max_det, _stream_ptr()))
+        fn = self.lib.aq_engine_infer_augment if augment else self.lib.aq_engine_infer
+        _check(fn(self.handle, tiles.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(),
+                  dets.data_ptr(), counts.data_ptr(), conf_thres, iou_thres, max_det, _stream_ptr()))
         return dets, counts
 
     def run_ops(self, tiles: torch.Tensor, first: int, last: int, conf_thres: float = 0.25, iou_thres: float = 0.45, max_det: int = 1000,
@@ -377,13 +395,14 @@ class Engine:
         return dets, counts
 
     # ---- S1 ----
-    def forward_raw(self, tiles: torch.Tensor) -> torch.Tensor:
-        """uint8 [B,H,W,3] -> pred float32 [B, N, 5+nc] (what Detect.forward returns at inference)."""
+    def forward_raw(self, tiles: torch.Tensor, augment: bool = False) -> torch.Tensor:
+        """uint8 [B,H,W,3] -> pred float32 [B, N, 5+nc] (what Detect.forward returns at inference).  ``augment``: what
+        ``model(im, augment=True)`` returns -- the three passes de-scaled, clipped and concatenated, [B, N_aug, 5+nc]."""
         B, H, W = self._check_tiles(tiles)
-        ws = self.workspace(B, H, W)
-        pred = torch.empty((B, self.num_candidates(H, W), self.no), dtype=torch.float32, device=self.device)
-        _check(self.lib.aq_engine_forward_raw(self.handle, tiles.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(),
-                                              pred.data_ptr(), _stream_ptr()))
+        ws = self.workspace(B, H, W, augment=augment)
+        pred = torch.empty((B, self.num_candidates(H, W, augment), self.no), dtype=torch.float32, device=self.device)
+        fn = self.lib.aq_engine_forward_raw_augment if augment else self.lib.aq_engine_forward_raw
+        _check(fn(self.handle, tiles.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(), pred.data_ptr(), _stream_ptr()))
         return pred
 
     # ---- S2 ----
@@ -437,16 +456,26 @@ class Engine:
         off = ",".join(sorted(f"{k}={v}" for k, v in os.environ.items() if k.startswith("AQ_DISABLE_") or k in ("AQ_PL_W8", "AQ_PL_ASM", "AQ_PL_NB", "AQ_C1_ASM", "AQ_C1_ASM_NB")))
         return key + (":" + off if off else "")
 
-    def autotune(self, tiles: torch.Tensor, reps: int = 3, cache: Optional[str] = None, shipped: bool = True) -> List[int]:
+    def autotune(self, tiles: torch.Tensor, reps: int = 3, cache: Optional[str] = None, shipped: bool = True, augment: bool = False):
         """Pick the fastest tile configuration per conv op for this batch geometry (synchronises).
         ``cache``: optional JSON file; a stored table for the same model/precision/geometry is applied
         instead of re-timing (used to keep tuning launches out of rocprof traces).
         ``shipped``: on a cache miss look in the table that ships in-tree (aquaculture_amd/data/tuned_tables.json: the geometries of
         BASELINE.json's configs, timed on MI355X with this library version) before timing anything -- two runs of the same build then
         launch the same kernels and write the same bf16 label bytes (the timing sweep's picks between near-equal shapes flip from run to
-        run); ``shipped=False`` (bench.py --retune, AQ_RETUNE=1) times regardless."""
+        run); ``shipped=False`` (bench.py --retune, AQ_RETUNE=1) times regardless.
+        ``augment``: tune (or install from the caches) the tables of all three geometries an augmented call runs at -- each pass uses the
+        table of its own network input; returns [((B, Hp, Wp), cfgs)] per pass.  The scaled passes are timed on the tiles' top-left Hp x Wp
+        corner (the kernels' speed does not depend on the pixel values)."""
         import json
         B, H, W = self._check_tiles(tiles)
+        if augment:
+            from . import augment as _aug
+            out = []
+            for ps in reversed(_aug.geometry(H, W, self.ck.na)[0]):     # (the plain geometry last: get_conv_config reports its table)
+                t = tiles if (ps.hp, ps.wp) == (H, W) else tiles[:, :ps.hp, :ps.wp].contiguous()
+                out.append(((B, ps.hp, ps.wp), self.autotune(t, reps, cache, shipped)))
+            return out[::-1]
         key = self.tune_key(B, H, W)
         table = {}
         if cache and os.path.exists(cache):
@@ -487,13 +516,16 @@ class Engine:
     FAMILIES = {0: "none", 1: "igemm_or_halo", 2: "pl3x3", 3: "pl3x3_w8", 4: "pl3x3s2", 5: "pl3x3_f8", 6: "direct1x1", 7: "direct1x1_f8out",
                 8: "direct3x3s2", 9: "bottleneck", 10: "downblock", 11: "stem", 12: "head_decode", 13: "asm1x1"}
 
-    def last_launches(self) -> List[Tuple[str, int]]:
+    def last_launches(self, augment_pass: Optional[int] = None) -> List[Tuple[str, int]]:
         """(kernel family, tile-configuration id) of every op's most recent launch (aq_engine_last_launch) -- what actually ran, as opposed
-        to what the tuned table asked for."""
+        to what the tuned table asked for.  ``augment_pass`` (0..2): the records of that pass of the last augmented call."""
         out = []
         fam, cfg = C.c_int(), C.c_int()
         for i in range(len(self.plan.ops)):
-            _check(self.lib.aq_engine_last_launch(self.handle, i, C.byref(fam), C.byref(cfg)))
+            if augment_pass is None:
+                _check(self.lib.aq_engine_last_launch(self.handle, i, C.byref(fam), C.byref(cfg)))
+            else:
+                _check(self.lib.aq_engine_last_launch_augment(self.handle, augment_pass, i, C.byref(fam), C.byref(cfg)))
             out.append((self.FAMILIES.get(fam.value, str(fam.value)), cfg.value))
         return out
 
@@ -1050,3 +1082,94 @@ def stemdown_nhwc(tiles_u8: torch.Tensor, ws_oihw: torch.Tensor, bs: torch.Tenso
                            C.c_void_p(bsbuf.data_ptr()), C.c_void_p(wbuf.data_ptr()), C.c_void_p(bbuf.data_ptr()), B, Hi, Wi, C.c_void_p(_stream_ptr())))
     torch.cuda.current_stream().synchronize()
     return out
+
+
+def _aug_taps_device(H: int, W: int, h: int, w: int, flip: bool, device):
+    from . import augment as _aug
+    ytab = torch.from_numpy(_aug.bilinear_taps(H, h).view(np.int32).copy()).to(device)
+    xtab = torch.from_numpy(_aug.bilinear_taps(W, w, flip).view(np.int32).copy()).to(device)
+    return ytab, xtab
+
+
+def stem_conv_scaled_nhwc(tiles_u8: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, h: int, w: int, hp: int, wp: int, flip: bool,
+                          act: bool = True, precision: str = "bf16") -> torch.Tensor:
+    """aq_stem_conv_scaled (tests): the stem on scale_img(flip(u8 / 255)) -- interpolated to h x w, padded with 0.447 to hp x wp --
+    as NHWC [B, hp/2, wp/2, cout]."""
+    _require_gpu()
+    lib = load_library()
+    prec = PRECISIONS[precision]
+    B, H, W, _ = tiles_u8.shape
+    cout = w_oihw.shape[0]
+    wk = np.ascontiguousarray(w_oihw.permute(0, 2, 3, 1).float().cpu().numpy())
+    n = C.c_size_t()
+    wptr = wk.ctypes.data_as(C.POINTER(C.c_float))
+    _check(lib.aq_pack_stem_weights(wptr, cout, prec, None, C.byref(n), None))
+    wbuf = torch.empty(n.value, dtype=torch.uint8, device=tiles_u8.device)
+    _check(lib.aq_pack_stem_weights(wptr, cout, prec, wbuf.data_ptr(), C.byref(n), _stream_ptr()))
+    bbuf = torch.zeros(64, dtype=torch.float32, device=tiles_u8.device)
+    bbuf[:cout] = bias.float().to(tiles_u8.device)
+    ytab, xtab = _aug_taps_device(H, W, h, w, flip, tiles_u8.device)
+    out = torch.empty((B, hp // 2, wp // 2, cout), dtype=_act_dtype(prec), device=tiles_u8.device)
+    _check(lib.aq_stem_conv_scaled(tiles_u8.data_ptr(), H, W, ytab.data_ptr(), xtab.data_ptr(), h, w, out.data_ptr(), cout, 0, cout,
+                                   wbuf.data_ptr(), bbuf.data_ptr(), B, hp, wp, int(act), prec, _stream_ptr()))
+    torch.cuda.current_stream().synchronize()
+    return out
+
+
+def preprocess_s2d_scaled(tiles_u8: torch.Tensor, h: int, w: int, hp: int, wp: int, flip: bool, precision: str = "fp32") -> torch.Tensor:
+    """aq_preprocess_s2d_scaled (tests): space-to-depth [B, hp/2, wp/2, 16] of the scaled network input (channels 12..15 zero)."""
+    _require_gpu()
+    lib = load_library()
+    prec = PRECISIONS[precision]
+    B, H, W, _ = tiles_u8.shape
+    ytab, xtab = _aug_taps_device(H, W, h, w, flip, tiles_u8.device)
+    out = torch.empty((B, hp // 2, wp // 2, 16), dtype=_act_dtype(prec), device=tiles_u8.device)
+    _check(lib.aq_preprocess_s2d_scaled(tiles_u8.data_ptr(), H, W, ytab.data_ptr(), xtab.data_ptr(), h, w, out.data_ptr(), B, hp, wp, prec,
+                                        _stream_ptr()))
+    torch.cuda.current_stream().synchronize()
+    return out
+
+
+def detect_decode_aug(heads, H: int, W: int, nc: int, anchors_px, strides, level_mask: int, cand_base: int, rows_per_image: int,
+                      scale: float, flip_w: float) -> torch.Tensor:
+    """aq_detect_decode_aug in pred mode (tests): fp32 head maps [B, ny, nx, na * (nc + 5)] per level -> pred [B, rows_per_image, nc + 5]
+    with this pass's rows at cand_base + n (the other rows stay zero)."""
+    _require_gpu()
+    lib = load_library()
+    heads = [h.contiguous() for h in heads]
+    B, na = heads[0].shape[0], len(anchors_px[0])
+    pred = torch.zeros((B, rows_per_image, nc + 5), dtype=torch.float32, device=heads[0].device)
+    hp = (C.c_void_p * 3)(*[h.data_ptr() for h in heads])
+    anch = (C.c_float * (3 * na * 2))(*[float(v) for lvl in anchors_px for a in lvl for v in a])
+    st = (C.c_float * 3)(*[float(s) for s in strides])
+    _check(lib.aq_detect_decode_aug(hp, int(heads[0].shape[3]), B, H, W, nc, na, anch, st, level_mask, cand_base, rows_per_image,
+                                    C.c_float(scale), C.c_float(flip_w), pred.data_ptr(), C.c_float(0.0), None, None, None, 0, _stream_ptr()))
+    torch.cuda.current_stream().synchronize()
+    return pred
+
+
+def head_decode_level_aug(x: torch.Tensor, w_oi: torch.Tensor, bias: torch.Tensor, cand_off: int, stride: float, anchors_px, nc: int,
+                          conf_thres: float, cap: int, scale: float, flip_w: float):
+    """head_decode_level through aq_head_decode_aug (tests): the same outputs, the boxes de-scaled."""
+    _require_gpu()
+    lib = load_library()
+    assert x.dtype == torch.bfloat16 and x.stride(3) == 1
+    B, ny, nx, cin = x.shape
+    ld = x.stride(2)
+    na = len(anchors_px)
+    cout = na * (nc + 5)
+    w = np.ascontiguousarray(w_oi.float().cpu().numpy().reshape(cout, cin))
+    bh = np.ascontiguousarray(bias.float().cpu().numpy())
+    n = C.c_size_t()
+    fp = C.POINTER(C.c_float)
+    _check(lib.aq_pack_head_weights(w.ctypes.data_as(fp), bh.ctypes.data_as(fp), cin, cout, None, C.byref(n), None))
+    wbuf = torch.empty(n.value, dtype=torch.uint8, device=x.device)
+    _check(lib.aq_pack_head_weights(w.ctypes.data_as(fp), bh.ctypes.data_as(fp), cin, cout, C.c_void_p(wbuf.data_ptr()), C.byref(n), C.c_void_p(_stream_ptr())))
+    counts = torch.zeros(B, dtype=torch.int32, device=x.device)
+    cand = torch.full((B, cap), -1, dtype=torch.int32, device=x.device)
+    rows = torch.zeros((B, cap, nc + 5), dtype=torch.float32, device=x.device)
+    anch = np.ascontiguousarray(np.asarray(anchors_px, np.float32).reshape(-1))
+    _check(lib.aq_head_decode_aug(x.data_ptr(), ld, 0, cin, wbuf.data_ptr(), B, ny, nx, cand_off, stride, anch.ctypes.data_as(fp), nc, na,
+                                  conf_thres, scale, flip_w, cand.data_ptr(), rows.data_ptr(), counts.data_ptr(), 1, cap, _stream_ptr()))
+    torch.cuda.current_stream().synchronize()
+    return counts, cand, rows

@@ -168,8 +168,9 @@ enum {
 int aq_engine_last_launch(aq_engine* e, int op, int* family, int* cfg);
 /* Install a table that aq_engine_autotune produced earlier (or on another rank) for the SAME engine and (B,H,W): cfgs[n_ops], one id per
  * op as aq_engine_get_conv_config returns them (-1 for ops that are not tuned).  Used for every batch of that tile geometry (H, W),
- * whatever its size -- a ragged last batch runs the same kernels as the full ones --; other geometries keep the built-in heuristic.
- * Ids are validated per op. */
+ * whatever its size -- a ragged last batch runs the same kernels as the full ones --; geometries without a table keep the built-in
+ * heuristic.  The engine holds one table per geometry (each pass of an augmented call uses its own); installing or tuning a geometry
+ * replaces that geometry's table only, and aq_engine_get_conv_config reports the most recently installed one.  Ids are validated per op. */
 int aq_engine_set_tuned_table(aq_engine* e, int B, int H, int W, const int* cfgs, int n_ops);
 int aq_conv_num_configs(void);
 /* Diagnostics: arm (buf != NULL) or disarm a device buffer that the STAMPED builds of a few conv tile shapes fill with
@@ -391,6 +392,65 @@ int aq_nms_opts(const float* rows_dev, int rows_per_tile, int B, int N, int nc, 
                 unsigned long long classes_hi, void* stream);
 /* The engine's NMS step (aq_engine_infer) with those options; defaults: agnostic = 0, every class. */
 int aq_engine_set_nms_options(aq_engine* e, int agnostic, unsigned long long classes_lo, unsigned long long classes_hi);
+
+/* ---- test-time augmentation (detect.py --augment) -------------------------------------- */
+/* [UPSTREAM models/yolo.py DetectionModel._forward_augment]: three passes (scale, flip) = (1, -), (0.83, left-right), (0.67, -) over
+ * xi = scale_img(flip(im), s, gs = 32) [UPSTREAM utils/torch_utils.py scale_img]: F.interpolate(bilinear, align_corners = False) to
+ * (int(H s), int(W s)), then padded right / bottom with 0.447 to ceil(H s / 32) 32 x ceil(W s / 32) 32.  Each pass's decoded Detect output
+ * is de-scaled (xywh / s; x = W - x for the flipped pass) [_descale_pred], the last N_0 // 21 rows of pass 0 and the first
+ * 16 (N_2 // 21) rows of pass 2 are dropped [_clip_augmented] -- with H, W multiples of 32 exactly the P5 level of pass 0 and the P3
+ * level of pass 2 --, and the passes are concatenated: N_aug rows per image (45147 at 640 x 640, against 25200 for one pass). */
+typedef struct aq_augment_pass {
+    float scale;
+    int32_t flip;              /* 1: left-right flip before scaling */
+    int32_t h, w;              /* interpolated size: int(H s), int(W s) */
+    int32_t hp, wp;            /* padded size the network runs at (multiples of 32) */
+    int32_t rows;              /* rows of the pass's Detect output (na x the three levels at hp x wp) */
+    int32_t keep_first, keep_count;   /* rows of the pass that _clip_augmented keeps */
+    int32_t out_first;         /* row of the concatenated prediction that row keep_first becomes */
+    int32_t level_mask;        /* bit l set: level l survives the clip (its head conv and decode run) */
+} aq_augment_pass;
+/* The three passes of an H x W tile (H, W positive multiples of 32; na anchors per level); *n_aug = rows per image of the augmented
+ * prediction.  The one place the geometry is derived (the engine and the Python side both call it). */
+int aq_augment_geometry(int H, int W, int na, aq_augment_pass passes_out[3], int* n_aug);
+/* One bilinear tap per output row / column of F.interpolate(align_corners = False) from `in` to `out` samples, in PyTorch's CPU fp32
+ * arithmetic: src = max(fmaf(float(in) / out, d + 0.5f, -0.5f), 0) (one rounding, as its build), i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1.
+ * flip != 0 mirrors the source indices (in - 1 - i) for a left-right flip done before the interpolation. */
+typedef struct aq_tap { int32_t i0, i1; float l0, l1; } aq_tap;
+int aq_augment_taps(int in, int out, int flip, aq_tap* taps_host);
+/* Scaled-input stem: aq_stem_conv on scale_img(flip(u8 / 255)) without writing that image anywhere.  tiles: uint8 [B][H0][W0][3];
+ * ytab_dev / xtab_dev: aq_tap [h] / [w] (aq_augment_taps, the column taps already mirrored for a flipped pass); the network input is
+ * hp x wp: interpolated samples inside h x w, 0.447 beyond them, and the stem's own zero padding outside hp x wp.  Each sample is
+ * computed in fp32 on the v / 255 values as h0 (w0 x00 + w1 x01) + h1 (w0 x10 + w1 x11) and rounded once to the element type of the
+ * precision (fp32, or bf16 RNE).  Same weight image and output layout as aq_stem_conv; hp % 4 == 0, wp even. */
+int aq_stem_conv_scaled(const uint8_t* tiles_dev, int H0, int W0, const aq_tap* ytab_dev, const aq_tap* xtab_dev, int h, int w,
+                        void* out_dev, int out_ld, int out_choff, int cout, const void* packed_w_dev, const float* bias_dev,
+                        int B, int hp, int wp, int act, int precision, void* stream);
+/* The same sampling in front of aq_preprocess_s2d (plans without the fused stem): out = space-to-depth of the hp x wp network input. */
+int aq_preprocess_s2d_scaled(const uint8_t* tiles_dev, int H0, int W0, const aq_tap* ytab_dev, const aq_tap* xtab_dev, int h, int w,
+                             void* out_dev, int B, int hp, int wp, int precision, void* stream);
+/* aq_head_decode for one pass of an augmented call: the same arithmetic, then xywh / scale (fp32 division) and, flip_w != 0,
+ * x = flip_w - x.  cand_off: row of the concatenated prediction that this level's first candidate becomes.  Appends to the counters;
+ * the caller zeroes them once for all three passes. */
+int aq_head_decode_aug(const void* in_dev, int in_ld, int in_choff, int cin, const void* packed_dev, int B, int ny, int nx,
+                       int cand_off, float stride, const float* anchors_px, int nc, int na, float conf_thres, float scale, float flip_w,
+                       int32_t* cand_dev, float* cand_rows_dev, int32_t* cand_count_dev, int count_stride, int cand_cap, void* stream);
+/* aq_detect_decode for one pass of an augmented call: H x W = the pass's network input; only levels in level_mask are decoded; pass row n
+ * becomes row cand_base + n of the concatenated prediction (pred_dev [B][rows_per_image][no]; cand indices likewise); de-scale as
+ * aq_head_decode_aug.  Appends to cand_count_dev (not zeroed here). */
+int aq_detect_decode_aug(const float* const head_dev[3], int head_ld, int B, int H, int W, int nc, int na, const float* anchors_px,
+                         const float* stride, int level_mask, int cand_base, int rows_per_image, float scale, float flip_w,
+                         float* pred_dev, float conf_thres, int32_t* cand_dev, float* cand_rows_dev, int32_t* cand_count_dev,
+                         int cand_cap, void* stream);
+/* The engine's augmented path: the same arguments as the plain entry points; forward_raw_augment writes pred_dev [B][N_aug][5+nc] in
+ * upstream's row order.  Refused (AQ_ERR_INVALID) when N_aug reaches aq_nms's row limit, and on engines with fp8 activation scales. */
+int aq_engine_workspace_bytes_augment(aq_engine* e, int max_batch, int H, int W, size_t* bytes);
+int aq_engine_infer_augment(aq_engine* e, const uint8_t* tiles_dev, int B, int H, int W, void* workspace_dev, size_t workspace_bytes,
+                            aq_det* dets_dev, int32_t* counts_dev, float conf_thres, float iou_thres, int max_det, void* stream);
+int aq_engine_forward_raw_augment(aq_engine* e, const uint8_t* tiles_dev, int B, int H, int W, void* workspace_dev,
+                                  size_t workspace_bytes, float* pred_dev, void* stream);
+/* aq_engine_last_launch for pass `pass` (0..2) of the most recent augmented call. */
+int aq_engine_last_launch_augment(aq_engine* e, int pass, int op, int* family, int* cfg);
 
 /* Host helper: n label rows (cls xc yc w h conf, fp32, stride 6) -> the text detect.py --save-txt [--save-conf] writes
  * ("%g" per value, one line per row).  Returns bytes written or -(bytes needed). */
