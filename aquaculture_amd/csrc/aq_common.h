@@ -106,4 +106,8 @@ inline hipError_t aq_query_cus(int* cus, int dev) {
 }
 int aq_conv_halo_tiles(int hcfg, int* bm, int* bn);
 extern "C" int aq_conv_config_tiles(int cfg, int* bm, int* bn);
+// aq_conv3x3_pl with the tile chosen for a batch of pick_B images (the engine passes its tuned table's batch size)
+int aq_conv3x3_pl_at(const void* in_dev, long long in_sp, long long in_ss, int cin, void* out_dev, int out_ld, int out_choff, int cout,
+                     const void* res_dev, int res_ld, int res_choff, const void* packed_w_dev, const float* bias_dev, int B, int H, int W,
+                     int act, int pick_B, void* stream);
 extern "C" int aq_conv_num_configs(void);

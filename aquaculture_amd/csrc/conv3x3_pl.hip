@@ -556,7 +556,7 @@ static int pl_pick(int B, int H, int W, int n_mt, int cus, int* rows_out) {
 // in_ss = 16).  out / res: NHWC bf16 with row lengths out_ld / res_ld (elements), channel slices at *_choff.
 static int pl_conv(const void* in_dev, long long in_sp, long long in_ss, int cin, void* out_dev, int out_ld, int out_choff,
                    int cout, const void* res_dev, int res_ld, int res_choff, const void* packed_w_dev, const float* bias_dev,
-                   int B, int H, int W, int act, void* stream, bool w8) {
+                   int B, int H, int W, int act, void* stream, bool w8, int pick_B) {
     AQ_REQUIRE(in_dev && out_dev && packed_w_dev && bias_dev, "conv3x3_pl: null pointer");
     AQ_REQUIRE(aq_conv3x3_pl_supported(cin, cout), "conv3x3_pl: unsupported %d -> %d", cin, cout);
     AQ_REQUIRE(B > 0 && H > 0 && W > 0 && (long long)B * (H + 1) * (W + 1) + W + 2 < (1LL << 23), "conv3x3_pl: shape outside the fast-index range");
@@ -586,7 +586,11 @@ static int pl_conv(const void* in_dev, long long in_sp, long long in_ss, int cin
     p.inv_hpwp = 1.0f / (float)((H + 1) * (W + 1)); p.inv_wp = 1.0f / (float)(W + 1);
     // tile shape: AQ_PL_NB forces the pixel-block count; the assembly build of that count is used when it exists and fits
     // (AQ_PL_ASM=0: HIP-source kernels only -- A/B and fallback; =2: the stamped assembly build when a stamp buffer is armed)
-    int rows = 0, k = pl_pick(B, H, W, p.n_mt, g_pl_cus[dev], &rows);
+    // pick_B: the batch size whose tile count chooses the tile.  The tile width decides the build (assembly / pixel-major / HIP source)
+    // and with it the accumulation order, so an engine running a tuned table passes the table's batch size: a tile's result then does
+    // not depend on which batch it landed in.  (A batch whose tiles would not fit the region rows at that width picks its own.)
+    int rows = 0, k = pl_pick(pick_B > 0 ? pick_B : B, H, W, p.n_mt, g_pl_cus[dev], &rows);
+    if (k >= 0 && pick_B > 0 && pick_B != B && pl_region_rows(B, H, W, kPl[k].nb * 16) > PL_ROWS) k = pl_pick(B, H, W, p.n_mt, g_pl_cus[dev], &rows);
     const char* forced = getenv("AQ_PL_NB");
     const char* use_asm = getenv("AQ_PL_ASM");
     const char* abl = getenv("AQ_PL_ABL");                  // timing-only diagnostic builds (wrong results), NB = 13 with shortcut only
@@ -678,7 +682,15 @@ extern "C" int aq_conv3x3_pl(const void* in_dev, long long in_sp, long long in_s
                              int cout, const void* res_dev, int res_ld, int res_choff, const void* packed_w_dev, const float* bias_dev,
                              int B, int H, int W, int act, void* stream) {
     return pl_conv(in_dev, in_sp, in_ss, cin, out_dev, out_ld, out_choff, cout, res_dev, res_ld, res_choff, packed_w_dev, bias_dev, B, H, W, act,
-                   stream, false);
+                   stream, false, B);
+}
+
+// The same, with the tile chosen for a batch of pick_B images (the engine's tuned-table batch size, see pl_conv).
+int aq_conv3x3_pl_at(const void* in_dev, long long in_sp, long long in_ss, int cin, void* out_dev, int out_ld, int out_choff, int cout,
+                     const void* res_dev, int res_ld, int res_choff, const void* packed_w_dev, const float* bias_dev, int B, int H, int W,
+                     int act, int pick_B, void* stream) {
+    return pl_conv(in_dev, in_sp, in_ss, cin, out_dev, out_ld, out_choff, cout, res_dev, res_ld, res_choff, packed_w_dev, bias_dev, B, H, W, act,
+                   stream, false, pick_B);
 }
 
 // ---- fp8-weight stream (precision AQ_BF16_W8): the same kernel loading OCP e4m3fn codes -- half the L2 -> register weight traffic, the
@@ -766,7 +778,7 @@ extern "C" int aq_conv3x3_pl_w8(const void* in_dev, long long in_sp, long long i
                                 int cout, const void* res_dev, int res_ld, int res_choff, const void* packed_w8_dev,
                                 const float* scale_bias_dev, int B, int H, int W, int act, void* stream) {
     return pl_conv(in_dev, in_sp, in_ss, cin, out_dev, out_ld, out_choff, cout, res_dev, res_ld, res_choff, packed_w8_dev, scale_bias_dev, B, H, W,
-                   act, stream, true);
+                   act, stream, true, B);
 }
 
 

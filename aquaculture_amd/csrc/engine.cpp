@@ -353,7 +353,8 @@ int run_conv(aq_engine* e, int oi, void* ws, const uint8_t* tiles, int B, hipStr
     int cfg = force_cfg >= 0 ? force_cfg : e->conv_cfg[oi];
     // The tuned table serves EVERY batch size of its tile geometry (a sweep's ragged last batch, a rank with fewer tiles): a kernel's
     // accumulation order per output element does not depend on the batch, so a tile's result no longer depends on which batch it
-    // landed in (before, batches of another size fell back to the heuristic kernels and could round differently in bf16).
+    // landed in (before, batches of another size fell back to the heuristic kernels and could round differently in bf16).  The one
+    // launcher that sizes its tile -- and so picks its build -- from the batch, the planar 3x3/s1, is given the table's batch size.
     if (cfg < 0 && tt) cfg = tt->cfg[oi];
     if (cfg == AQ_CONV_CFG_DIRECT3X3S2) {
         if (pw.direct_cfg != cfg) { aq_set_error("conv op %d has no direct 3x3/s2 form", oi); return AQ_ERR_INVALID; }
@@ -372,11 +373,11 @@ int run_conv(aq_engine* e, int oi, void* ws, const uint8_t* tiles, int B, hipStr
                                     op.res.tensor >= 0 ? tptr(e, ws, tiles, op.res.tensor) : nullptr,
                                     op.res.tensor >= 0 ? e->tensors[op.res.tensor].channels : 0, op.res.ch_off,
                                     pw.w_pl8, pw.sb_pl8, B, ps.h, ps.w, op.act, stream);
-        return aq_conv3x3_pl(tptr(e, ws, tiles, op.src.tensor) + (size_t)op.src.ch_off * 2, (long long)ld * 2, 16, op.src.channels,
-                             tptr(e, ws, tiles, op.dst.tensor), e->tensors[op.dst.tensor].channels, op.dst.ch_off, op.dst.channels,
-                             op.res.tensor >= 0 ? tptr(e, ws, tiles, op.res.tensor) : nullptr,
-                             op.res.tensor >= 0 ? e->tensors[op.res.tensor].channels : 0, op.res.ch_off,
-                             pw.w_direct, pw.bias, B, ps.h, ps.w, op.act, stream);
+        return aq_conv3x3_pl_at(tptr(e, ws, tiles, op.src.tensor) + (size_t)op.src.ch_off * 2, (long long)ld * 2, 16, op.src.channels,
+                                tptr(e, ws, tiles, op.dst.tensor), e->tensors[op.dst.tensor].channels, op.dst.ch_off, op.dst.channels,
+                                op.res.tensor >= 0 ? tptr(e, ws, tiles, op.res.tensor) : nullptr,
+                                op.res.tensor >= 0 ? e->tensors[op.res.tensor].channels : 0, op.res.ch_off,
+                                pw.w_direct, pw.bias, B, ps.h, ps.w, op.act, tt ? tt->B : B, stream);
     }
     if (cfg == AQ_CONV_CFG_PL3X3S2) {
         if (pw.direct_cfg != cfg) { aq_set_error("conv op %d has no planar 3x3/s2 form", oi); return AQ_ERR_INVALID; }

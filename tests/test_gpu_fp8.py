@@ -143,6 +143,9 @@ def test_fp8_engine_matches_the_fp8_oracle(lib, synth_ck):
     # (max 0.163 -> 0.137 and 0.056 -> 0.042) and failed "max <= 3 x max" for it.
     q999 = lambda t: float(torch.quantile(t.flatten(), 0.999))
     assert float(d_eng.mean()) <= 3.0 * float(d_bf.mean()) + 1e-4 and q999(d_eng) <= 3.0 * q999(d_bf) + 1e-3 and float(d_eng.max()) <= float(d_q.max())
+    # ... and an absolute cap on the single worst logit (0.137 after round 4), so that the percentile gate cannot hide one runaway value
+    assert float(d_eng.max()) <= 0.2, (f"fp8 engine vs fp8 oracle: max |d objectness| {float(d_eng.max()):.4g} > 0.2 (mean {float(d_eng.mean()):.3g}, "
+                                       f"99.9th percentile {q999(d_eng):.3g}; oracle fp8 vs bf16 max {float(d_q.max()):.4g})")
     assert float((pred[..., 4] - p16[..., 4]).abs().mean()) > 0.0                  # the fp8 layers did run
     dets, counts = eng.infer(torch.from_numpy(x).cuda())
     assert int(counts.sum()) > 0
