@@ -20,6 +20,7 @@ ARCH = "gfx950"
 
 SOURCES = [
     # (file, extra flags)
+    ("launch_state.hip", []),                    # per-device launch state of every kernel family: CU counts, LDS limits, occupancy, code objects
     ("conv_igemm.hip", []),
     ("conv_halo.hip", []),
     ("stem_conv.hip", []),

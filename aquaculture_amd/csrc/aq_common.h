@@ -92,18 +92,6 @@ int aq_launch_conv(const ConvParams& p, int precision, int out_f32, int cfg, hip
 int aq_conv_pick_config(int cout, int npix, int precision);
 int aq_launch_conv_halo(const ConvParams& p, int precision, int out_f32, int hcfg, bool one_tile_per_wg, hipStream_t stream);
 int aq_conv_halo_num_configs();
-unsigned long long* aq_stamp_buffer(size_t* bytes);
-// 256 zero bytes on the CURRENT device (allocated on first use, one per device, never freed): the LDS-DMA source for pixels
-// outside the image in the standalone kernel entry points (the engine passes its own zero page to the conv kernels).
-const char* aq_zero_page();
-// Compute units the persistent grids are sized for: the device's count, or AQ_NUM_CUS when the caller runs this process's streams on a
-// subset of the CUs (hipExtStreamCreateWithCUMask: bench.py --cu-split gives each of the two batches in flight half of the chip).
-// Read once per kernel family (their grid caches are process-global), so set the variable before the first launch.
-inline hipError_t aq_query_cus(int* cus, int dev) {
-    const char* v = getenv("AQ_NUM_CUS");
-    if (v && atoi(v) > 0) { *cus = atoi(v); return hipSuccess; }
-    return hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
-}
 int aq_conv_halo_tiles(int hcfg, int* bm, int* bn);
 extern "C" int aq_conv_config_tiles(int cfg, int* bm, int* bn);
 // aq_conv3x3_pl with the tile chosen for a batch of pick_B images (the engine passes its tuned table's batch size)
@@ -111,3 +99,22 @@ int aq_conv3x3_pl_at(const void* in_dev, long long in_sp, long long in_ss, int c
                      const void* res_dev, int res_ld, int res_choff, const void* packed_w_dev, const float* bias_dev, int B, int H, int W,
                      int act, int pick_B, void* stream);
 extern "C" int aq_conv_num_configs(void);
+
+// ---- launch-time device state (launch_state.hip): kept per device, under one mutex ----
+// Compute units the persistent grids are sized for: the device's count, or AQ_NUM_CUS when the caller runs this process's streams on a
+// subset of the CUs (hipExtStreamCreateWithCUMask: bench.py --cu-split gives each of the two batches in flight half of the chip).
+// Read once per device, so set the variable before the first launch.
+hipError_t aq_cus(int* cus);
+// Raises fn's dynamic-LDS limit to max_dyn_lds (once per device and kernel).
+hipError_t aq_kernel_lds(const void* fn, int max_dyn_lds);
+// aq_kernel_lds, then the workgroups of `threads` threads and `lds` bytes of dynamic LDS that stay resident per CU (at least 1).
+hipError_t aq_kernel_blocks(const void* fn, int threads, size_t lds, int max_dyn_lds, int* blocks);
+// Kernel `name` of an embedded code object, loaded once per device.  optional: a kernel the object lacks gives a null *fn, not an error.
+hipError_t aq_asm_fn(const void* image, const char* name, hipFunction_t* fn, bool optional);
+// Launches an assembly kernel: a 1-D grid, its argument block passed as one buffer.
+hipError_t aq_asm_launch(hipFunction_t fn, unsigned grid, unsigned threads, void* args, size_t bytes, hipStream_t stream);
+// 256 zero bytes on the CURRENT device (allocated on first use, one per device, never freed): the LDS-DMA source for pixels
+// outside the image in the standalone kernel entry points (the engine passes its own zero page to the conv kernels).
+const char* aq_zero_page();
+// The stamp buffer aq_debug_conv_stamp armed, when it holds bytes_needed; else null (diagnostic builds only).
+unsigned long long* aq_stamp_target(size_t bytes_needed);

@@ -506,8 +506,6 @@ __global__ __launch_bounds__(NW * 64) void bottleneck_kernel(const BtlParams p) 
     }
 }
 
-int g_btl_cus = 0;
-
 struct BtlShape { int mbw, msplit, nw, tw, ktail; bool w1reg, resg; };
 
 // Tile shapes of the HIP-source kernel (since round 4 the fallback for C = 48 / 96: images narrower than two tiles, AQ_BTL_ASM=0 -- the
@@ -534,32 +532,27 @@ bool btl_shape(int C, BtlShape* s) {
 template <int MBW, int MSPLIT, int NW, int TW, int KT, bool W1REG, bool RESG>
 int launch_btl(BtlParams p, hipStream_t stream) {
     using G = BtlGeom<MBW, MSPLIT, NW, TW, KT, W1REG, RESG>;
-    static int occ = 0;                                      // resident workgroups per CU (registers + LDS)
     auto fn = bottleneck_kernel<MBW, MSPLIT, NW, TW, KT, W1REG, RESG>;
     constexpr size_t lds = G::LDS;
     p.tiles_x = (p.W + TW - 1) / TW; p.tiles_y = (p.H + G::TH - 1) / G::TH;
     AQ_REQUIRE((long long)p.B * p.tiles_x * p.tiles_y < (1LL << 30), "bottleneck: batch too large");
     p.n_tiles = p.B * p.tiles_x * p.tiles_y;
+    int cus = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
     if constexpr (MBW * MSPLIT == 3 || MBW * MSPLIT == 6) {  // stamped diagnostic builds exist for C = 48 and C = 96
-        size_t sbytes = 0;
-        unsigned long long* sbuf = aq_stamp_buffer(&sbytes);
-        if (sbuf && (size_t)g_btl_cus * NW * 64 <= sbytes) {
+        if (unsigned long long* sbuf = aq_stamp_target((size_t)cus * NW * 64)) {
             auto sfn = bottleneck_kernel<MBW, MSPLIT, NW, TW, KT, W1REG, RESG, true>;
-            AQ_CHECK_HIP(hipFuncSetAttribute((const void*)sfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS));
+            AQ_CHECK_HIP(aq_kernel_lds((const void*)sfn, (int)G::LDS));
             p.debug = sbuf;
-            const long long sgrid = g_btl_cus < p.n_tiles ? g_btl_cus : p.n_tiles;
+            const long long sgrid = cus < p.n_tiles ? cus : p.n_tiles;
             hipLaunchKernelGGL(sfn, dim3((unsigned)sgrid), dim3(G::THREADS), G::LDS, stream, p);
             AQ_CHECK_HIP(hipGetLastError());
             return AQ_OK;
         }
     }
-    if (!occ) {
-        AQ_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int o = 0;
-        AQ_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)fn, G::THREADS, lds));
-        occ = o > 0 ? o : 1;                                 // a persistent grid must be fully resident
-    }
-    long long grid = (long long)g_btl_cus * occ;
+    int occ = 0;                                             // resident workgroups per CU (registers + LDS)
+    AQ_CHECK_HIP(aq_kernel_blocks((const void*)fn, G::THREADS, lds, (int)lds, &occ));
+    long long grid = (long long)cus * occ;
     if (grid > p.n_tiles) grid = p.n_tiles;
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(G::THREADS), lds, stream, p);
     AQ_CHECK_HIP(hipGetLastError());
@@ -578,19 +571,7 @@ static_assert(sizeof(BtlAsmArgs) == 96, "kernel argument block");
 const unsigned char kBtlAsmCode[] = {
 #include "bottleneck_asm_hsaco.inc"
 };
-hipModule_t g_btl_asm_mod[64];
-hipFunction_t g_btl_asm_fn[64][2];           // plain, stamped
 constexpr size_t kBtlAsmWBytes = (size_t)(6 + 42) * 1024;     // six A fragments of the 1x1, 42 of the 3x3
-
-int btl_asm_load(int dev) {
-    if (g_btl_asm_mod[dev]) return AQ_OK;
-    hipModule_t mod = nullptr;
-    AQ_CHECK_HIP(hipModuleLoadData(&mod, kBtlAsmCode));
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_btl_asm_fn[dev][0], mod, "bottleneck_asm_c48"));
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_btl_asm_fn[dev][1], mod, "bottleneck_asm_c48_stamped"));
-    g_btl_asm_mod[dev] = mod;
-    return AQ_OK;
-}
 
 // AQ_BTL_ASM=0: the HIP-source kernel everywhere (A/B and fallback).
 bool btl_asm_enabled() {
@@ -608,10 +589,8 @@ bool btl_asm_fits(int C, int B, int H, int W, int in_ld, int out_ld) {
 }
 
 int launch_btl_asm(const BtlParams& p, hipStream_t stream) {
-    int dev = 0;
-    AQ_CHECK_HIP(hipGetDevice(&dev));
-    AQ_REQUIRE(dev >= 0 && dev < 64, "bottleneck: device ordinal %d", dev);
-    { const int rc = btl_asm_load(dev); if (rc) return rc; }
+    int cus = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
     BtlAsmArgs a{};
     a.in = p.in; a.out = p.out; a.bias = p.bias;
     a.w = p.w;                                                 // (the caller passes the assembly image: it follows the HIP kernel's in the packed buffer)
@@ -620,27 +599,20 @@ int launch_btl_asm(const BtlParams& p, hipStream_t stream) {
     a.tpi = a.tiles_x * ((p.H + 15) / 16);
     a.ntiles = a.tpi * p.B;
     a.shortcut = p.shortcut;
-    long long grid = g_btl_cus;
+    long long grid = cus;
     if (grid > a.ntiles) grid = a.ntiles;
     a.G = (int)grid;
     a.magic_tpi = (unsigned)((1ULL << 32) / (unsigned)a.tpi + 1);
     a.magic_tx = (unsigned)((1ULL << 32) / (unsigned)a.tiles_x + 1);
     // bytes of the input slice from its first channel to the end of its last pixel: lanes beyond it (and "negative" offsets) read zeros
     a.in_bytes = (unsigned)(((long long)p.B * p.H * p.W - 1) * p.in_ld_b + 96);
-    int which = 0;
-    size_t sbytes = 0;
-    unsigned long long* sbuf = aq_stamp_buffer(&sbytes);
-    if (sbuf && (size_t)grid * 8 * 64 <= sbytes) { a.debug = sbuf; which = 1; }
-    hipFunction_t fn = g_btl_asm_fn[dev][which];
+    a.debug = aq_stamp_target((size_t)grid * 8 * 64);   // an armed stamp buffer that holds this grid: the stamped build
     const char* exp_kernel = getenv("AQ_BTL_ASM_KERNEL");      // timing experiments: another kernel of the code object, by name (tools/time_bottleneck.py)
-    if (exp_kernel && *exp_kernel) {
-        char name[96];
-        snprintf(name, sizeof name, "%s%s", exp_kernel, which ? "_stamped" : "");
-        AQ_CHECK_HIP(hipModuleGetFunction(&fn, g_btl_asm_mod[dev], name));
-    }
-    size_t asz = sizeof(a);
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-    AQ_CHECK_HIP(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 512, 1, 1, 0, stream, nullptr, extra));
+    char name[96];
+    snprintf(name, sizeof name, "%s%s", exp_kernel && *exp_kernel ? exp_kernel : "bottleneck_asm_c48", a.debug ? "_stamped" : "");
+    hipFunction_t fn = nullptr;
+    AQ_CHECK_HIP(aq_asm_fn(kBtlAsmCode, name, &fn, false));
+    AQ_CHECK_HIP(aq_asm_launch(fn, (unsigned)grid, 512, &a, sizeof a, stream));
     return AQ_OK;
 }
 
@@ -673,19 +645,7 @@ void btl_asm_pack(const float* w1, const float* w2, bf16_t* dst) {
 const unsigned char kBtl96AsmCode[] = {
 #include "bottleneck96_asm_hsaco.inc"
 };
-hipModule_t g_btl96_mod[64];
-hipFunction_t g_btl96_fn[64][2];             // plain, stamped
 constexpr size_t kBtl96AsmWBytes = (size_t)2 * (9 + 81) * 1024;     // per channel half: nine A fragments of the 1x1, 81 of the 3x3
-
-int btl96_load(int dev) {
-    if (g_btl96_mod[dev]) return AQ_OK;
-    hipModule_t mod = nullptr;
-    AQ_CHECK_HIP(hipModuleLoadData(&mod, kBtl96AsmCode));
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_btl96_fn[dev][0], mod, "bottleneck_asm_c96"));
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_btl96_fn[dev][1], mod, "bottleneck_asm_c96_stamped"));
-    g_btl96_mod[dev] = mod;
-    return AQ_OK;
-}
 
 // Does the C = 96 assembly kernel take this launch?  (8 x 16 tiles; 32-bit buffer offsets; magic-number tile decode needs >= 2 tiles per row and image.)
 bool btl96_asm_fits(int C, int B, int H, int W, int in_ld, int out_ld) {
@@ -698,10 +658,8 @@ bool btl96_asm_fits(int C, int B, int H, int W, int in_ld, int out_ld) {
 }
 
 int launch_btl96_asm(const BtlParams& p, hipStream_t stream) {
-    int dev = 0;
-    AQ_CHECK_HIP(hipGetDevice(&dev));
-    AQ_REQUIRE(dev >= 0 && dev < 64, "bottleneck: device ordinal %d", dev);
-    { const int rc = btl96_load(dev); if (rc) return rc; }
+    int cus = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
     BtlAsmArgs a{};
     a.in = p.in; a.out = p.out; a.bias = p.bias;
     a.w = p.w;                                                 // (the caller passes the assembly image: it follows the HIP kernel's in the packed buffer)
@@ -710,7 +668,7 @@ int launch_btl96_asm(const BtlParams& p, hipStream_t stream) {
     a.tpi = a.tiles_x * ((p.H + 7) / 8);
     a.ntiles = a.tpi * p.B;
     a.shortcut = p.shortcut;
-    long long grid = g_btl_cus;
+    long long grid = cus;
     if (grid > a.ntiles) grid = a.ntiles;
     a.G = (int)grid;
     a.magic_tpi = (unsigned)((1ULL << 32) / (unsigned)a.tpi + 1);
@@ -718,20 +676,13 @@ int launch_btl96_asm(const BtlParams& p, hipStream_t stream) {
     // bytes of the slices from their first channel to the end of their last pixel: loads beyond read zeros, stores beyond are dropped
     a.in_bytes = (unsigned)(((long long)p.B * p.H * p.W - 1) * p.in_ld_b + 192);
     a.pad = (unsigned)(((long long)p.B * p.H * p.W - 1) * p.out_ld_b + 192);          // (out_bytes in this kernel's argument block)
-    int which = 0;
-    size_t sbytes = 0;
-    unsigned long long* sbuf = aq_stamp_buffer(&sbytes);
-    if (sbuf && (size_t)grid * 4 * 64 <= sbytes) { a.debug = sbuf; which = 1; }
-    hipFunction_t fn = g_btl96_fn[dev][which];
+    a.debug = aq_stamp_target((size_t)grid * 4 * 64);   // an armed stamp buffer that holds this grid: the stamped build
     const char* exp_kernel = getenv("AQ_BTL96_ASM_KERNEL");    // timing experiments: another kernel of the code object, by name (tools/time_bottleneck.py)
-    if (exp_kernel && *exp_kernel) {
-        char name[96];
-        snprintf(name, sizeof name, "%s%s", exp_kernel, which ? "_stamped" : "");
-        AQ_CHECK_HIP(hipModuleGetFunction(&fn, g_btl96_mod[dev], name));
-    }
-    size_t asz = sizeof(a);
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-    AQ_CHECK_HIP(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, stream, nullptr, extra));
+    char name[96];
+    snprintf(name, sizeof name, "%s%s", exp_kernel && *exp_kernel ? exp_kernel : "bottleneck_asm_c96", a.debug ? "_stamped" : "");
+    hipFunction_t fn = nullptr;
+    AQ_CHECK_HIP(aq_asm_fn(kBtl96AsmCode, name, &fn, false));
+    AQ_CHECK_HIP(aq_asm_launch(fn, (unsigned)grid, 256, &a, sizeof a, stream));
     return AQ_OK;
 }
 
@@ -824,12 +775,6 @@ extern "C" int aq_bottleneck(const void* in_dev, int in_ld, int in_choff, void* 
     p.B = B; p.H = H; p.W = W; p.shortcut = shortcut;
     p.zero = aq_zero_page();
     AQ_REQUIRE(p.zero, "bottleneck: zero page allocation failed");
-    if (g_btl_cus == 0) {
-        int dev = 0, cus = 256;
-        AQ_CHECK_HIP(hipGetDevice(&dev));
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_btl_cus = cus;
-    }
     const hipStream_t st = (hipStream_t)stream;
     if (btl_asm_fits(C, B, H, W, in_ld, out_ld)) {
         BtlShape sh48;

@@ -26,21 +26,6 @@ static_assert(sizeof(C1AsmArgs) == 96, "kernel argument block");
 const unsigned char kC1AsmCode[] = {
 #include "conv1x1_asm_hsaco.inc"
 };
-hipModule_t g_c1a_mod[64];
-hipFunction_t g_c1a_fn[64][2][2];            // [family nb13 / nb7][plain, stamped]
-int g_c1a_cus = 0;
-
-int c1a_load(int dev) {
-    if (g_c1a_mod[dev]) return AQ_OK;
-    hipModule_t mod = nullptr;
-    AQ_CHECK_HIP(hipModuleLoadData(&mod, kC1AsmCode));
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_c1a_fn[dev][0][0], mod, "conv1x1_asm_nb13"));
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_c1a_fn[dev][0][1], mod, "conv1x1_asm_nb13_stamped"));
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_c1a_fn[dev][1][0], mod, "conv1x1_asm_nb7"));
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_c1a_fn[dev][1][1], mod, "conv1x1_asm_nb7_stamped"));
-    g_c1a_mod[dev] = mod;
-    return AQ_OK;
-}
 
 // Output channel of row r = 4 g + e of M block m of wave w in channel tile ct: lane group g's twelve outputs of a pixel are 8 consecutive
 // channels (blocks 0 and 1) and 4 consecutive ones (block 2) of the wave's 48.
@@ -99,15 +84,8 @@ extern "C" int aq_conv1x1_asm(const void* in_dev, int in_ld, int in_choff, void*
     // 32-bit buffer offsets; "no tile left" fetches from in_bytes + 0x100 + lane parts, which must not wrap
     AQ_REQUIRE(npix > 0 && npix * (long long)in_ld * 2 < (1LL << 31) - (1LL << 22) && npix * (long long)out_ld * 2 < (1LL << 32) - (1LL << 22),
                "conv1x1_asm: tensor too large for 32-bit offsets");
-    int dev = 0;
-    AQ_CHECK_HIP(hipGetDevice(&dev));
-    AQ_REQUIRE(dev >= 0 && dev < 64, "conv1x1_asm: device ordinal %d", dev);
-    { const int rc = c1a_load(dev); if (rc) return rc; }
-    if (g_c1a_cus == 0) {
-        int cus = 256;
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_c1a_cus = cus;
-    }
+    int cus = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
     C1AsmArgs a{};
     a.in = (const char*)in_dev + (size_t)in_choff * 2;
     a.out = (char*)out_dev + (size_t)out_choff * 2;
@@ -123,7 +101,7 @@ extern "C" int aq_conv1x1_asm(const void* in_dev, int in_ld, int in_choff, void*
     int fam = 0;
     {
         const long long t13 = (npix + kTPX[0] - 1) / kTPX[0] * nct, t7 = (npix + kTPX[1] - 1) / kTPX[1] * nct;
-        const double c13 = (double)((t13 + g_c1a_cus - 1) / g_c1a_cus) * 13.0, c7 = (double)((t7 + g_c1a_cus - 1) / g_c1a_cus) * 7.0 * 1.15;
+        const double c13 = (double)((t13 + cus - 1) / cus) * 13.0, c7 = (double)((t7 + cus - 1) / cus) * 7.0 * 1.15;
         if (c7 < c13) fam = 1;
         const char* fe = getenv("AQ_C1_ASM_NB");          // (read per call: tests and tools/time_conv1x1_asm.py switch it)
         const int forced = fe ? atoi(fe) : 0;
@@ -132,7 +110,7 @@ extern "C" int aq_conv1x1_asm(const void* in_dev, int in_ld, int in_choff, void*
     }
     const long long ptiles = (npix + kTPX[fam] - 1) / kTPX[fam];
     a.ntiles = (int)(ptiles * nct);
-    long long grid = g_c1a_cus;
+    long long grid = cus;
     if (grid > a.ntiles) grid = a.ntiles;
     a.G = (int)grid;
     a.in_bytes = (unsigned)((npix - 1) * a.in_ld_b + (long long)cin * 2);
@@ -140,19 +118,12 @@ extern "C" int aq_conv1x1_asm(const void* in_dev, int in_ld, int in_choff, void*
     a.w_bytes = (unsigned)c1a_weight_bytes(cin, cout);
     a.stream_b = (unsigned)((cin / 32) * kStepB);
     a.cout = cout;
-    int which = 0;
-    size_t sbytes = 0;
-    unsigned long long* sbuf = aq_stamp_buffer(&sbytes);
-    if (sbuf && (size_t)grid * 8 * 64 <= sbytes) { a.debug = sbuf; which = 1; }
-    hipFunction_t fn = g_c1a_fn[dev][fam][which];
+    a.debug = aq_stamp_target((size_t)grid * 8 * 64);   // an armed stamp buffer that holds this grid: the stamped build
     const char* exp_kernel = getenv("AQ_C1_ASM_KERNEL");       // timing experiments: another kernel of the code object, by name (tools/time_conv1x1.py)
-    if (exp_kernel && *exp_kernel) {
-        char name[96];
-        snprintf(name, sizeof name, "%s%s", exp_kernel, which ? "_stamped" : "");
-        AQ_CHECK_HIP(hipModuleGetFunction(&fn, g_c1a_mod[dev], name));
-    }
-    size_t asz = sizeof(a);
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-    AQ_CHECK_HIP(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 512, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+    char name[96];
+    snprintf(name, sizeof name, "%s%s", exp_kernel && *exp_kernel ? exp_kernel : fam ? "conv1x1_asm_nb7" : "conv1x1_asm_nb13", a.debug ? "_stamped" : "");
+    hipFunction_t fn = nullptr;
+    AQ_CHECK_HIP(aq_asm_fn(kC1AsmCode, name, &fn, false));
+    AQ_CHECK_HIP(aq_asm_launch(fn, (unsigned)grid, 512, &a, sizeof a, (hipStream_t)stream));
     return AQ_OK;
 }

@@ -146,19 +146,15 @@ __global__ __launch_bounds__(kNW * 64) void conv1x1_direct_kernel(const C1Params
     }
 }
 
-int g_c1_cus = 0;
-
 template <int KS, int MBT, int MBW, int NBW, bool F8OUT = false>
 int launch_c1(C1Params p, hipStream_t stream) {
     using G = C1Geom<KS, MBT, MBW, NBW>;
-    static bool attr = false;
     auto fn = conv1x1_direct_kernel<KS, MBT, MBW, NBW, F8OUT>;
-    if (!attr) {
-        AQ_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        attr = true;
-    }
+    int cus = 0;
+    AQ_CHECK_HIP(aq_kernel_lds((const void*)fn, G::LDS));
+    AQ_CHECK_HIP(aq_cus(&cus));
     p.n_tiles = (p.npix + G::TP - 1) / G::TP;
-    long long grid = g_c1_cus;                               // > 80 KB of LDS: one persistent workgroup per CU
+    long long grid = cus;                                    // > 80 KB of LDS: one persistent workgroup per CU
     if (grid > p.n_tiles) grid = p.n_tiles;
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kNW * 64), G::LDS, stream, p);
     AQ_CHECK_HIP(hipGetLastError());
@@ -212,12 +208,6 @@ extern "C" int aq_conv1x1_direct(const void* in_dev, int in_ld, int in_choff, vo
     p.npix = (int)npix; p.act = act;
     p.zero = aq_zero_page();
     AQ_REQUIRE(p.zero, "conv1x1_direct: zero page allocation failed");
-    if (g_c1_cus == 0) {
-        int dev = 0, cus = 256;
-        AQ_CHECK_HIP(hipGetDevice(&dev));
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_c1_cus = cus;
-    }
     const hipStream_t st = (hipStream_t)stream;
     if (cin == 96) return launch_c1<3, 6, 2, 4>(p, st);      // 3 channel pairs x 4 pixel groups, 256-pixel tiles
     if (cin == 192) return launch_c1<6, 12, 2, 4>(p, st);    // 6 x 2, 128-pixel tiles
@@ -243,12 +233,6 @@ extern "C" int aq_conv1x1_direct_f8out(const void* in_dev, int in_ld, int in_cho
     p.npix = (int)npix; p.act = act; p.out_inv_scale = 1.0f / out_scale;
     p.zero = aq_zero_page();
     AQ_REQUIRE(p.zero, "conv1x1_direct_f8out: zero page allocation failed");
-    if (g_c1_cus == 0) {
-        int dev = 0, cus = 256;
-        AQ_CHECK_HIP(hipGetDevice(&dev));
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_c1_cus = cus;
-    }
     const hipStream_t st = (hipStream_t)stream;
     if (cin == 192) return launch_c1<6, 12, 2, 4, true>(p, st);
     return launch_c1<12, 24, 2, 4, true>(p, st);

@@ -407,11 +407,6 @@ const unsigned char kPlAsmCode[] = {
 struct PlAsmFamily { int nb, rows, occ; };
 const PlAsmFamily kPlAsm[] = {{13, 384, 1}, {7, 256, 2}, {8, 256, 2}};
 constexpr int kNumPlAsm = sizeof(kPlAsm) / sizeof(kPlAsm[0]);
-hipModule_t g_pl_asm_mod[64];
-hipFunction_t g_pl_asm_fn[64][kNumPlAsm][5];     // res0, res1, res1 stamped, and (NB = 13 only) the fp8-weight res0, res1
-hipFunction_t g_pl_s2_fn[64][2];                 // stride-2 family (s2nb13): plain, stamped
-hipFunction_t g_pl_f8_fn[64][3];                 // fp8 family (f8nb13): res0, res1, res1 stamped
-hipFunction_t g_pl_pm_fn[64][3][3];              // pixel-major builds of the stride-1 bf16 kernel (pm13: any width, pm13w20, pm13w40) x (res0, res1, res1 stamped)
 constexpr int PL_S2_NB = 13, PL_S2_ROWS = 304;   // gen_conv3x3_pl_asm.py CONFIGS["s2nb13"]
 
 struct PlKernel { int nb; void (*plain)(const PlParams); void (*res)(const PlParams); };
@@ -421,8 +416,6 @@ const PlAblation kPlAbl[] = { PLA(16) };
 #define PLK(NB) { NB, conv3x3_pl_kernel<NB, false>, conv3x3_pl_kernel<NB, true> }
 const PlKernel kPl[] = { PLK(13), PLK(10), PLK(7) };
 constexpr int kNumPl = sizeof(kPl) / sizeof(kPl[0]);
-bool g_pl_attr[64][kNumPl][2];
-int g_pl_cus[64];
 
 // widest run of padded coordinates any tile of bn pixels needs, halo included.  O(npix / bn) divisions: remembered per geometry, because
 // every launch asks several times (~1 ms of launch-thread time per step otherwise, invisible to the event-timed tuner)
@@ -455,49 +448,19 @@ int pl_region_rows_uncached(int B, int H, int W, int bn) {
     return (int)worst;
 }
 
-int pl_load_module(int dev) {
-    if (g_pl_asm_mod[dev]) return AQ_OK;
-    hipModule_t mod = nullptr;
-    AQ_CHECK_HIP(hipModuleLoadData(&mod, kPlAsmCode));
-    for (int i = 0; i < kNumPlAsm; ++i)
-        for (int v = 0; v < (kPlAsm[i].nb == 13 ? 5 : 3); ++v) {
-            char name[64];
-            snprintf(name, sizeof name, "conv3x3_pl_asm_nb%d_res%d%s", kPlAsm[i].nb, v == 0 || v == 3 ? 0 : 1,
-                     v == 2 ? "_stamped" : v >= 3 ? "_w8" : "");
-            const hipError_t e = hipModuleGetFunction(&g_pl_asm_fn[dev][i][v], mod, name);
-            if (e != hipSuccess && kPlAsm[i].nb != 13) {    // the two-workgroup families are built only with AQ_GEN_EXPERIMENTAL=1
-                (void)hipGetLastError();
-                g_pl_asm_fn[dev][i][v] = nullptr;
-                continue;
-            }
-            AQ_CHECK_HIP(e);
-        }
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_pl_s2_fn[dev][0], mod, "conv3x3_pl_asm_s2nb13_res0"));
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_pl_s2_fn[dev][1], mod, "conv3x3_pl_asm_s2nb13_res0_stamped"));
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_pl_f8_fn[dev][0], mod, "conv3x3_pl_asm_f8nb13_res0"));
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_pl_f8_fn[dev][1], mod, "conv3x3_pl_asm_f8nb13_res1"));
-    AQ_CHECK_HIP(hipModuleGetFunction(&g_pl_f8_fn[dev][2], mod, "conv3x3_pl_asm_f8nb13_res1_stamped"));
-    for (int f = 0; f < 3; ++f)
-        for (int v = 0; v < 3; ++v) {
-            char name[64];
-            snprintf(name, sizeof name, "conv3x3_pl_asm_pm13%s_res%d%s", f == 0 ? "" : f == 1 ? "w20" : "w40", v ? 1 : 0, v == 2 ? "_stamped" : "");
-            AQ_CHECK_HIP(hipModuleGetFunction(&g_pl_pm_fn[dev][f][v], mod, name));
-        }
-    g_pl_asm_mod[dev] = mod;
-    return AQ_OK;
-}
-
 }  // namespace
 
 // 1 when the assembly family with `nb` pixel blocks per tile is in this build (13 always; 7 and 8 -- two workgroups per CU, measured no
 // faster anywhere on the BASELINE geometries -- only when the library was built with AQ_GEN_EXPERIMENTAL=1), 0 when not, < 0 on error.
 extern "C" int aq_conv3x3_pl_asm_family(int nb) {
-    int dev = 0;
-    AQ_CHECK_HIP(hipGetDevice(&dev));
-    AQ_REQUIRE(dev >= 0 && dev < 64, "conv3x3_pl_asm_family: device ordinal %d", dev);
-    { const int rc = pl_load_module(dev); if (rc) return rc; }
     for (int i = 0; i < kNumPlAsm; ++i)
-        if (kPlAsm[i].nb == nb) return g_pl_asm_fn[dev][i][0] ? 1 : 0;
+        if (kPlAsm[i].nb == nb) {
+            char name[64];
+            snprintf(name, sizeof name, "conv3x3_pl_asm_nb%d_res0", nb);
+            hipFunction_t fn = nullptr;
+            AQ_CHECK_HIP(aq_asm_fn(kPlAsmCode, name, &fn, nb != 13));     // the two-workgroup families are built only with AQ_GEN_EXPERIMENTAL=1
+            return fn ? 1 : 0;
+        }
     return 0;
 }
 
@@ -565,14 +528,8 @@ static int pl_conv(const void* in_dev, long long in_sp, long long in_ss, int cin
     AQ_REQUIRE(!res_dev || (res_ld % 4 == 0 && res_choff % 4 == 0 && res_choff + cout <= res_ld), "conv3x3_pl: bad residual slice");
     AQ_REQUIRE((long long)B * H * W * out_ld * 2 < (1LL << 31) && (long long)B * H * W * res_ld * 2 < (1LL << 31),
                "conv3x3_pl: output / residual tensors beyond the 32-bit offset range");
-    int dev = 0;
-    AQ_CHECK_HIP(hipGetDevice(&dev));
-    AQ_REQUIRE(dev >= 0 && dev < 64, "conv3x3_pl: device ordinal %d", dev);
-    if (g_pl_cus[dev] == 0) {
-        int cus = 256;
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_pl_cus[dev] = cus;
-    }
+    int cus = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
     PlParams p{};
     p.in = (const char*)in_dev; p.in_sp = in_sp; p.in_ss = in_ss;
     p.out = (char*)out_dev + (size_t)out_choff * 2; p.out_ld_b = out_ld * 2;
@@ -589,8 +546,8 @@ static int pl_conv(const void* in_dev, long long in_sp, long long in_ss, int cin
     // pick_B: the batch size whose tile count chooses the tile.  The tile width decides the build (assembly / pixel-major / HIP source)
     // and with it the accumulation order, so an engine running a tuned table passes the table's batch size: a tile's result then does
     // not depend on which batch it landed in.  (A batch whose tiles would not fit the region rows at that width picks its own.)
-    int rows = 0, k = pl_pick(pick_B > 0 ? pick_B : B, H, W, p.n_mt, g_pl_cus[dev], &rows);
-    if (k >= 0 && pick_B > 0 && pick_B != B && pl_region_rows(B, H, W, kPl[k].nb * 16) > PL_ROWS) k = pl_pick(B, H, W, p.n_mt, g_pl_cus[dev], &rows);
+    int rows = 0, k = pl_pick(pick_B > 0 ? pick_B : B, H, W, p.n_mt, cus, &rows);
+    if (k >= 0 && pick_B > 0 && pick_B != B && pl_region_rows(B, H, W, kPl[k].nb * 16) > PL_ROWS) k = pl_pick(B, H, W, p.n_mt, cus, &rows);
     const char* forced = getenv("AQ_PL_NB");
     const char* use_asm = getenv("AQ_PL_ASM");
     const char* abl = getenv("AQ_PL_ABL");                  // timing-only diagnostic builds (wrong results), NB = 13 with shortcut only
@@ -601,12 +558,15 @@ static int pl_conv(const void* in_dev, long long in_sp, long long in_ss, int cin
         for (int i = 0; i < kNumPl; ++i)
             if (kPl[i].nb == nb && pl_region_rows(B, H, W, nb * 16) <= PL_ROWS) k = i;
     }
-    { const int rc = pl_load_module(dev); if (rc) return rc; }
     int fam = -1;
     if (w8) nb = 13;                                        // the fp8-weight stream exists in the NB = 13 assembly family only
     if ((w8 || (!(use_asm && *use_asm == '0') && !(abl && *abl))) && (p.n_mt & (p.n_mt - 1)) == 0 && in_sp < (1LL << 32) && in_ss < (1LL << 31))
         for (int i = 0; i < kNumPlAsm; ++i)
-            if (kPlAsm[i].nb == nb && g_pl_asm_fn[dev][i][0] && pl_region_rows(B, H, W, nb * 16) <= kPlAsm[i].rows) fam = i;
+            if (kPlAsm[i].nb == nb && pl_region_rows(B, H, W, nb * 16) <= kPlAsm[i].rows) {
+                const int built = aq_conv3x3_pl_asm_family(nb);
+                if (built < 0) return built;
+                if (built) fam = i;
+            }
     AQ_REQUIRE(!w8 || fam >= 0, "conv3x3_pl_w8: shape outside the fp8-weight kernel (aq_conv3x3_pl_w8_supported)");
     AQ_REQUIRE(k >= 0 || fam >= 0, "conv3x3_pl: no tile of this kernel fits a %d-wide image in its region rows", W);
     const int bn = nb * 16;
@@ -614,7 +574,7 @@ static int pl_conv(const void* in_dev, long long in_sp, long long in_ss, int cin
     AQ_REQUIRE(ntiles > 0 && ntiles < (1LL << 30), "conv3x3_pl: bad tile count");
     p.ntiles = (int)ntiles;
     if (fam >= 0) {
-        long long grid = (long long)g_pl_cus[dev] * kPlAsm[fam].occ;
+        long long grid = (long long)cus * kPlAsm[fam].occ;
         if (grid > ntiles) grid = ntiles;
         PlAsmArgs a{};
         a.in = p.in; a.in_sp = p.in_sp; a.in_ss = p.in_ss; a.out = p.out; a.res = p.res; a.w = p.w; a.bias = p.bias; a.zero = p.zero;
@@ -623,13 +583,9 @@ static int pl_conv(const void* in_dev, long long in_sp, long long in_ss, int cin
         a.mt_log2 = 0;
         while ((1 << a.mt_log2) < p.n_mt) ++a.mt_log2;
         a.inv_hw = p.inv_hw; a.inv_w = p.inv_w; a.inv_hpwp = p.inv_hpwp; a.inv_wp = p.inv_wp; a.debug = nullptr;
-        int which = (res_dev ? 1 : 0) + (w8 ? 3 : 0);
-        if (!w8 && use_asm && *use_asm == '2' && res_dev) {        // stamped diagnostic build (tools/time_conv3x3.py --stamp): per-wave phase cycle sums
-            size_t sbytes = 0;
-            unsigned long long* sbuf = aq_stamp_buffer(&sbytes);
-            if (sbuf && sbytes >= (size_t)grid * 4 * 64) { a.debug = sbuf; which = 2; }
-        }
-        hipFunction_t fn_asm = g_pl_asm_fn[dev][fam][which];
+        if (!w8 && use_asm && *use_asm == '2' && res_dev)          // stamped diagnostic build (tools/time_conv3x3.py --stamp): per-wave phase cycle sums
+            a.debug = aq_stamp_target((size_t)grid * 4 * 64);
+        const bool stamped = a.debug != nullptr;
         // The pixel-major build of the same kernel (family pm13: same tiles, weights, arguments and results; 64-byte pixel-major region rows
         // loaded through a buffer descriptor -- a quarter of the cache-line look-ups per LDS-DMA instruction) wherever its addressing holds:
         // contiguous channel groups, 24-bit pixel stride and pixel count, the tensor inside 2 GiB.  It pays where the image width is known at
@@ -641,17 +597,19 @@ static int pl_conv(const void* in_dev, long long in_sp, long long in_ss, int cin
         const int pmf = pm_mode == 2 ? 0 : W == 20 ? 1 : W == 40 ? 2 : 0;
         const bool pm = nb == 13 && !w8 && pm_mode != 0 && (pmf != 0 || pm_mode == 2) && in_ss == 16 && in_sp < (1 << 24) && in_sp % 16 == 0 &&
                         p.npix < (1 << 24) && (long long)p.npix * in_sp < (1LL << 31);
-        if (pm) fn_asm = g_pl_pm_fn[dev][pmf][which];
         const char* asm_abl = getenv("AQ_PL_ASM_ABL");      // timing-only ablations of the stamped build (wrong results)
-        if (which == 2 && asm_abl && *asm_abl) {
-            char name[80];
+        char name[80];
+        if (stamped && asm_abl && *asm_abl) {
             if (pm) snprintf(name, sizeof name, "conv3x3_pl_asm_pm13w40_res1_stamped_abl%d", atoi(asm_abl));
             else snprintf(name, sizeof name, "conv3x3_pl_asm_nb%d_res1_stamped_abl%d", nb, atoi(asm_abl));
-            AQ_CHECK_HIP(hipModuleGetFunction(&fn_asm, g_pl_asm_mod[dev], name));
+        } else if (pm) {
+            snprintf(name, sizeof name, "conv3x3_pl_asm_pm13%s_res%d%s", pmf == 1 ? "w20" : pmf == 2 ? "w40" : "", res_dev ? 1 : 0, stamped ? "_stamped" : "");
+        } else {
+            snprintf(name, sizeof name, "conv3x3_pl_asm_nb%d_res%d%s", nb, res_dev ? 1 : 0, stamped ? "_stamped" : w8 ? "_w8" : "");
         }
-        size_t asz = sizeof(a);
-        void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-        AQ_CHECK_HIP(hipModuleLaunchKernel(fn_asm, (unsigned)grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+        hipFunction_t fn_asm = nullptr;
+        AQ_CHECK_HIP(aq_asm_fn(kPlAsmCode, name, &fn_asm, false));
+        AQ_CHECK_HIP(aq_asm_launch(fn_asm, (unsigned)grid, 256, &a, sizeof a, (hipStream_t)stream));
         return AQ_OK;
     }
     auto fn = res_dev ? kPl[k].res : kPl[k].plain;
@@ -659,19 +617,11 @@ static int pl_conv(const void* in_dev, long long in_sp, long long in_ss, int cin
     if (abl && *abl && kPl[k].nb == 13 && res_dev)
         for (const PlAblation& a : kPlAbl)
             if (a.abl == atoi(abl)) { fn = a.fn; ablated = true; }
-    if (ablated) {
-        size_t sbytes = 0;
-        unsigned long long* sbuf = aq_stamp_buffer(&sbytes);
-        if (sbuf && sbytes >= (size_t)g_pl_cus[dev] * 4 * 64) p.debug = sbuf;
-    }
+    if (ablated) p.debug = aq_stamp_target((size_t)cus * 4 * 64);
     const size_t lds = (size_t)PL_BIAS + 4096;
     AQ_REQUIRE(lds <= 160 * 1024, "conv3x3_pl: LDS");
-    if (ablated) AQ_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (!g_pl_attr[dev][k][res_dev ? 1 : 0]) {
-        AQ_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        g_pl_attr[dev][k][res_dev ? 1 : 0] = true;
-    }
-    long long grid = g_pl_cus[dev];
+    AQ_CHECK_HIP(aq_kernel_lds((const void*)fn, 160 * 1024));
+    long long grid = cus;
     if (grid > ntiles) grid = ntiles;
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, p);
     AQ_CHECK_HIP(hipGetLastError());
@@ -834,15 +784,8 @@ extern "C" int aq_conv3x3_pl_s2(const void* in_dev, int in_ld, int in_choff, int
     // (the input goes through a buffer descriptor with num_records = 2^31: valid offsets must stay below it, the padding rows' 2^31 is beyond)
     AQ_REQUIRE((long long)B * Ho * Wo * out_ld * 2 < (1LL << 31) && (long long)B * H * W * in_ld * 2 < (1LL << 31) && in_ld * 2 < (1 << 24),
                "conv3x3_pl_s2: tensors beyond the 31-bit offset range");
-    int dev = 0;
-    AQ_CHECK_HIP(hipGetDevice(&dev));
-    AQ_REQUIRE(dev >= 0 && dev < 64, "conv3x3_pl_s2: device ordinal %d", dev);
-    if (g_pl_cus[dev] == 0) {
-        int cus = 256;
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_pl_cus[dev] = cus;
-    }
-    { const int rc = pl_load_module(dev); if (rc) return rc; }
+    int cus = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
     PlAsmArgs a{};
     a.in = (const char*)in_dev + (size_t)in_choff * 2; a.in_sp = (long long)in_ld * 2; a.in_ss = 16;
     a.in_row = (long long)W * in_ld * 2;
@@ -858,30 +801,21 @@ extern "C" int aq_conv3x3_pl_s2(const void* in_dev, int in_ld, int in_choff, int
     const long long ntiles = ((long long)a.npix + bn - 1) / bn * n_mt;
     AQ_REQUIRE(ntiles > 0 && ntiles < (1LL << 30), "conv3x3_pl_s2: bad tile count");
     a.ntiles = (int)ntiles;
-    long long grid = g_pl_cus[dev];
+    long long grid = cus;
     if (grid > ntiles) grid = ntiles;
     a.G = (int)grid;
     a.inv_hw = 1.0f / (float)(Ho * Wo); a.inv_w = 1.0f / (float)Wo;
     a.inv_hpwp = 1.0f / (float)((Ho + 1) * (Wo + 1)); a.inv_wp = 1.0f / (float)(Wo + 1);
-    hipFunction_t fn = g_pl_s2_fn[dev][0];
     const char* use_asm = getenv("AQ_PL_ASM");
-    if (use_asm && *use_asm == '2') {                          // stamped diagnostic build (tools/time_conv3x3.py --stamp): per-wave phase cycle sums
-        size_t sbytes = 0;
-        unsigned long long* sbuf = aq_stamp_buffer(&sbytes);
-        if (sbuf && sbytes >= (size_t)grid * 4 * 64) {
-            a.debug = sbuf;
-            fn = g_pl_s2_fn[dev][1];
-            const char* asm_abl = getenv("AQ_PL_ASM_ABL");    // timing-only ablations of the stamped build (wrong results)
-            if (asm_abl && *asm_abl) {
-                char name[80];
-                snprintf(name, sizeof name, "conv3x3_pl_asm_s2nb13_res0_stamped_abl%d", atoi(asm_abl));
-                AQ_CHECK_HIP(hipModuleGetFunction(&fn, g_pl_asm_mod[dev], name));
-            }
-        }
-    }
-    size_t asz = sizeof(a);
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-    AQ_CHECK_HIP(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+    if (use_asm && *use_asm == '2')                            // stamped diagnostic build (tools/time_conv3x3.py --stamp): per-wave phase cycle sums
+        a.debug = aq_stamp_target((size_t)grid * 4 * 64);
+    const char* asm_abl = getenv("AQ_PL_ASM_ABL");            // timing-only ablations of the stamped build (wrong results)
+    char name[80];
+    if (a.debug && asm_abl && *asm_abl) snprintf(name, sizeof name, "conv3x3_pl_asm_s2nb13_res0_stamped_abl%d", atoi(asm_abl));
+    else snprintf(name, sizeof name, "conv3x3_pl_asm_s2nb13_res0%s", a.debug ? "_stamped" : "");
+    hipFunction_t fn = nullptr;
+    AQ_CHECK_HIP(aq_asm_fn(kPlAsmCode, name, &fn, false));
+    AQ_CHECK_HIP(aq_asm_launch(fn, (unsigned)grid, 256, &a, sizeof a, (hipStream_t)stream));
     return AQ_OK;
 }
 
@@ -976,15 +910,8 @@ extern "C" int aq_conv3x3_pl_f8(const void* in_dev, int in_ld, int in_choff, int
     AQ_REQUIRE(!res_dev || (res_ld % 4 == 0 && res_choff % 4 == 0 && res_choff + cout <= res_ld), "conv3x3_pl_f8: bad residual slice");
     AQ_REQUIRE((long long)B * H * W * out_ld * 2 < (1LL << 31) && (long long)B * H * W * res_ld * 2 < (1LL << 31) && (long long)B * H * W * in_ld < (1LL << 31) &&
                    in_ld < (1 << 24), "conv3x3_pl_f8: tensors beyond the 31-bit offset range");
-    int dev = 0;
-    AQ_CHECK_HIP(hipGetDevice(&dev));
-    AQ_REQUIRE(dev >= 0 && dev < 64, "conv3x3_pl_f8: device ordinal %d", dev);
-    if (g_pl_cus[dev] == 0) {
-        int cus = 256;
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_pl_cus[dev] = cus;
-    }
-    { const int rc = pl_load_module(dev); if (rc) return rc; }
+    int cus = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
     PlAsmArgs a{};
     a.in = (const char*)in_dev + in_choff; a.in_sp = in_ld; a.in_ss = 16;
     a.out = (char*)out_dev + (size_t)out_choff * 2; a.out_ld_b = out_ld * 2;
@@ -999,29 +926,20 @@ extern "C" int aq_conv3x3_pl_f8(const void* in_dev, int in_ld, int in_choff, int
     const long long ntiles = ((long long)a.npix + 207) / 208 * n_mt;
     AQ_REQUIRE(ntiles > 0 && ntiles < (1LL << 30), "conv3x3_pl_f8: bad tile count");
     a.ntiles = (int)ntiles;
-    long long grid = g_pl_cus[dev];
+    long long grid = cus;
     if (grid > ntiles) grid = ntiles;
     a.G = (int)grid;
     a.inv_hw = 1.0f / (float)(H * W); a.inv_w = 1.0f / (float)W;
     a.inv_hpwp = 1.0f / (float)((H + 1) * (W + 1)); a.inv_wp = 1.0f / (float)(W + 1);
-    hipFunction_t fn = g_pl_f8_fn[dev][res_dev ? 1 : 0];
     const char* use_asm = getenv("AQ_PL_ASM");
-    if (use_asm && *use_asm == '2' && res_dev) {              // stamped diagnostic build
-        size_t sbytes = 0;
-        unsigned long long* sbuf = aq_stamp_buffer(&sbytes);
-        if (sbuf && sbytes >= (size_t)grid * 4 * 64) {
-            a.debug = sbuf;
-            fn = g_pl_f8_fn[dev][2];
-            const char* asm_abl = getenv("AQ_PL_ASM_ABL");
-            if (asm_abl && *asm_abl) {
-                char name[80];
-                snprintf(name, sizeof name, "conv3x3_pl_asm_f8nb13_res1_stamped_abl%d", atoi(asm_abl));
-                AQ_CHECK_HIP(hipModuleGetFunction(&fn, g_pl_asm_mod[dev], name));
-            }
-        }
-    }
-    size_t asz = sizeof(a);
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-    AQ_CHECK_HIP(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+    if (use_asm && *use_asm == '2' && res_dev)                 // stamped diagnostic build
+        a.debug = aq_stamp_target((size_t)grid * 4 * 64);
+    const char* asm_abl = getenv("AQ_PL_ASM_ABL");
+    char name[80];
+    if (a.debug && asm_abl && *asm_abl) snprintf(name, sizeof name, "conv3x3_pl_asm_f8nb13_res1_stamped_abl%d", atoi(asm_abl));
+    else snprintf(name, sizeof name, "conv3x3_pl_asm_f8nb13_res%d%s", res_dev ? 1 : 0, a.debug ? "_stamped" : "");
+    hipFunction_t fn = nullptr;
+    AQ_CHECK_HIP(aq_asm_fn(kPlAsmCode, name, &fn, false));
+    AQ_CHECK_HIP(aq_asm_launch(fn, (unsigned)grid, 256, &a, sizeof a, (hipStream_t)stream));
     return AQ_OK;
 }

@@ -313,8 +313,6 @@ const HaloConfig kHalo[] = {
     HCFG(128, 256, 2, 2),   // per-wave 64x128, 4 waves
 };
 constexpr int kNumHalo = sizeof(kHalo) / sizeof(kHalo[0]);
-bool g_halo_attr[kNumHalo][2];
-int g_halo_cus = 0;
 
 }  // namespace
 
@@ -356,25 +354,17 @@ int aq_launch_conv_halo(const ConvParams& p_in, int precision, int out_f32, int 
     if (lds > 160 * 1024 || (wbuf < stg && xb < stg)) { aq_set_error("halo conv: config %d does not fit LDS for W=%d", hcfg, p.W); return AQ_ERR_INVALID; }
     const int variant = precision == AQ_FP32 ? 1 : 0;
     auto fn = variant ? k.f32 : k.bf16;
-    if (!g_halo_attr[hcfg][variant]) {
-        AQ_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        g_halo_attr[hcfg][variant] = true;
-    }
-    if (g_halo_cus == 0) {
-        int dev = 0, cus = 256;
-        AQ_CHECK_HIP(hipGetDevice(&dev));
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_halo_cus = cus;
-    }
-    long long grid = g_halo_cus;          // > 80 KiB of LDS per workgroup: one resident workgroup per CU
+    int cus = 0;
+    AQ_CHECK_HIP(aq_kernel_lds((const void*)fn, 160 * 1024));
+    AQ_CHECK_HIP(aq_cus(&cus));
+    long long grid = cus;                 // > 80 KiB of LDS per workgroup: one resident workgroup per CU
     if (lds <= 80 * 1024) grid *= 2;
     if (grid > ntiles) grid = ntiles;
     if (one_tile_per_wg) grid = ntiles;     // see aq_launch_conv
-    size_t sbytes = 0;
-    unsigned long long* sbuf = aq_stamp_buffer(&sbytes);
-    if (sbuf && variant == 0 && hcfg == 0 && (size_t)grid * nw * 64 <= sbytes) {
+    unsigned long long* sbuf = variant == 0 && hcfg == 0 ? aq_stamp_target((size_t)grid * nw * 64) : nullptr;
+    if (sbuf) {
         auto sfn = conv3x3_halo_kernel<false, 192, 256, 2, 4, true>;
-        AQ_CHECK_HIP(hipFuncSetAttribute((const void*)sfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        AQ_CHECK_HIP(aq_kernel_lds((const void*)sfn, 160 * 1024));
         p.debug = sbuf;
         hipLaunchKernelGGL(sfn, dim3((unsigned)grid), dim3(k.threads), lds, stream, p);
         AQ_CHECK_HIP(hipGetLastError());

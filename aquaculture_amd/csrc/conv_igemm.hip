@@ -566,37 +566,13 @@ const StampedKernel kStamped[] = {
     {7, conv_igemm_kernel<false, 128, 128, 2, 2, false, 2, true, true>},
     {10, conv_igemm_kernel<false, 64, 128, 1, 4, false, 2, true, true>},
 };
-unsigned long long* g_stamp_buf = nullptr;
-size_t g_stamp_bytes = 0;
 
 // dynamic LDS: NSTAGE K-chunk buffers (the epilogue staging lives inside the just-consumed one)
 size_t conv_lds_bytes(const ConvConfig& k, int bias_n) { return (size_t)k.nstage * (k.bm + k.bn) * 128 + (k.bias_lds ? (size_t)bias_n * 4 : 0); }
-bool g_attr_set[kNumConfigs][4];
-struct OccEntry { size_t lds; int blocks; };
-OccEntry g_occ[kNumConfigs][4][8];   // resident blocks per CU by dynamic-LDS size (a handful of sizes per kernel)
-int g_num_cus = 0;
 
 }  // namespace
 
 // one index space for tuning: [0, kNumConfigs) = implicit-GEMM tiles, then the halo-reuse 3x3 kernel's tiles
-unsigned long long* aq_stamp_buffer(size_t* bytes) { if (bytes) *bytes = g_stamp_bytes; return g_stamp_buf; }
-const char* aq_zero_page() {
-    static void* pages[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    if (!pages[dev]) {
-        void* q = nullptr;
-        if (hipMalloc(&q, 256) != hipSuccess || hipMemset(q, 0, 256) != hipSuccess) return nullptr;
-        pages[dev] = q;
-    }
-    return (const char*)pages[dev];
-}
-extern "C" int aq_debug_conv_stamp(void* buf_dev, size_t bytes) {
-    g_stamp_buf = (unsigned long long*)buf_dev;
-    g_stamp_bytes = buf_dev ? bytes : 0;
-    return AQ_OK;
-}
-
 extern "C" int aq_conv_num_configs(void) { return kNumConfigs + aq_conv_halo_num_configs(); }
 
 extern "C" int aq_conv_config_tiles(int cfg, int* bm, int* bn) {
@@ -662,45 +638,26 @@ int aq_launch_conv(const ConvParams& p_in, int precision, int out_f32, int cfg_i
     }
     const size_t lds = conv_lds_bytes(k, variant == 3 ? 2 * p.bias_n : p.bias_n);
     if (lds > 160 * 1024) { aq_set_error("conv: config %d needs %zu B of LDS", cfg, lds); return AQ_ERR_INVALID; }
-    if (!g_attr_set[cfg][variant]) {
-        AQ_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        g_attr_set[cfg][variant] = true;
-    }
     const long long ntiles = (long long)p.n_tiles_m * p.n_tiles_n;
     if (ntiles <= 0 || ntiles > 0x7fffffffLL) { aq_set_error("conv: bad tile count %lld", ntiles); return AQ_ERR_INVALID; }
     p.magic_ntm = (unsigned)(0x100000000ull / (unsigned)p.n_tiles_m) + 1u;
     if (ntiles * p.n_tiles_m >= (1LL << 31)) { aq_set_error("conv: too many tiles"); return AQ_ERR_INVALID; }
-    // persistent grid: as many workgroups as stay resident (occupancy query once per kernel), capped by the tile count
-    if (g_num_cus == 0) {
-        int dev = 0, cus = 256;
-        AQ_CHECK_HIP(hipGetDevice(&dev));
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_num_cus = cus;
-    }
-    int blocks = 0;
-    OccEntry* occ = g_occ[cfg][variant];
-    for (int i = 0; i < 8; ++i) {
-        if (occ[i].blocks && occ[i].lds == lds) { blocks = occ[i].blocks; break; }
-        if (!occ[i].blocks || i == 7) {
-            int nb = 0;
-            AQ_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)fn, k.threads, lds));
-            occ[i].lds = lds; occ[i].blocks = blocks = nb > 0 ? nb : 1;
-            break;
-        }
-    }
-    long long grid = (long long)g_num_cus * blocks;
+    // persistent grid: as many workgroups as stay resident, capped by the tile count
+    int cus = 0, blocks = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
+    AQ_CHECK_HIP(aq_kernel_blocks((const void*)fn, k.threads, lds, 160 * 1024, &blocks));
+    long long grid = (long long)cus * blocks;
     if (grid > ntiles) grid = ntiles;
     if (one_tile_per_wg) grid = ntiles;     // hardware dispatch order instead of the static persistent split
-    if (g_stamp_buf && variant == 0) {
-        for (const StampedKernel& sk : kStamped)
-            if (sk.cfg == cfg && (size_t)grid * (k.threads / 64) * 64 <= g_stamp_bytes) {
-                AQ_CHECK_HIP(hipFuncSetAttribute((const void*)sk.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                p.debug = g_stamp_buf;
-                hipLaunchKernelGGL(sk.fn, dim3((unsigned)grid), dim3(k.threads), lds, stream, p);
-                AQ_CHECK_HIP(hipGetLastError());
-                return AQ_OK;
-            }
-    }
+    unsigned long long* sbuf = variant == 0 ? aq_stamp_target((size_t)grid * (k.threads / 64) * 64) : nullptr;
+    for (const StampedKernel& sk : kStamped)
+        if (sbuf && sk.cfg == cfg) {
+            AQ_CHECK_HIP(aq_kernel_lds((const void*)sk.fn, 160 * 1024));
+            p.debug = sbuf;
+            hipLaunchKernelGGL(sk.fn, dim3((unsigned)grid), dim3(k.threads), lds, stream, p);
+            AQ_CHECK_HIP(hipGetLastError());
+            return AQ_OK;
+        }
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(k.threads), lds, stream, p);
     AQ_CHECK_HIP(hipGetLastError());
     return AQ_OK;

@@ -541,19 +541,12 @@ extern "C" int aq_nms_opts(const float* rows_dev, int rows_per_tile, int B, int 
     s += align_up((size_t)B * N * sizeof(float4), 256);
     p.mask = (unsigned long long*)s;
     p.dets = dets_dev; p.counts = counts_dev;
-    {   // diagnostics: an armed stamp buffer (aq_debug_conv_stamp) receives 8 phase timestamps per tile
-        size_t sbytes = 0;
-        unsigned long long* sbuf = aq_stamp_buffer(&sbytes);
-        p.dbg = (sbuf && (size_t)B * 64 <= sbytes) ? sbuf : nullptr;
-    }
-    static bool attr_set[2] = {false, false};
+    // diagnostics: an armed stamp buffer (aq_debug_conv_stamp) receives 8 phase timestamps per tile
+    p.dbg = aq_stamp_target((size_t)B * 64);
     const bool big = nms_fast(N) == kFastBig;
     auto fn = big ? nms_kernel<kFastBig> : nms_kernel<kFast>;
     const int lds = nms_lds(big ? kFastBig : kFast);
-    if (!attr_set[big]) {
-        AQ_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set[big] = true;
-    }
+    AQ_CHECK_HIP(aq_kernel_lds((const void*)fn, lds));
     hipLaunchKernelGGL(fn, dim3(B), dim3(kNmsThreads), lds, (hipStream_t)stream, p);
     AQ_CHECK_HIP(hipGetLastError());
     return AQ_OK;

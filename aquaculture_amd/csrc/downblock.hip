@@ -417,7 +417,6 @@ __global__ __launch_bounds__(kNW * 64) void downblock_kernel(const DownParams p)
     }
 }
 
-int g_down_cus = 0;
 int down_common(DownParams& p, const void* in_dev, int in_ld, int in_choff, int cin, void* out_dev, int out_ld, int out_choff, int cout,
                 const void* packed_w_dev, const float* bias_dev, int B, int H, int W, int th) {
     AQ_REQUIRE(in_dev && out_dev && packed_w_dev && bias_dev, "downblock: null pointer");
@@ -434,25 +433,17 @@ int down_common(DownParams& p, const void* in_dev, int in_ld, int in_choff, int 
     p.n_tiles = B * p.tiles_x * p.tiles_y;
     p.zero = aq_zero_page();
     AQ_REQUIRE(p.zero, "downblock: zero page allocation failed");
-    if (g_down_cus == 0) {
-        int dev = 0, cus = 256;
-        AQ_CHECK_HIP(hipGetDevice(&dev));
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_down_cus = cus;
-    }
     return AQ_OK;
 }
 
 template <int CIN, int CMID, bool FUSE, int KT, bool STEM = false>
 int launch_down(const DownParams& p, hipStream_t stream) {
     using G = DownGeom<CIN, CMID, FUSE, KT, STEM>;
-    static bool attr = false;
     auto fn = downblock_kernel<CIN, CMID, FUSE, KT, STEM>;
-    if (!attr) {
-        AQ_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        attr = true;
-    }
-    long long grid = g_down_cus;                             // > 150 KB of LDS: one persistent workgroup per CU
+    int cus = 0;
+    AQ_CHECK_HIP(aq_kernel_lds((const void*)fn, G::LDS));
+    AQ_CHECK_HIP(aq_cus(&cus));
+    long long grid = cus;                                    // > 150 KB of LDS: one persistent workgroup per CU
     if (grid > p.n_tiles) grid = p.n_tiles;
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kNW * 64), G::LDS, stream, p);
     AQ_CHECK_HIP(hipGetLastError());

@@ -755,9 +755,8 @@ extern "C" int aq_engine_create(const aq_model_desc* d, int device, aq_engine** 
     AQ_REQUIRE(d->nl == 3 && d->na >= 1 && d->na <= 8 && d->nc >= 1, "engine_create: unsupported head nl=%d na=%d nc=%d", d->nl, d->na, d->nc);
     AQ_REQUIRE(d->precision == AQ_BF16 || d->precision == AQ_FP32 || d->precision == AQ_BF16_W8 || d->precision == AQ_F16X3,
                "engine_create: bad precision %d", d->precision);
-    {   // One device per process (one process per GPU is how every entry point of this package runs): the kernels' launch-attribute,
-        // CU-count and occupancy caches in conv_igemm / conv_halo / downblock / conv1x1_direct / detect_nms are process-global, and
-        // hipFuncSetAttribute is per device -- a second device would skip it and fail to launch anything above 64 KiB of LDS.
+    {   // One device per process (one process per GPU is how every entry point of this package runs).  The launch-time state of the
+        // kernels is kept per device (launch_state.hip), but no test runs two devices in one process yet, so a second one is refused.
         static std::atomic<int> first_device{-1};
         int expected = -1;
         if (!first_device.compare_exchange_strong(expected, device))

@@ -171,7 +171,6 @@ const HeadKernel kHead[] = {
     {20, 4, head_decode_kernel<5, 4>, head_decode_kernel<5, 4, 4, true>},    {24, 4, head_decode_kernel<6, 4>, head_decode_kernel<6, 4, 4, true>},
     {32, 4, head_decode_kernel<8, 4>, head_decode_kernel<8, 4, 4, true>},    {40, 4, head_decode_kernel<10, 4, 2>, head_decode_kernel<10, 4, 2, true>},
 };
-int g_head_cus[64];
 
 }  // namespace
 
@@ -215,14 +214,8 @@ int head_decode_launch(const void* in_dev, int in_ld, int in_choff, int cin, con
     AQ_REQUIRE(aq_head_decode_supported(cin, na, nc), "head_decode: unsupported cin=%d na=%d nc=%d", cin, na, nc);
     AQ_REQUIRE(B > 0 && ny > 0 && nx > 0 && (long long)B * ny * nx < (1LL << 30) && in_ld % 8 == 0 && in_choff % 8 == 0 && in_choff + cin <= in_ld && cand_cap > 0,
                "head_decode: bad geometry");
-    int dev = 0;
-    AQ_CHECK_HIP(hipGetDevice(&dev));
-    AQ_REQUIRE(dev >= 0 && dev < 64, "head_decode: device ordinal %d", dev);
-    if (g_head_cus[dev] == 0) {
-        int cus = 256;
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_head_cus[dev] = cus;
-    }
+    int cus = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
     HeadDecParams p{};
     p.in = (const char*)in_dev + (size_t)in_choff * 2; p.in_ld_b = in_ld * 2;
     p.w = (const char*)packed_dev;
@@ -235,7 +228,7 @@ int head_decode_launch(const void* in_dev, int in_ld, int in_choff, int cin, con
         if (c.ks == cin / 32) k = &c;
     const int pxi = 64 / k->split;
     const int nit = (p.npix + pxi - 1) / pxi;
-    long long grid = (long long)g_head_cus[dev] * 4;                      // persistent (four workgroups per CU): the weights are loaded once per wave
+    long long grid = (long long)cus * 4;                                 // persistent (four workgroups per CU): the weights are loaded once per wave
     if (grid > nit) grid = nit;
     hipLaunchKernelGGL(aug ? k->fn_aug : k->fn, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
     AQ_CHECK_HIP(hipGetLastError());

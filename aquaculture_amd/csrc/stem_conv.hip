@@ -300,9 +300,6 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const ConvParams p, c
     }
 }
 
-int g_stem_occ[4][kMaxMB + 1];                // resident workgroups per CU, 0 = not queried yet ([F32 + 2 * DMA])
-int g_stem_cus = 0;
-
 size_t stem_packed_bytes(bool f32, int mb) {
     return f32 ? (size_t)StemGeom<true>::KS * mb * 64 * 4 : (size_t)StemGeom<false>::KS * mb * 64 * 16;
 }
@@ -311,13 +308,10 @@ template <bool F32, int MB, bool DMA = false>
 int launch_stem(const ConvParams& p, const uint8_t* tiles, int tiles_x, int tiles_y, hipStream_t stream) {
     auto fn = stem_conv_kernel<F32, MB, DMA>;
     constexpr size_t lds = StemGeom<F32>::LDS;
-    if (!g_stem_occ[F32 + 2 * DMA][MB]) {
-        AQ_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int occ = 0;
-        AQ_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)fn, 256, lds));
-        g_stem_occ[F32 + 2 * DMA][MB] = occ > 0 ? occ : 1;
-    }
-    long long grid = (long long)g_stem_cus * g_stem_occ[F32 + 2 * DMA][MB];
+    int cus = 0, occ = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
+    AQ_CHECK_HIP(aq_kernel_blocks((const void*)fn, 256, lds, (int)lds, &occ));
+    long long grid = (long long)cus * occ;
     if (grid > p.n_tiles_n) grid = p.n_tiles_n;
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(256), lds, stream, p, tiles, tiles_x, tiles_y);
     AQ_CHECK_HIP(hipGetLastError());
@@ -449,19 +443,14 @@ __global__ __launch_bounds__(256, 2) void stem_conv_scaled_kernel(const ConvPara
     }
 }
 
-int g_stem_scaled_occ[2][kMaxMB + 1];
-
 template <bool F32, int MB>
 int launch_stem_scaled(const ConvParams& p, const uint8_t* tiles, const StemAugSrc& src, int tiles_x, int tiles_y, hipStream_t stream) {
     auto fn = stem_conv_scaled_kernel<F32, MB>;
     constexpr size_t lds = StemGeom<F32>::PATCHB;
-    if (!g_stem_scaled_occ[F32][MB]) {
-        AQ_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int occ = 0;
-        AQ_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)fn, 256, lds));
-        g_stem_scaled_occ[F32][MB] = occ > 0 ? occ : 1;
-    }
-    long long grid = (long long)g_stem_cus * g_stem_scaled_occ[F32][MB];
+    int cus = 0, occ = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
+    AQ_CHECK_HIP(aq_kernel_blocks((const void*)fn, 256, lds, (int)lds, &occ));
+    long long grid = (long long)cus * occ;
     if (grid > p.n_tiles_n) grid = p.n_tiles_n;
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(256), lds, stream, p, tiles, src, tiles_x, tiles_y);
     AQ_CHECK_HIP(hipGetLastError());
@@ -521,12 +510,6 @@ extern "C" int aq_stem_conv(const uint8_t* tiles_dev, void* out_dev, int out_ld,
     AQ_REQUIRE((long long)B * tiles_x * tiles_y < (1LL << 31), "stem_conv: batch too large");
     p.n_tiles_n = B * tiles_y * tiles_x;
     p.n_tiles_m = 1;
-    if (g_stem_cus == 0) {
-        int dev = 0, cus = 256;
-        AQ_CHECK_HIP(hipGetDevice(&dev));
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_stem_cus = cus;
-    }
     const hipStream_t st = (hipStream_t)stream;
     const int mb = (cout + 15) / 16;
     // DMA variant: bf16, every image row a whole number of dwords from a 4-byte aligned base (a dword is inside or outside the row)
@@ -570,12 +553,6 @@ extern "C" int aq_stem_conv_scaled(const uint8_t* tiles_dev, int H0, int W0, con
     AQ_REQUIRE((long long)B * tiles_x * tiles_y < (1LL << 31), "stem_conv_scaled: batch too large");
     p.n_tiles_n = B * tiles_y * tiles_x;
     p.n_tiles_m = 1;
-    if (g_stem_cus == 0) {
-        int dev = 0, cus = 256;
-        AQ_CHECK_HIP(hipGetDevice(&dev));
-        AQ_CHECK_HIP(aq_query_cus(&cus, dev));
-        g_stem_cus = cus;
-    }
     const StemAugSrc src{ytab_dev, xtab_dev, H0, W0, h, w};
     const hipStream_t st = (hipStream_t)stream;
     switch ((cout + 15) / 16) {
