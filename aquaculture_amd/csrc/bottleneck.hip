@@ -710,7 +710,96 @@ void btl96_asm_pack(const float* w1, const float* w2, bf16_t* dst) {
     }
 }
 
+// ---- C = 48 with the C3 tail (gen_bottleneck_asm.py TAIL): the same kernel, and in its epilogue the C3 block's cv3 1x1
+// over [y | cv2 out] -- y never leaves the CU, the block's output is written instead.  Two more arguments: the cv2 half of the concat. ----
+struct BtlTailArgs {               // must match ARG / ARG_TAIL in gen_bottleneck_asm.py
+    BtlAsmArgs a;
+    const char* cat;
+    int cat_ld_b, pad2;
+};
+static_assert(sizeof(BtlTailArgs) == 112, "kernel argument block");
+constexpr size_t kBtlTailWBytes = kBtlAsmWBytes + (size_t)18 * 1024;     // the C = 48 image, then cv3's 18 A fragments
+
+// cv3's A fragments [M block 6][k-step 3], 64 lanes x 8 bf16: lane (r = lane & 15, g = lane >> 4) of M block m holds output channel 16 m + r,
+// input channels 32 s + 8 g .. + 7 -- conv1x1_direct's k-step order, so that the fused form rounds exactly as the two launches.
+void btl_tail_pack_w3(const float* w3, bf16_t* dst) {
+    for (int m = 0; m < 6; ++m)
+        for (int s = 0; s < 3; ++s)
+            for (int lane = 0; lane < 64; ++lane, dst += 8) {
+                const int co = 16 * m + (lane & 15), c0 = 32 * s + 8 * (lane >> 4);
+                for (int e = 0; e < 8; ++e) dst[e] = aq_f2bf(w3[(size_t)co * 96 + c0 + e]);
+            }
+}
+
 }  // namespace
+
+// AQ_C3TAIL=0 (the engine's A/B switch) is read by the engine; this query follows btl_asm_fits, plus the concat's 32-bit row offsets.
+extern "C" int aq_bottleneck_c3tail_supported(int B, int H, int W, int in_ld, int cat_ld, int out_ld) {
+    if (!btl_asm_fits(48, B, H, W, in_ld, out_ld)) return 0;
+    return (long long)B * H * W * cat_ld * 2 < (1LL << 31) && in_ld % 8 == 0 && cat_ld % 8 == 0 && out_ld % 8 == 0;
+}
+
+// w1 (48,1,1,48), w2 (48,3,3,48), w3 (96,1,1,96) fp32 KRSC -> the tail kernel's weight image (bias: b1 | b2 | b3 as 192 floats, the caller's).
+extern "C" int aq_pack_bottleneck_c3tail_weights(const float* w1_host, const float* w2_host, const float* w3_host, void* packed_dev, size_t* bytes,
+                                                  void* stream) {
+    AQ_REQUIRE(w1_host && w2_host && w3_host && bytes, "pack_bottleneck_c3tail: null pointer");
+    *bytes = kBtlTailWBytes;
+    if (!packed_dev) return AQ_OK;
+    bf16_t* host = (bf16_t*)calloc(1, *bytes);
+    AQ_REQUIRE(host, "pack_bottleneck_c3tail: out of host memory");
+    btl_asm_pack(w1_host, w2_host, host);
+    btl_tail_pack_w3(w3_host, (bf16_t*)((char*)host + kBtlAsmWBytes));
+    hipError_t e = hipMemcpyAsync(packed_dev, host, *bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    free(host);
+    AQ_CHECK_HIP(e);
+    return AQ_OK;
+}
+
+// One C3 block's last Bottleneck (C = 48) and its cv3: out = SiLU(W3 [Bottleneck(x) | cat] + b3), 96 channels.  x: [B][H][W][in_ld] at in_choff;
+// cat: cv2's 48 channels at cat_choff; out: 96 channels at out_choff.  Returns AQ_ERR_INVALID ("unsupported", no launch) where
+// aq_bottleneck_c3tail_supported says no: the caller then runs aq_bottleneck and the 1x1.
+extern "C" int aq_bottleneck_c3tail(const void* in_dev, int in_ld, int in_choff, const void* cat_dev, int cat_ld, int cat_choff, void* out_dev,
+                                    int out_ld, int out_choff, const void* packed_w_dev, const float* bias_dev, int B, int H, int W, int shortcut,
+                                    void* stream) {
+    AQ_REQUIRE(in_dev && cat_dev && out_dev && packed_w_dev && bias_dev, "bottleneck_c3tail: null pointer");
+    AQ_REQUIRE(B > 0 && H > 0 && W > 0, "bottleneck_c3tail: empty input");
+    AQ_REQUIRE(in_choff % 8 == 0 && cat_choff % 8 == 0 && out_choff % 8 == 0 && in_choff + 48 <= in_ld && cat_choff + 48 <= cat_ld &&
+                   out_choff + 96 <= out_ld, "bottleneck_c3tail: channel slices must be 8-aligned and inside their rows");
+    if (!aq_bottleneck_c3tail_supported(B, H, W, in_ld, cat_ld, out_ld)) {
+        aq_set_error("bottleneck_c3tail: unsupported geometry %d x %d x %d (or AQ_BTL_ASM=0)", B, H, W);
+        return AQ_ERR_INVALID;
+    }
+    {   // the kernel reads halos of x that other workgroups see, and cat pixels beside the ones it writes: refuse aliasing buffers
+        const size_t np = (size_t)B * H * W;      // (first to last byte of each slice)
+        const char* i0 = (const char*)in_dev + (size_t)in_choff * 2; const char* i1 = i0 + (np - 1) * in_ld * 2 + 96;
+        const char* c0 = (const char*)cat_dev + (size_t)cat_choff * 2; const char* c1 = c0 + (np - 1) * cat_ld * 2 + 96;
+        const char* o0 = (const char*)out_dev + (size_t)out_choff * 2; const char* o1 = o0 + (np - 1) * out_ld * 2 + 192;
+        AQ_REQUIRE((o1 <= i0 || i1 <= o0) && (o1 <= c0 || c1 <= o0), "bottleneck_c3tail: output overlaps an input");
+    }
+    int cus = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
+    BtlTailArgs t{};
+    BtlAsmArgs& a = t.a;
+    a.in = (const char*)in_dev + (size_t)in_choff * 2; a.out = (char*)out_dev + (size_t)out_choff * 2;
+    a.w = (const char*)packed_w_dev; a.bias = bias_dev;
+    a.in_ld_b = in_ld * 2; a.out_ld_b = out_ld * 2; a.B = B; a.H = H; a.W = W;
+    a.tiles_x = (W + 15) / 16;
+    a.tpi = a.tiles_x * ((H + 15) / 16);
+    a.ntiles = a.tpi * B;
+    a.shortcut = shortcut;
+    long long grid = cus;
+    if (grid > a.ntiles) grid = a.ntiles;
+    a.G = (int)grid;
+    a.magic_tpi = (unsigned)((1ULL << 32) / (unsigned)a.tpi + 1);
+    a.magic_tx = (unsigned)((1ULL << 32) / (unsigned)a.tiles_x + 1);
+    a.in_bytes = (unsigned)(((long long)B * H * W - 1) * a.in_ld_b + 96);
+    t.cat = (const char*)cat_dev + (size_t)cat_choff * 2; t.cat_ld_b = cat_ld * 2;
+    hipFunction_t fn = nullptr;
+    AQ_CHECK_HIP(aq_asm_fn(kBtlAsmCode, "bottleneck_asm_c48_tail", &fn, false));
+    AQ_CHECK_HIP(aq_asm_launch(fn, (unsigned)grid, 512, &t, sizeof t, (hipStream_t)stream));
+    return AQ_OK;
+}
 
 // Packs the fused fp32 weights of one Bottleneck -- w1 KRSC (C,1,1,C), w2 KRSC (C,3,3,C) -- into the A-fragment image the
 // kernel loads once per workgroup: [channel group][k-step][M block][lane] x 8 bf16.  Lane (m = lane & 15, g = lane >> 4) of

@@ -75,6 +75,9 @@ struct PackedW {
     float act_scale = 0.0f;     // consumer: the scale of its input tensor; producer: of its output tensor
     int f8_consumer = -1;       // producer: the op that reads its codes (the pair runs in fp8 only when that op's geometry fits)
     std::vector<float> w_host, b_host;   // layers with an fp8 form keep their fused fp32 weights: the fp8 packer needs the activation scale, known later
+    // a C3 block's last Bottleneck (C = 48) whose cv3 1x1 is the next op: the aq_bottleneck_c3tail image and b1 | b2 | b3 (AQ_C3TAIL)
+    void* w_tail = nullptr;
+    float* b_tail = nullptr;
 };
 
 // Host-side packing: KRSC fp32 -> [cout_rows][kgroups_pad*16 B] of bf16 / fp32, zero padded.
@@ -421,6 +424,24 @@ bool heads_fused(const aq_engine* e) {
     return n_heads == 3;
 }
 
+// Does Bottleneck op oi run together with the next op, its C3 block's cv3, as ONE aq_bottleneck_c3tail launch?  Only where the two-launch form
+// runs cv3 on the direct 1x1 kernel -- the fused kernel reproduces that kernel's rounding, so the outputs are the same bits -- and only when
+// the range being run holds both ops (aq_engine_run_ops stepping one op at a time runs, and checks, the two-launch form).
+bool c3tail_active(aq_engine* e, int oi, int last, int B) {
+    if (!e->packed[oi].w_tail || oi + 1 >= last || e->calib_amax || e->tuning) return false;
+    const int ci = oi + 1;
+    const PackedW& pc = e->packed[ci];
+    if (pc.direct_cfg != AQ_CONV_CFG_DIRECT1X1 || (pc.f8_consumer >= 0 && f8_pair_active(e, pc.f8_consumer, B))) return false;
+    const aq_engine::Tuned* tt = tuned_for(e);
+    const int cfg = e->conv_cfg[ci] >= 0 ? e->conv_cfg[ci] : tt ? tt->cfg[ci] : -1;
+    if (cfg != AQ_CONV_CFG_DIRECT1X1) return false;
+    const aq_op_desc& b = e->ops[oi];
+    const aq_op_desc& c = e->ops[ci];
+    const TensorPlace& pl = e->place[b.src.tensor];
+    return aq_bottleneck_c3tail_supported(B, pl.h, pl.w, e->tensors[b.src.tensor].channels, e->tensors[c.src.tensor].channels,
+                                          e->tensors[c.dst.tensor].channels) != 0;
+}
+
 // One pass of an augmented call (run_augment): its geometry, the u8 tiles' size and the pass's tap tables in the workspace.
 struct AugRun {
     int pass;
@@ -481,6 +502,7 @@ int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, 
             heads_started = true;
             ++heads_done;
         }
+    int tail_conv = -1;                                  // a cv3 op the Bottleneck op before it has computed (aq_bottleneck_c3tail)
     for (int oi = first; oi < last; ++oi) {
         const aq_op_desc& op = e->ops[oi];
         if (ev) AQ_CHECK_HIP(hipEventRecord(ev[oi], stream));
@@ -500,6 +522,11 @@ int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, 
                 rc = aq_preprocess_s2d(tiles, tptr(e, ws, tiles, op.dst.tensor), B, H, W, prec, stream);
             break;
         case AQ_OP_CONV:
+            if (oi == tail_conv) {
+                // computed inside the Bottleneck launch; it stands for the direct 1x1 launch it replaces, bit for bit
+                note_launch(e, oi, AQ_FAM_DIRECT1X1, AQ_CONV_CFG_DIRECT1X1);
+                break;
+            }
             if (ar && op.level >= 0 && !((ar->ps->level_mask >> op.level) & 1)) {
                 note_launch(e, oi, AQ_FAM_NONE);         // a level _clip_augmented drops: neither its head conv nor its decode runs
                 break;
@@ -554,6 +581,16 @@ int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, 
         case AQ_OP_BOTTLENECK: {
             note_launch(e, oi, AQ_FAM_BOTTLENECK);
             const TensorPlace& pl = e->place[op.src.tensor];
+            if (c3tail_active(e, oi, last, B)) {
+                // C3 tail: this Bottleneck and cv3 (the next op) as one launch; the Bottleneck's output is not written
+                const aq_op_desc& c = e->ops[oi + 1];
+                rc = aq_bottleneck_c3tail(tptr(e, ws, tiles, op.src.tensor), e->tensors[op.src.tensor].channels, op.src.ch_off,
+                                          tptr(e, ws, tiles, c.src.tensor), e->tensors[c.src.tensor].channels, op.dst.channels,
+                                          tptr(e, ws, tiles, c.dst.tensor), e->tensors[c.dst.tensor].channels, c.dst.ch_off,
+                                          e->packed[oi].w_tail, e->packed[oi].b_tail, B, pl.h, pl.w, op.res.tensor >= 0, stream);
+                tail_conv = oi + 1;
+                break;
+            }
             rc = aq_bottleneck(tptr(e, ws, tiles, op.src.tensor), e->tensors[op.src.tensor].channels, op.src.ch_off,
                                tptr(e, ws, tiles, op.dst.tensor), e->tensors[op.dst.tensor].channels, op.dst.ch_off,
                                op.src.channels, e->packed[oi].w, e->packed[oi].bias, B, pl.h, pl.w, op.res.tensor >= 0, stream);
@@ -786,6 +823,38 @@ extern "C" int aq_engine_create(const aq_model_desc* d, int device, aq_engine** 
         aq_set_error("engine_create: zero page allocation failed");
         return fail(AQ_ERR_NOMEM);
     }
+    // C3 tails (aq_bottleneck_c3tail): a C = 48 Bottleneck writing the first half of a 96-channel buffer, immediately followed by a 1x1
+    // (96 -> 96, SiLU) over exactly that buffer, and no later op reading the Bottleneck's output -- packed while both ops' host weights are here
+    const char* use_tail = getenv("AQ_C3TAIL");          // A/B switch: AQ_C3TAIL=0 keeps the two launches
+    for (size_t oi = 0; d->precision == AQ_BF16 && !(use_tail && *use_tail == '0') && oi + 1 < e->ops.size(); ++oi) {
+        const aq_op_desc& b = e->ops[oi];
+        const aq_op_desc& c = e->ops[oi + 1];
+        if (b.kind != AQ_OP_BOTTLENECK || c.kind != AQ_OP_CONV || !b.weight || !b.bias || !c.weight || !c.bias) continue;
+        if (b.src.channels != 48 || b.dst.channels != 48 || b.k != 3 || b.dst.tensor < 0 || b.dst.tensor >= d->n_tensors || b.dst.ch_off != 0 ||
+            e->tensors[b.dst.tensor].channels != 96 || b.src.tensor == b.dst.tensor)
+            continue;
+        if (c.k != 1 || c.stride != 1 || c.act != 1 || c.res.tensor >= 0 || c.level >= 0 || c.src.tensor != b.dst.tensor || c.src.ch_off != 0 ||
+            c.src.channels != 96 || c.dst.channels != 96 || c.dst.tensor < 0 || c.dst.tensor >= d->n_tensors || c.dst.tensor == c.src.tensor ||
+            c.dst.tensor == b.src.tensor || c.dst.ch_off % 8 || e->tensors[c.dst.tensor].channels % 8 || e->tensors[c.dst.tensor].dtype != AQ_T_ACT)
+            continue;
+        bool read_later = false;
+        for (size_t oj = oi + 2; oj < e->ops.size(); ++oj)
+            for (const aq_slice* s : {&e->ops[oj].src, &e->ops[oj].res})
+                if (s->tensor == b.dst.tensor && s->ch_off < b.dst.ch_off + b.dst.channels && b.dst.ch_off < s->ch_off + s->channels) read_later = true;
+        if (read_later) continue;
+        PackedW& pw = e->packed[oi];
+        size_t nb = 0;
+        float bias[192];
+        memcpy(bias, b.bias, sizeof(float) * 96);
+        memcpy(bias + 96, c.bias, sizeof(float) * 96);
+        if (aq_pack_bottleneck_c3tail_weights(b.weight, b.weight + (size_t)48 * 48, c.weight, nullptr, &nb, nullptr) != AQ_OK ||
+            hipMalloc(&pw.w_tail, nb) != hipSuccess || hipMalloc((void**)&pw.b_tail, sizeof bias) != hipSuccess ||
+            aq_pack_bottleneck_c3tail_weights(b.weight, b.weight + (size_t)48 * 48, c.weight, pw.w_tail, &nb, nullptr) != AQ_OK ||
+            hipMemcpy(pw.b_tail, bias, sizeof bias, hipMemcpyHostToDevice) != hipSuccess) {
+            aq_set_error("engine_create: C3 tail weight upload failed (op %zu)", oi);
+            return fail(AQ_ERR_HIP);
+        }
+    }
     for (size_t oi = 0; oi < e->ops.size(); ++oi) {
         aq_op_desc& op = e->ops[oi];
         for (const aq_slice* s : {&op.src, &op.dst}) {
@@ -991,6 +1060,8 @@ extern "C" void aq_engine_destroy(aq_engine* e) {
         if (pw.w_f8) (void)hipFree(pw.w_f8);
         if (pw.sb_f8) (void)hipFree(pw.sb_f8);
         if (pw.sb_pl8) (void)hipFree(pw.sb_pl8);
+        if (pw.w_tail) (void)hipFree(pw.w_tail);
+        if (pw.b_tail) (void)hipFree(pw.b_tail);
         if (pw.bias) (void)hipFree(pw.bias);
     }
     if (e->zero_page) (void)hipFree(e->zero_page);

@@ -59,6 +59,14 @@ ARG = dict(inp=0, out=8, w=16, bias=24, in_ld=32, out_ld=36, B=40, H=44, W=48, t
            magic_tpi=72, magic_tx=76, in_bytes=80, pad=84, debug=88)
 ARG_BYTES = 96
 
+# TAIL (bottleneck_asm_c48_tail): the C3 block's cv3 1x1 (96 -> 96 + SiLU over [y | cv2 out]) in the epilogue, y never leaves the CU.
+# Its 18 A fragments [M block 6][k-step 3] and b3 live in LDS behind b1 | b2; two more arguments: the cv2 half of the concat buffer.
+BIAS3_OFF = BIAS_OFF + 384       # b1 | b2 | b3 = 192 floats
+W3_OFF = BIAS_OFF + 768
+LDS_BYTES_TAIL = W3_OFF + 18 * 1024
+ARG_TAIL = dict(cat=96, cat_ld=104)
+ARG_BYTES_TAIL = 112
+
 
 class Regs:
     def __init__(self, prefix, limit):
@@ -122,14 +130,19 @@ V.alloc("F", 16, 4)
 V.alloc("P", 28, 4)
 
 
+# the tail kernel has no stamped build: its extra scalars live in the stamp accumulators (the SGPR file is full)
+S_TAIL = dict(cat=(S.names["st_acc"][0], 2), cat_ld=(S.names["st_acc"][0] + 2, 1), crow0=(S.names["st_acc"][0] + 4, 2),
+              crow1=(S.names["st_acc"][0] + 6, 2))
+
+
 def s(name, i=0):
-    b, n = S.names[name]
+    b, n = S.names[name] if name in S.names else S_TAIL[name]
     assert i < n
     return f"s{b + i}"
 
 
 def s2(name, i=0):
-    b, n = S.names[name]
+    b, n = S.names[name] if name in S.names else S_TAIL[name]
     assert i + 1 < n and (b + i) % 2 == 0
     return f"s[{b + i}:{b + i + 1}]"
 
@@ -163,7 +176,7 @@ def acc(j, m):
 out = []
 _uid = [0]
 STAMPED = [False]
-OPT = dict(stagger=True, nosilu=False, nomfma=False, nopk=False, nodma=False, nold=False, nost=False, prio=0, ntst=False, ntld=False)      # experiment switches of a kernel variant (main() sets them per kernel)
+OPT = dict(stagger=True, nosilu=False, nomfma=False, nopk=False, nodma=False, nold=False, nost=False, prio=0, ntst=False, ntld=False, tail=False)      # switches of a kernel variant (main() sets them per kernel)
 PH_PROLOGUE, PH_DMA, PH_B, PH_C_MFMA, PH_C_EPI, PH_BARRIER = range(6)      # (PH_DMA: the vmcnt wait in front of the epilogue)
 
 
@@ -389,6 +402,102 @@ def emit_phase_b_dispatch():
     label(skip)
 
 
+# ---- TAIL: out = SiLU(W3 [y | c] + b3), c = cv2's 48 channels at the same pixels.  Register map of the tail (the 68 registers ACC, F, P
+# are one run R0 .. R67 = ACC .. P + 27; W2 and the address registers are untouched):
+#   B fragments of output row j (K = 96 in three k-steps of 32, each in conv1x1_direct's order: lane group g holds channels 32 s + 8 g .. + 7)
+#     k-step 0 = y 0-31      R[12 j .. 12 j + 3]         (y blocks 0, 1 packed in place by the epilogue above, then two lane swaps)
+#     k-step 1 = y 32-47 | c 0-15   R[24 + 8 j .. + 3]   (y block 2 and c 4 g .. + 3 (8-byte loads), then the same two lane swaps)
+#     k-step 2 = c 16-47     R[28 + 8 j .. + 3]          (16-byte loads of c 16 + 8 g .. + 7: already in place)
+#   cat lane offsets R64, R65 (only until the loads are issued); then, per third of the 96 output channels (M blocks 2 t, 2 t + 1):
+#   accumulators R40 .. R55 (acc3(j, i) = R40 + 4 (2 j + i)), A-fragment ring R56, R60, R64 (from LDS, as phase B reads W1),
+#   b3 R4 .. R11, SiLU temporaries R4 .. R11 + R16 .. R23, store data R16 .. R23, store address R4.
+def tail_r(i):
+    return V.names["ACC"][0] + i
+
+
+def emit_tail_cat_loads():
+    """Issue the cv2 values of both output rows (lanes outside the image keep stale registers: they only feed their own, unstored pixel).
+    Returns the number of vector-memory instructions issued."""
+    R = tail_r
+    tid = V.names["tid"][0]
+    E(f"v_lshrrev_b32 v{R(65)}, 1, v{tid}")
+    E(f"v_and_b32 v{R(65)}, 0x18, v{R(65)}", "8 g")
+    E(f"v_mad_u32_u24 v{R(64)}, {v('l15')}, {s('cat_ld')}, v{R(65)}", "l15 cat_ld + 8 g: c 4 g")
+    E(f"v_add_u32 v{R(65)}, v{R(64)}, v{R(65)}", "+ 8 g more: c 16 + 8 g (at offset 32)")
+    for j in range(2):
+        E(f"s_mov_b64 exec, {s2('mask' + str(j))}")
+        E(f"global_load_dwordx2 v[{R(26 + 8 * j)}:{R(27 + 8 * j)}], v{R(64)}, {s2('crow' + str(j))}")
+        E(f"global_load_dwordx4 v[{R(28 + 8 * j)}:{R(31 + 8 * j)}], v{R(65)}, {s2('crow' + str(j))} offset:32")
+    E("s_mov_b64 exec, -1")
+    return 4
+
+
+def emit_tail_gemm():
+    R = tail_r
+    E("s_waitcnt vmcnt(0)", "the cv2 values")
+    # lane swaps: (block a, block b) of lane groups 0-3 -> channels 8 g .. + 7 of the pair.  permlane32 then permlane16 (rows = lane groups):
+    # a = [a0 a1 b0 b1], b = [a2 a3 b2 b3] -> a = [a0 a2 b0 b2], b = [a1 a3 b1 b3]: lane group g holds (a, b) = channels 8 g .. + 3, + 4 .. + 7
+    pairs = [(R(12 * j + k), R(12 * j + 2 + k)) for j in range(2) for k in range(2)] + [(R(24 + 8 * j + k), R(26 + 8 * j + k)) for j in range(2) for k in range(2)]
+    for op in ("v_permlane32_swap_b32", "v_permlane16_swap_b32"):
+        for a, b in pairs:
+            E(f"{op} v{a}, v{b}")       # (eight instructions apart from the last write of either operand: hz VALU -> permlane, 2 wait states)
+
+    def bfrag(j, k):
+        base = (R(12 * j), R(24 + 8 * j), R(28 + 8 * j))[k]
+        return f"v[{base}:{base + 3}]"
+
+    def acc3(j, i):
+        return f"v[{R(40 + 4 * (2 * j + i))}:{R(43 + 4 * (2 * j + i))}]"
+
+    ring = [R(56), R(60), R(64)]
+    silu_temps = [R(4 + i) for i in range(8)] + [R(16 + i) for i in range(8)]
+    E(f"s_mov_b32 {s('sa')}, 0xffff0000", "lanes with odd g")
+    E(f"s_mov_b32 {s('sa', 1)}, 0xffff0000")
+    E("s_nop 1", "hz: VALU write -> MFMA read")
+    for t in range(3):
+        frags = [(i, k) for i in range(2) for k in range(3)]      # (M block 2 t + i, k-step k)
+
+        def fread(f):
+            i, k = frags[f]
+            r = ring[f % 3]
+            E(f"ds_read_b128 v[{r}:{r + 3}], {v('w1a')} offset:{W3_OFF - W1_OFF + 1024 * (3 * (2 * t + i) + k)}")
+
+        for i in range(2):
+            E(f"ds_read_b128 v[{R(4 + 4 * i)}:{R(7 + 4 * i)}], {v('bb')} offset:{BIAS3_OFF - BIAS_OFF + 64 * (2 * t + i)}", "b3")
+        fread(0)
+        fread(1)
+        for f in range(6):
+            if f + 2 < 6:
+                fread(f + 2)
+            E(f"s_waitcnt lgkmcnt({min(5, f + 2) - f})")
+            i, k = frags[f]
+            for j in range(2):
+                # accumulators from zero, k-steps in order, bias after: conv1x1_direct_kernel's sequence (bit-identical results)
+                E(f"v_mfma_f32_16x16x32_bf16 {acc3(j, i)}, v[{ring[f % 3]}:{ring[f % 3] + 3}], {bfrag(j, k)}, {'0' if k == 0 else acc3(j, i)}")
+        E("s_nop 15", "hz: MFMA result -> VALU read")
+        regs = [R(40 + i) for i in range(16)]
+        for q in range(0, 16, 2):
+            bq = R(4 + 4 * ((q // 4) % 2) + q % 4)
+            E(f"v_pk_add_f32 v[{regs[q]}:{regs[q] + 1}], v[{regs[q]}:{regs[q] + 1}], v[{bq}:{bq + 1}]")
+        emit_silu(regs, silu_temps)
+        for q in range(0, 16, 2):
+            E(f"v_pk_mul_f32 v[{regs[q]}:{regs[q] + 1}], v[{regs[q]}:{regs[q] + 1}], v[{silu_temps[q]}:{silu_temps[q] + 1}]")
+        # bf16, then W16's pairing: v_permlane16_swap gives even-g lanes block 2 t's channels 8 (g / 2) .. + 7 and odd-g lanes block 2 t + 1's,
+        # 16 bytes each, 24 bytes beyond their own 8-byte offset for the odd ones
+        for j in range(2):
+            for q in range(4):
+                E(f"v_cvt_pk_bf16_f32 v{R(16 + 4 * j + q)}, v{regs[8 * j + 2 * q]}, v{regs[8 * j + 2 * q] + 1}")
+        E(f"v_cndmask_b32 v{R(4)}, 0, 24, {s2('sa')}")
+        E(f"v_add_u32 v{R(4)}, v{R(4)}, {v('vout')}")
+        for j in range(2):
+            E(f"v_permlane16_swap_b32 v{R(16 + 4 * j)}, v{R(18 + 4 * j)}")
+            E(f"v_permlane16_swap_b32 v{R(17 + 4 * j)}, v{R(19 + 4 * j)}")
+        for j in range(2):
+            E(f"s_mov_b64 exec, {s2('mask' + str(j))}")
+            E(f"global_store_dwordx4 v{R(4)}, v[{R(16 + 4 * j)}:{R(19 + 4 * j)}], {s2('orow' + str(j))} offset:{64 * t}")
+        E("s_mov_b64 exec, -1")
+
+
 def emit_phase_c(dma_inside):
     """y = (x +) SiLU(W2 (*) t + b2) for the wave's two output rows of stage C's tile.  dma_inside (waves 0-3, whose interval starts with
     this phase): the next x patch's LDS-DMA is issued BEHIND the shortcut loads, so that the wait in front of the epilogue covers the
@@ -419,7 +528,7 @@ def emit_phase_c(dma_inside):
     E(f"s_add_u32 {s('tmp1')}, {s('tmp1')}, {s('tmp0')}")
     E(f"s_mul_i32 {s('tmp1')}, {s('tmp1')}, {s('W')}")
     E(f"s_add_u32 {s('tmp1')}, {s('tmp1')}, {s('c_x0')}", "pixel index of (row 0, x0)")
-    for nm, ld, base in (("orow", "out_ld", "out"), ("irow", "in_ld", "inp")):
+    for nm, ld, base in (("orow", "out_ld", "out"), ("irow", "in_ld", "inp")) + ((("crow", "cat_ld", "cat"),) if OPT["tail"] else ()):
         E(f"s_mul_i32 {s('tmp2')}, {s('tmp1')}, {s(ld)}")
         E(f"s_mul_hi_u32 {s('tmp3')}, {s('tmp1')}, {s(ld)}")
         E(f"s_add_u32 {s(nm + '0')}, {s(base)}, {s('tmp2')}")
@@ -480,17 +589,20 @@ def emit_phase_c(dma_inside):
         E("s_setprio 0")
     stamp(PH_C_MFMA)
     E("s_nop 15", "hz: MFMA result -> VALU read")
+    ncat = 0
+    if OPT["tail"]:
+        ncat = emit_tail_cat_loads()
     if dma_inside:
         w0, wd = uid("w0"), uid("wd")
         E(f"s_cmp_eq_u32 {s('d_ok')}, 0")
         E(f"s_cbranch_scc1 {w0}")
-        E("s_waitcnt vmcnt(4)", "shortcut values (the four LDS-DMA instructions behind them stay in flight)")
+        E(f"s_waitcnt vmcnt({4 + ncat})", "shortcut values (the four LDS-DMA instructions behind them stay in flight)")
         E(f"s_branch {wd}")
         label(w0)
-        E("s_waitcnt vmcnt(0)")
+        E(f"s_waitcnt vmcnt({ncat})")
         label(wd)
     else:
-        E("s_waitcnt vmcnt(0)", "shortcut values (and, vmcnt being in order, this interval's LDS-DMA and the previous tile's stores)")
+        E(f"s_waitcnt vmcnt({ncat})", "shortcut values (and, vmcnt being in order, this interval's LDS-DMA and the previous tile's stores)")
     stamp(PH_DMA)
     # ---- epilogue, one output row (12 accumulator registers) at a time: SiLU, shortcut, bf16, store.  Two copies behind ONE branch. ----
     temps = [P0 + 12 + i for i in range(12)]
@@ -550,6 +662,13 @@ def emit_phase_c(dma_inside):
                     E(f"global_store_dwordx4 v{temps[7]}, v[{A0}:{A0 + 3}], {s2('orow0')} offset:64")
                     E("s_mov_b64 exec, -1")
                 continue
+            if OPT["tail"]:
+                # y rounded to bf16 as the stored output would be, kept for the tail's B fragments: blocks 0, 1 packed in place into
+                # ACC + 12 j .. + 3 (register k is read by the conversion that writes register k / 2), block 2 into F + 8 j, + 1
+                for k in range(6):
+                    d = A0 + 12 * j + k if k < 4 else F0 + 8 * j + k - 4
+                    E(f"v_cvt_pk_bf16_f32 v{d}, v{regs[2 * k]}, v{regs[2 * k] + 1}")
+                continue
             for k in range(6):
                 E(f"v_cvt_pk_bf16_f32 v{temps[k]}, v{regs[2 * k]}, v{regs[2 * k] + 1}")
             E(f"s_mov_b64 exec, {s2('mask' + str(j))}")
@@ -559,6 +678,8 @@ def emit_phase_c(dma_inside):
         if with_sc:
             E(f"s_branch {done}")
     label(done)
+    if OPT["tail"]:
+        emit_tail_gemm()
     stamp(PH_C_EPI)
     label(skip)
 
@@ -570,7 +691,8 @@ def gen_kernel(name, stamped=False, **opt):
     global out
     out = []
     STAMPED[0] = stamped
-    OPT.update(dict(stagger=True, nosilu=False, nomfma=False, nopk=False, nodma=False, nold=False, nost=False, prio=0, ntst=False, ntld=False))
+    assert not (stamped and opt.get("tail")), "the tail kernel keeps its scalars in the stamp accumulators"
+    OPT.update(dict(stagger=True, nosilu=False, nomfma=False, nopk=False, nodma=False, nold=False, nost=False, prio=0, ntst=False, ntld=False, tail=False))
     OPT.update(opt)
     _kernel_no[0] += 1
     _uid[0] = 100000 * _kernel_no[0]
@@ -583,6 +705,9 @@ def gen_kernel(name, stamped=False, **opt):
     E(f"s_load_dwordx8 s[{b0}:{b0 + 7}], {s2('karg')}, 0x20", "in_ld .. ntiles")
     E(f"s_load_dwordx4 s[{b0 + 8}:{b0 + 11}], {s2('karg')}, 0x40", "shortcut, G, magic_tpi, magic_tx")
     E(f"s_load_dwordx4 s[{b0 + 12}:{b0 + 15}], {s2('karg')}, 0x50", "in_bytes, pad, debug")
+    if OPT["tail"]:
+        E(f"s_load_dwordx2 {s2('cat')}, {s2('karg')}, {ARG_TAIL['cat']:#x}", "cv2's half of the concat buffer")
+        E(f"s_load_dword {s('cat_ld')}, {s2('karg')}, {ARG_TAIL['cat_ld']:#x}")
     T = [V.names["P"][0] + i for i in range(28)]
     E(f"v_and_b32 v{T[0]}, 63, {v('tid')}", "lane")
     E(f"v_lshrrev_b32 v{T[1]}, 6, {v('tid')}")
@@ -701,7 +826,10 @@ def gen_kernel(name, stamped=False, **opt):
     nb = uid("nb")
     E(f"s_cmp_lg_u32 {s('wave')}, 6")
     E(f"s_cbranch_scc1 {nb}")
-    E(f"v_cmp_gt_u32 vcc, 24, v{T[0]}", "96 floats = 24 lanes x 16 B")
+    if OPT["tail"]:
+        E(f"v_cmp_gt_u32 vcc, 48, v{T[0]}", "b1 | b2 | b3: 192 floats = 48 lanes x 16 B")
+    else:
+        E(f"v_cmp_gt_u32 vcc, 24, v{T[0]}", "96 floats = 24 lanes x 16 B")
     E("s_and_saveexec_b64 s[98:99], vcc")
     E(f"global_load_dwordx4 v[{T[8]}:{T[8] + 3}], v{T[3]}, {s2('bias')}")
     E("s_waitcnt vmcnt(0)")
@@ -709,6 +837,21 @@ def gen_kernel(name, stamped=False, **opt):
     E(f"ds_write_b128 v{T[4]}, v[{T[8]}:{T[8] + 3}]")
     E("s_mov_b64 exec, s[98:99]")
     label(nb)
+    if OPT["tail"]:
+        # the tail's 18 A fragments (behind W1 and W2 in the weight image) -> LDS: fragments wave, wave + 8 and (waves 0, 1) wave + 16
+        for f0 in (0, 8, 16):
+            nw3 = uid("nw3")
+            if f0 == 16:
+                E(f"s_cmp_gt_u32 {s('wave')}, 1")
+                E(f"s_cbranch_scc1 {nw3}")
+            E(f"s_lshl_b32 {s('tmp0')}, {s('wave')}, 10")
+            E(f"s_add_u32 {s('tmp0')}, {s('tmp0')}, {(6 + 42 + f0) * 1024}")
+            E(f"v_add_u32 v{T[4]}, {s('tmp0')}, v{T[3]}")
+            E(f"global_load_dwordx4 v[{T[8]}:{T[8] + 3}], v{T[4]}, {s2('w')}")
+            E("s_waitcnt vmcnt(0)")
+            E(f"v_add_u32 v{T[4]}, {W3_OFF - (6 + 42) * 1024}, v{T[4]}")
+            E(f"ds_write_b128 v{T[4]}, v[{T[8]}:{T[8] + 3}]")
+            label(nw3)
     # ---- pipeline fill: x patch of the first tile -> x buffer 0; second tile decoded ----
     E(f"s_mov_b32 {s('c_ok')}, 0")
     E(f"s_mov_b32 {s('b_ok')}, 0")
@@ -798,16 +941,16 @@ def gen_kernel(name, stamped=False, **opt):
     return list(out)
 
 
-def descriptor(name):
+def descriptor(name, lds=LDS_BYTES, arg_bytes=ARG_BYTES):
     total = (V.next + 7) // 8 * 8
-    assert total <= 256 and LDS_BYTES <= 160 * 1024
+    assert total <= 256 and lds <= 160 * 1024
     return f"""
 	.rodata
 	.p2align 6
 	.amdhsa_kernel {name}
-		.amdhsa_group_segment_fixed_size {LDS_BYTES}
+		.amdhsa_group_segment_fixed_size {lds}
 		.amdhsa_private_segment_fixed_size 0
-		.amdhsa_kernarg_size {ARG_BYTES}
+		.amdhsa_kernarg_size {arg_bytes}
 		.amdhsa_user_sgpr_count 2
 		.amdhsa_user_sgpr_kernarg_segment_ptr 1
 		.amdhsa_system_sgpr_workgroup_id_x 1
@@ -825,16 +968,16 @@ def descriptor(name):
 """
 
 
-def metadata_entry(name):
+def metadata_entry(name, lds=LDS_BYTES, arg_bytes=ARG_BYTES):
     total = (V.next + 7) // 8 * 8
     return f"""  - .agpr_count:     0
     .args:
       - .offset:         0
-        .size:           {ARG_BYTES}
+        .size:           {arg_bytes}
         .value_kind:     by_value
-    .group_segment_fixed_size: {LDS_BYTES}
+    .group_segment_fixed_size: {lds}
     .kernarg_segment_align: 8
-    .kernarg_segment_size: {ARG_BYTES}
+    .kernarg_segment_size: {arg_bytes}
     .max_flat_workgroup_size: 512
     .name:           {name}
     .private_segment_fixed_size: 0
@@ -867,11 +1010,13 @@ def main():
                      ("bottleneck_asm_c48_nomem", False, dict(nodma=True, nold=True, nost=True)),
                      ("bottleneck_asm_c48_ntst", False, dict(ntst=True)), ("bottleneck_asm_c48_ntld", False, dict(ntld=True)),
                      ("bottleneck_asm_c48_nt", False, dict(ntst=True, ntld=True))]
+    variants.append(("bottleneck_asm_c48_tail", False, dict(tail=True)))       # the C3 tail form (aq_bottleneck_c3tail; DESIGN.md 4.1f)
     for name, stamped, opt in variants:
         text += [f"\t.globl\t{name}", "\t.p2align\t8", f"\t.type\t{name},@function"]
         text += gen_kernel(name, stamped, **opt)
-        entries.append(metadata_entry(name))
-        text += [f".Lfend_{name}:", f"\t.size\t{name}, .Lfend_{name}-{name}", descriptor(name)]
+        sizes = (LDS_BYTES_TAIL, ARG_BYTES_TAIL) if opt.get("tail") else (LDS_BYTES, ARG_BYTES)
+        entries.append(metadata_entry(name, *sizes))
+        text += [f".Lfend_{name}:", f"\t.size\t{name}, .Lfend_{name}-{name}", descriptor(name, *sizes)]
     text.append(f"""	.amdgpu_metadata
 ---
 amdhsa.kernels:

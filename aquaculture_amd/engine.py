@@ -67,7 +67,7 @@ EXPORTS = (
     "aq_engine_infer", "aq_engine_run_ops", "aq_engine_candidates", "aq_engine_forward_raw", "aq_engine_tensor_ptr", "aq_engine_profile",
     "aq_engine_op_times", "aq_engine_num_ops", "aq_engine_set_conv_config", "aq_engine_autotune", "aq_engine_set_tuned_table",
     "aq_engine_get_conv_config", "aq_conv_num_configs", "aq_debug_conv_stamp", "aq_debug_mfma_peak",
-    "aq_conv_config_tiles", "aq_pack_conv_weights", "aq_pack_conv_weights_x3", "aq_conv2d", "aq_pack_stem_weights", "aq_stem_conv", "aq_pack_bottleneck_weights", "aq_bottleneck", "aq_pack_downblock_weights", "aq_downblock", "aq_stemdown_supported", "aq_stemdown", "aq_conv1x1_direct_supported", "aq_pack_conv1x1_direct", "aq_conv1x1_direct", "aq_conv1x1_asm_supported", "aq_pack_conv1x1_asm", "aq_conv1x1_asm", "aq_nms_opts", "aq_engine_set_nms_options",
+    "aq_conv_config_tiles", "aq_pack_conv_weights", "aq_pack_conv_weights_x3", "aq_conv2d", "aq_pack_stem_weights", "aq_stem_conv", "aq_pack_bottleneck_weights", "aq_bottleneck", "aq_bottleneck_c3tail_supported", "aq_pack_bottleneck_c3tail_weights", "aq_bottleneck_c3tail", "aq_pack_downblock_weights", "aq_downblock", "aq_stemdown_supported", "aq_stemdown", "aq_conv1x1_direct_supported", "aq_pack_conv1x1_direct", "aq_conv1x1_direct", "aq_conv1x1_asm_supported", "aq_pack_conv1x1_asm", "aq_conv1x1_asm", "aq_nms_opts", "aq_engine_set_nms_options",
     "aq_conv3x3s2_direct_supported", "aq_pack_conv3x3s2_direct", "aq_conv3x3s2_direct",
     "aq_conv3x3_pl_supported", "aq_conv3x3_pl_asm_family", "aq_pack_conv3x3_pl", "aq_conv3x3_pl", "aq_conv3x3_pl_s2_supported", "aq_pack_conv3x3_pl_s2", "aq_conv3x3_pl_s2", "aq_jpeg_scratch_bytes", "aq_jpeg_idct_rgb", "aq_f32_to_e4m3", "aq_conv1x1_direct_f8out", "aq_absmax_bf16", "aq_engine_calibrate_amax", "aq_engine_set_fp8_scales", "aq_engine_last_launch", "aq_conv3x3_pl_f8_supported", "aq_pack_conv3x3_pl_f8", "aq_conv3x3_pl_f8", "aq_conv3x3_pl_w8_supported", "aq_pack_conv3x3_pl_w8", "aq_conv3x3_pl_w8", "aq_head_decode_supported", "aq_pack_head_weights", "aq_head_decode", "aq_head_counts_gather", "aq_preprocess_s2d", "aq_sppf_pool",
     "aq_upsample2x", "aq_letterbox_u8", "aq_letterbox_tiles_u8", "aq_format_label_rows", "aq_detect_decode", "aq_nms_scratch_bytes", "aq_nms", "aq_jpeg_huffman_decode", "aq_write_label_files",
@@ -126,6 +126,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_stem_conv.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.aq_pack_bottleneck_weights.argtypes = [C.POINTER(f32), C.POINTER(f32), i32, vp, C.POINTER(sz), vp]
     lib.aq_bottleneck.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]
+    lib.aq_bottleneck_c3tail_supported.argtypes = [i32, i32, i32, i32, i32, i32]
+    lib.aq_pack_bottleneck_c3tail_weights.argtypes = [C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), vp, C.POINTER(sz), vp]
+    lib.aq_bottleneck_c3tail.argtypes = [vp, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp]
     lib.aq_pack_downblock_weights.argtypes = [C.POINTER(f32), C.POINTER(f32), vp, C.POINTER(sz), vp]
     lib.aq_downblock.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, i32, vp]
     lib.aq_conv1x1_direct_supported.argtypes = [i32, i32]
@@ -777,6 +780,41 @@ def bottleneck_nhwc(x: torch.Tensor, w1_oihw: torch.Tensor, b1: torch.Tensor, w2
     _check(lib.aq_bottleneck(x.data_ptr(), ld, 0, out.data_ptr(), old, 0, c, wbuf.data_ptr(), bbuf.data_ptr(), B, H, W, int(shortcut),
                              _stream_ptr()))
     torch.cuda.current_stream().synchronize()
+    return out
+
+
+def pack_bottleneck_c3tail(w1_oihw: torch.Tensor, b1: torch.Tensor, w2_oihw: torch.Tensor, b2: torch.Tensor, w3_oihw: torch.Tensor,
+                           b3: torch.Tensor, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(weight image, b1 | b2 | b3) of aq_bottleneck_c3tail: a C3 block's last Bottleneck (C = 48) and its cv3 1x1 (96 -> 96) (tests)."""
+    lib = load_library()
+    ws = [np.ascontiguousarray(w.permute(0, 2, 3, 1).float().cpu().numpy()) for w in (w1_oihw, w2_oihw, w3_oihw)]
+    ps = [w.ctypes.data_as(C.POINTER(C.c_float)) for w in ws]
+    n = C.c_size_t()
+    _check(lib.aq_pack_bottleneck_c3tail_weights(*ps, None, C.byref(n), None))
+    wbuf = torch.empty(n.value, dtype=torch.uint8, device=device)
+    _check(lib.aq_pack_bottleneck_c3tail_weights(*ps, wbuf.data_ptr(), C.byref(n), _stream_ptr()))
+    return wbuf, torch.cat([b1.float(), b2.float(), b3.float()]).to(device).contiguous()
+
+
+def bottleneck_c3tail_supported(B: int, H: int, W: int, in_ld: int = 48, cat_ld: int = 96, out_ld: int = 96) -> bool:
+    return bool(load_library().aq_bottleneck_c3tail_supported(B, H, W, in_ld, cat_ld, out_ld))
+
+
+def bottleneck_c3tail_nhwc(x: torch.Tensor, c: torch.Tensor, packed: Tuple[torch.Tensor, torch.Tensor], shortcut: bool = True,
+                           out: Optional[torch.Tensor] = None, sync: bool = True) -> torch.Tensor:
+    """bf16 NHWC x [B,H,W,48] and cv2's output c [B,H,W,48] (channel slices of dense tensors) -> SiLU(W3 [Bottleneck(x) | c] + b3)
+    [B,H,W,96] through aq_bottleneck_c3tail, on the current stream (tests, tools/time_c3tail.py).  ``packed``: pack_bottleneck_c3tail."""
+    _require_gpu()
+    lib = load_library()
+    assert x.dtype == torch.bfloat16 and c.dtype == torch.bfloat16 and x.stride(3) == 1 and c.stride(3) == 1
+    B, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty((B, H, W, 96), dtype=torch.bfloat16, device=x.device)
+    # data_ptr() of a channel slice already points at its first channel: ch_off = 0 with the parent's row length
+    _check(lib.aq_bottleneck_c3tail(x.data_ptr(), x.stride(2), 0, c.data_ptr(), c.stride(2), 0, out.data_ptr(), out.stride(2), 0,
+                                    packed[0].data_ptr(), packed[1].data_ptr(), B, H, W, int(shortcut), _stream_ptr()))
+    if sync:
+        torch.cuda.current_stream().synchronize()
     return out
 
 

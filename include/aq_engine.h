@@ -216,6 +216,18 @@ int aq_pack_bottleneck_weights(const float* w1_host, const float* w2_host, int C
 int aq_bottleneck(const void* in_dev, int in_ld, int in_choff, void* out_dev, int out_ld, int out_choff, int C,
                   const void* packed_w_dev, const float* bias_dev, int B, int H, int W, int shortcut, void* stream);
 
+/* A C3 block's last Bottleneck (C = 48) with the block's cv3 1x1 in its epilogue (AQ_OP_BOTTLENECK followed by its AQ_OP_CONV; engines do
+ * this on their own, AQ_C3TAIL=0 turns it off): out = SiLU(W3 [Bottleneck(x) | cat] + b3), 96 channels; the Bottleneck's output is not
+ * written.  cat: cv2's 48 channels at cat_choff.  bias_dev: b1 | b2 | b3 (192 floats); w3: fp32 KRSC [96][1][1][96].  Bit-identical to
+ * aq_bottleneck followed by aq_conv1x1_direct.  Unsupported geometries (the assembly kernel's: images narrower than two tiles,
+ * AQ_BTL_ASM=0, 32-bit offsets) return AQ_ERR_INVALID without a launch; aq_bottleneck_c3tail_supported asks first. */
+int aq_bottleneck_c3tail_supported(int B, int H, int W, int in_ld, int cat_ld, int out_ld);
+int aq_pack_bottleneck_c3tail_weights(const float* w1_host, const float* w2_host, const float* w3_host, void* packed_dev, size_t* bytes,
+                                      void* stream);
+int aq_bottleneck_c3tail(const void* in_dev, int in_ld, int in_choff, const void* cat_dev, int cat_ld, int cat_choff, void* out_dev,
+                         int out_ld, int out_choff, const void* packed_w_dev, const float* bias_dev, int B, int H, int W, int shortcut,
+                         void* stream);
+
 /* Fused down-sampling block (bf16 only, 48 -> 96 -> 96 channels): y = SiLU(Wb_1x1 . SiLU(Wa_3x3/s2 (*) x)) in ONE launch.
  * Replaces yolov5m's model.1 = Conv(48, 96, 3, 2) followed by the stacked model.2.cv1|cv2 1x1 convs
  * [UPSTREAM models/common.py Conv.forward_fuse, C3.forward].  In the plan (op kind AQ_OP_DOWNBLOCK): weight = wa KRSC

@@ -122,8 +122,9 @@ def steps_of(disp, kernels_per_step=None):
                 step.append((max(cur - 1, 0), d))
                 continue
             step.append((nxt, d))
-            cur = nxt + 1
+            cur = nxt + (2 if "bottleneck_asm_c48_tail" in d["name"] else 1)      # (the C3 tail computes the next op, cv3, too)
         seen = {i for i, _ in step}
+        seen |= {i + 1 for i, d in step if "bottleneck_asm_c48_tail" in d["name"]}     # the C3 tail: cv3 runs inside the Bottleneck's launch
         need = {i for i, o in enumerate(plan.ops) if o.kind != spec.OP_DECODE}
         if need - seen:
             ok = False
