@@ -30,7 +30,7 @@ from . import postprocess
 from .checkpoint import load_checkpoint
 from .dataloader import LoadImages, check_img_size
 
-UNSUPPORTED = ("view_img", "save_crop", "visualize", "update", "dnn")
+UNSUPPORTED = ("view_img", "visualize", "update", "dnn")
 
 
 def increment_path(path, exist_ok=False, sep="", mkdir=False) -> Path:
@@ -62,7 +62,9 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--view-img", action="store_true")
     p.add_argument("--save-txt", action="store_true", help="save results to *.txt")
     p.add_argument("--save-conf", action="store_true", help="save confidences in --save-txt labels")
-    p.add_argument("--save-crop", action="store_true")
+    p.add_argument("--save-crop", action="store_true",
+                   help="save each detection's crop as <save_dir>/crops/<class>/<image stem>[k].jpg [UPSTREAM save_one_box]: pixels encoded on the GPU, "
+                        "Huffman coding and files on host threads; byte-identical to Pillow's quality=95 4:4:4 JPEG of the same window")
     p.add_argument("--nosave", action="store_true", help="do not save images/videos")
     p.add_argument("--classes", nargs="+", type=int, help="filter by class: --classes 0, or --classes 0 2 3")
     p.add_argument("--agnostic-nms", action="store_true")
@@ -112,21 +114,23 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
     return opt
 
 
-def run_params(weights_id, conf_thres, iou_thres, max_det, imgsz, precision, save_conf, classes=None, agnostic_nms=False, augment=False) -> dict:
+def run_params(weights_id, conf_thres, iou_thres, max_det, imgsz, precision, save_conf, classes=None, agnostic_nms=False, augment=False,
+               save_crop=False) -> dict:
     """What the label bytes depend on (run_params.json; --resume refuses a directory written with anything else).  The optional settings are
     recorded only when set, so that the record of a run without them stays what it always was."""
     return {"weights_sha256": weights_id, "conf_thres": float(conf_thres), "iou_thres": float(iou_thres), "max_det": int(max_det),
             "imgsz": [int(v) for v in imgsz], "precision": precision, "save_conf": bool(save_conf),
             **({"classes": sorted(int(c) for c in classes)} if classes is not None else {}),
             **({"agnostic_nms": True} if agnostic_nms else {}),
-            **({"augment": True} if augment else {})}
+            **({"augment": True} if augment else {}),
+            **({"save_crop": True} if save_crop else {})}
 
 
 def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_det=1000, device="",
         save_txt=False, save_conf=False, nosave=False, classes=None, agnostic_nms=False,
         project="runs/detect", name="exp", exist_ok=False, half=False, batch_size=64, precision=None,
         workers=8, decode_threads=False, quiet=False, geocode_bboxes=None, geocode_out=None, tile_scenes=0, autotune="auto", resume=False,
-        jpeg_decode="auto", augment=False, log=print, **unsupported):
+        jpeg_decode="auto", augment=False, save_crop=False, log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb, jpeg_slots_to_rgb, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     for k in UNSUPPORTED:
@@ -155,6 +159,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
     if rank == 0:
         save_dir = increment_path(Path(project) / name, exist_ok=exist_ok or resume)
         (save_dir / "labels" if save_txt else save_dir).mkdir(parents=True, exist_ok=True)
+        if save_crop:
+            (save_dir / "crops").mkdir(exist_ok=True)
     if multi:
         box = [str(save_dir) if rank == 0 else None]
         torch.distributed.broadcast_object_list(box, src=0)
@@ -168,7 +174,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
     # a tile before rank 0 has accepted the directory, and a refusal reaches every rank.
     aqdist.on_rank0(lambda: None if tile_scenes else check_run_params(
         str(save_dir), run_params(file_digest(weights) if os.path.isfile(str(weights)) else str(weights), conf_thres, iou_thres, max_det, imgsz,
-                                  precision, save_conf, classes, agnostic_nms, augment), resume))
+                                  precision, save_conf, classes, agnostic_nms, augment, save_crop), resume))
     done_before = DoneManifest.load(str(save_dir)) if resume else set()
     manifest = DoneManifest(str(save_dir), rank)
     if not tile_scenes:
@@ -230,11 +236,14 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
 
     def writer():
         try:
+            if save_crop:
+                torch.cuda.set_device(dev)          # HIP's current device is per thread: the crop encode launches from here
             while True:
                 item = q.get()
                 if item is None:
                     return
-                ev, counts_h, dets_h, paths, shapes0, hw, gidx, t_inf, slot_id = item
+                ev, counts_h, dets_h, paths, shapes0, hw, gidx, t_inf, slot_id, crop_src = item
+                item = None
                 ev.synchronize()
                 t0 = time.perf_counter()
                 nlab = ndet = 0
@@ -242,6 +251,10 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 H, W = hw
                 cnt = counts_h.numpy()
                 det_all = dets_h.numpy()
+                crops = None
+                if crop_src is not None:            # before the slot goes back: its stream and arenas carry the encode
+                    crops = encode_batch_crops(det_all, cnt[:len(paths)], (H, W), shapes0, paths, crop_src, slot_id)
+                    crop_src = None                 # the batch's original images may go
                 written = []
                 same = all(sh == shapes0[0] for sh in shapes0)       # the pinned path: one original size per batch -> one numpy pass for all tiles
                 if same:
@@ -290,6 +303,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                             gather.add(torch.full((det.shape[0],), gidx[b], dtype=torch.int32), aqdist.pack_rows(torch.from_numpy(det.copy())))
                 if not released:
                     slot_free[slot_id].release()
+                if crops is not None:
+                    write_batch_crops(*crops)
                 # the manifest line below vouches for these bytes: on disk first (files and their directory entries), then the record -- a
                 # node crash must not leave a recorded tile without its label file (it would look like "no detections" for good).
                 # One syncfs per batch; per-file fsync + directory fsync where that is unavailable.
@@ -317,6 +332,52 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             while True:              # keep draining so q.put() cannot block either
                 if q.get() is None:
                     return
+
+    crops_dir = str(save_dir / "crops")
+    crop_arena = [None] * depth                            # per slot: (device int16, pinned int16) coefficient arenas, made on first use
+
+    def encode_batch_crops(det_all, cnt, hw, shapes0, paths, crop_src, slot_id):
+        """--save-crop, first half (slot held): upstream's crop rectangles and names for the batch, the encode kernel on the slot's stream,
+        the used part of the arena back in host memory.  -> (coefficients, crop table, paths relative to save_dir) or None."""
+        from .engine import CROP_ARENA_BLOCKS, crop_blocks, crop_table, encode_crops
+        images, bases, pitch = crop_src
+        groups = {}
+        for b, sh in enumerate(shapes0):                  # (one original size per batch in practice; tiles of another size in turn)
+            groups.setdefault(tuple(sh), []).append(b)
+        tiles_, rects_, rel = [], [], []
+        for sh, idx in groups.items():
+            idx = np.asarray(idx)
+            tile, cls, rects, ordinal = postprocess.batch_crops(det_all[idx], cnt[idx], hw, sh)
+            tiles_.append(idx[tile])
+            rects_.append(rects)
+            for t_, c_, k_ in zip(idx[tile].tolist(), cls.tolist(), ordinal.tolist()):
+                rel.append(f"crops/{ck.names[c_]}/{postprocess.crop_file_name(Path(paths[t_]).stem, k_)}")
+        if not rel:
+            return None
+        table = crop_table(np.asarray(bases, np.int64)[np.concatenate(tiles_)], pitch, np.concatenate(rects_))
+        need = max(CROP_ARENA_BLOCKS, int(crop_blocks(table).max()))
+        with torch.cuda.stream(streams[slot_id]):
+            if crop_arena[slot_id] is None or crop_arena[slot_id][0].numel() < need * 192:
+                crop_arena[slot_id] = (torch.empty(need * 192, dtype=torch.int16, device=dev), torch.empty(need * 192, dtype=torch.int16, pin_memory=True))
+            coef, table = encode_crops(images, table, arena_blocks=crop_arena[slot_id][0].numel() // 192, arena=crop_arena[slot_id][0],
+                                       arena_host=crop_arena[slot_id][1])
+        return coef, table, rel
+
+    def write_batch_crops(coef, table, rel):
+        """--save-crop, second half (slot free): Huffman coding and files in one C call on four threads, then on disk before the manifest
+        records the batch (syncfs; per-file fsync and directory fsyncs where that is unavailable)."""
+        from .engine import write_crop_files
+        write_crop_files(str(save_dir), rel, coef, table, threads=4, fsync=durable and not can_syncfs[0])
+        if durable and not (can_syncfs[0] and sync_filesystem_of(crops_dir)):
+            if can_syncfs[0]:
+                can_syncfs[0] = False
+                for r_ in rel:
+                    fd_ = os.open(os.path.join(str(save_dir), r_), os.O_RDONLY)
+                    os.fsync(fd_)
+                    os.close(fd_)
+            for d_ in sorted({os.path.dirname(r_) for r_ in rel}):
+                fsync_dir(os.path.join(str(save_dir), d_))
+            fsync_dir(crops_dir)
 
     lock = threading.Lock()
     manifest_lock = threading.Lock()
@@ -493,6 +554,13 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 yield p_, h_, s_, bi_, sub.indices[n_: n_ + len(p_)]
                 n_ += len(p_)
 
+    def original_images(tiles0):
+        """--save-crop: the batch's decoded tiles (uint8 CUDA [B, H0, W0, 3]) as the crop encoder addresses them; None without the flag."""
+        if not save_crop:
+            return None
+        B_, H0_, W0_, _ = tiles0.shape
+        return tiles0.view(-1), [b_ * H0_ * W0_ * 3 for b_ in range(B_)], W0_ * 3
+
     release_of = [None]
     split_note = [False]
     t_steady, n_steady, n_fed = [None], [0], [0]
@@ -521,6 +589,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             if diag is not None:
                 diag["slot_wait"] += time.perf_counter() - t0
             st = streams[slot]
+            crop_src = None
             with torch.cuda.stream(st):
                 if isinstance(host, tuple) and host[0] == "scene":      # scene mode: one upload per scene, tiles cut by the letterbox kernel
                     _, spath, sarr, origins, thw = host
@@ -532,6 +601,9 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     else:
                         st.wait_event(scene_ev)            # another stream uploaded this scene
                     scene_dev.record_stream(st)
+                    if save_crop:                          # the crops are cut from the raster: tile b's pixel (x, y) at its origin + (x, y)
+                        row_b = int(scene_dev.shape[1]) * 3
+                        crop_src = (scene_dev.view(-1), [y0 * row_b + x0 * 3 for x0, y0 in origins], row_b)
                     tiles = letterbox_scene_tiles(scene_dev, origins, thw, tuple(imgsz), int(max(ck.stride)), True)
                 elif isinstance(host, tuple) and host[0] == "gpu_coef":   # --jpeg-decode gpu: the coefficient blocks are in HBM already
                     _, coef_v, qt_v, dec_ev, hook, (h0_, w0_), nco_ = host
@@ -543,6 +615,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     used_ev = torch.cuda.Event()
                     used_ev.record(st)
                     hook(used_ev)                          # the super-batch's buffer is free for its next decode once this batch has read it
+                    crop_src = original_images(tiles)
                     tiles = letterbox_device(tiles, tuple(imgsz), int(max(ck.stride)), True)
                 else:
                     tiles = host.to(dev, non_blocking=True)
@@ -555,6 +628,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                         if jpeg_scratch[slot] is None:
                             jpeg_scratch[slot] = torch.empty(eng.lib.aq_jpeg_scratch_bytes(batch_size, h0_, w0_), dtype=torch.uint8, device=tiles.device)
                         tiles = jpeg_slots_to_rgb(tiles, h0_, w0_, scratch=jpeg_scratch[slot])
+                    crop_src = original_images(tiles)
                     tiles = letterbox_device(tiles, tuple(imgsz), int(max(ck.stride)), True)
                 if tune:                                   # once, before the pipeline fills
                     tune = False
@@ -587,7 +661,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             H, W = int(tiles.shape[1]), int(tiles.shape[2])
             shape_str = f"(1, 3, {H}, {W})"
             t2 = time.perf_counter()
-            q.put((ev, counts_h, dets_h, paths, shapes0, (H, W), list(gidx), t2 - t1, slot))
+            q.put((ev, counts_h, dets_h, paths, shapes0, (H, W), list(gidx), t2 - t1, slot, crop_src))
+            crop_src = None
             if diag is not None:
                 diag["put"] += time.perf_counter() - t2
             n_fed[0] += len(paths)

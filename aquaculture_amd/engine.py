@@ -71,6 +71,7 @@ EXPORTS = (
     "aq_conv3x3s2_direct_supported", "aq_pack_conv3x3s2_direct", "aq_conv3x3s2_direct",
     "aq_conv3x3_pl_supported", "aq_conv3x3_pl_asm_family", "aq_pack_conv3x3_pl", "aq_conv3x3_pl", "aq_conv3x3_pl_s2_supported", "aq_pack_conv3x3_pl_s2", "aq_conv3x3_pl_s2", "aq_jpeg_scratch_bytes", "aq_jpeg_idct_rgb", "aq_f32_to_e4m3", "aq_conv1x1_direct_f8out", "aq_absmax_bf16", "aq_engine_calibrate_amax", "aq_engine_set_fp8_scales", "aq_engine_last_launch", "aq_conv3x3_pl_f8_supported", "aq_pack_conv3x3_pl_f8", "aq_conv3x3_pl_f8", "aq_conv3x3_pl_w8_supported", "aq_pack_conv3x3_pl_w8", "aq_conv3x3_pl_w8", "aq_head_decode_supported", "aq_pack_head_weights", "aq_head_decode", "aq_head_counts_gather", "aq_preprocess_s2d", "aq_sppf_pool",
     "aq_upsample2x", "aq_letterbox_u8", "aq_letterbox_tiles_u8", "aq_format_label_rows", "aq_detect_decode", "aq_nms_scratch_bytes", "aq_nms", "aq_jpeg_huffman_decode", "aq_write_label_files",
+    "aq_crop_jpeg_coefs", "aq_crop_jpeg_bytes", "aq_write_crop_files",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -110,6 +111,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_jpeg_huffman_decode.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     lib.aq_write_label_files.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(f32), C.POINTER(C.c_longlong), i32, i32, i32]
     lib.aq_write_label_files.restype = C.c_long
+    lib.aq_crop_jpeg_coefs.argtypes = [vp, C.c_longlong, vp, i32, i32, vp, vp]
+    lib.aq_crop_jpeg_bytes.argtypes = [vp, i32, i32, vp, sz]
+    lib.aq_crop_jpeg_bytes.restype = C.c_long
+    lib.aq_write_crop_files.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), vp, vp, i32, i32, i32]
+    lib.aq_write_crop_files.restype = C.c_long
     lib.aq_engine_set_tuned_table.argtypes = [vp, i32, i32, i32, C.POINTER(i32), i32]
     lib.aq_engine_calibrate_amax.argtypes = [vp, vp, i32, i32, i32, vp, sz, C.POINTER(f32), i32, vp]
     lib.aq_engine_set_fp8_scales.argtypes = [vp, C.POINTER(f32), i32]
@@ -730,6 +736,111 @@ def write_label_files(labels_dir: str, stems, rows: np.ndarray, offsets: np.ndar
                                  int(save_conf), int(fsync))
     if k < 0:
         raise OSError(f"could not write the label file of {stems[-1 - k]} in {labels_dir}")
+    return int(k)
+
+
+# aq_crop (include/aq_engine.h): one crop of a uint8 RGB device image -- pixel (x, y) at base + y * pitch + 3 x, window [x1, x2) x [y1, y2),
+# first block position in the coefficient arena
+CROP_DTYPE = np.dtype([("base", "<i8"), ("pitch", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"), ("block", "<i4")])
+CROP_ARENA_BLOCKS = 1 << 16        # block positions (384 bytes each) per encode piece: 25 MB of device arena and as much pinned
+
+
+def crop_blocks(table: np.ndarray) -> np.ndarray:
+    """Block positions (8 x 8 pixels, three components) of each crop of a CROP_DTYPE table."""
+    return ((table["x2"].astype(np.int64) - table["x1"] + 7) // 8) * ((table["y2"].astype(np.int64) - table["y1"] + 7) // 8)
+
+
+def crop_table(bases, pitch, rects) -> np.ndarray:
+    """CROP_DTYPE table of n crops: bases int64 [n] (byte offset of each crop's image), pitch (row bytes; scalar or [n]), rects int [n, 4]
+    (x1, y1, x2, y2); the crops' block positions follow each other from 0."""
+    rects = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
+    t = np.zeros(rects.shape[0], CROP_DTYPE)
+    t["base"], t["pitch"] = bases, pitch
+    t["x1"], t["y1"], t["x2"], t["y2"] = rects.T
+    nb = crop_blocks(t)
+    if nb.sum() >= 1 << 31:
+        raise ValueError("crop table: more than 2^31 block positions in one call")
+    t["block"][1:] = np.cumsum(nb)[:-1]
+    return t
+
+
+def encode_crops(images_dev: torch.Tensor, table: np.ndarray, arena_blocks: int = CROP_ARENA_BLOCKS, arena: Optional[torch.Tensor] = None,
+                 arena_host: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """The device half of --save-crop (aq_crop_jpeg_coefs) on the current stream: images_dev = the uint8 CUDA buffer the table's byte offsets
+    point into, table = crop_table(...).  The crops go through an arena of `arena_blocks` block positions in pieces (a crop never straddles
+    two); after each piece only its used part comes back through the pinned arena.  `arena` (int16 CUDA) / `arena_host` (int16 pinned),
+    at least arena_blocks x 192 values each, are reused when given.  Returns (coefficients int16 [positions, 192] in host memory, table)."""
+    _require_gpu()
+    lib = load_library()
+    assert images_dev.is_cuda and images_dev.dtype == torch.uint8 and images_dev.is_contiguous()
+    table = np.ascontiguousarray(table, dtype=CROP_DTYPE)
+    n = table.shape[0]
+    nb = crop_blocks(table)
+    if n == 0:
+        return np.zeros((0, 192), np.int16), table
+    ends = table["block"].astype(np.int64) + nb
+    if table["block"][0] != 0 or np.any(table["block"][1:] != ends[:-1]):
+        raise ValueError("crop table: block positions must follow each other from 0 (crop_table)")
+    w, h = table["x2"] - table["x1"], table["y2"] - table["y1"]
+    last = table["base"] + (table["y2"].astype(np.int64) - 1) * table["pitch"] + 3 * table["x2"].astype(np.int64)
+    bad = (w <= 0) | (h <= 0) | (w > 65535) | (h > 65535) | (table["x1"] < 0) | (table["y1"] < 0) | (table["base"] < 0) | \
+          (table["pitch"] < 3 * table["x2"].astype(np.int64)) | (last > images_dev.numel())
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"crop {i} {table[i]} is empty or leaves its image ({images_dev.numel()} bytes)")
+    if int(nb.max()) > arena_blocks:
+        raise ValueError(f"a crop of {int(nb.max())} block positions does not fit an arena of {arena_blocks}")
+    if arena is None or arena.numel() < arena_blocks * 192:
+        arena = torch.empty(arena_blocks * 192, dtype=torch.int16, device=images_dev.device)
+    if arena_host is None or arena_host.numel() < arena_blocks * 192:
+        arena_host = torch.empty(arena_blocks * 192, dtype=torch.int16, pin_memory=True)
+    table_dev = torch.from_numpy(table.view(np.uint8)).to(images_dev.device, non_blocking=False)
+    out = np.empty((int(ends[-1]), 192), np.int16)
+    stream = torch.cuda.current_stream()
+    c0 = 0
+    while c0 < n:
+        p0 = int(table["block"][c0])
+        c1 = int(np.searchsorted(ends, p0 + arena_blocks, side="right"))
+        used = int(ends[c1 - 1]) - p0
+        _check(lib.aq_crop_jpeg_coefs(images_dev.data_ptr(), images_dev.numel(), table_dev.data_ptr() + c0 * CROP_DTYPE.itemsize, c1 - c0, used,
+                                      arena.data_ptr(), stream.cuda_stream))
+        arena_host[:used * 192].copy_(arena[:used * 192], non_blocking=True)
+        stream.synchronize()
+        out[p0:p0 + used] = arena_host[:used * 192].numpy().reshape(used, 192)
+        c0 = c1
+    return out, table
+
+
+def crop_jpeg_bytes(coef: np.ndarray, w: int, h: int) -> bytes:
+    """The JPEG file of one w x h crop from its coefficient positions (aq_crop_jpeg_bytes; int16 [ceil(w/8) ceil(h/8), 192])."""
+    lib = load_library()
+    nblk = ((w + 7) // 8) * ((h + 7) // 8)
+    coef = np.ascontiguousarray(coef.reshape(-1)[:nblk * 192], dtype=np.int16)
+    assert coef.size == nblk * 192
+    buf = C.create_string_buffer(1024 + nblk * 192)
+    k = lib.aq_crop_jpeg_bytes(coef.ctypes.data, int(w), int(h), buf, len(buf))
+    if k < 0:
+        buf = C.create_string_buffer(-k)
+        k = lib.aq_crop_jpeg_bytes(coef.ctypes.data, int(w), int(h), buf, len(buf))
+    if k <= 0:
+        raise ValueError(f"crop_jpeg_bytes: bad crop size {w} x {h}")
+    return buf.raw[:k]
+
+
+def write_crop_files(root_dir: str, rel_paths, coef: np.ndarray, table: np.ndarray, threads: int = 4, fsync: bool = False) -> int:
+    """One C call per batch (aq_write_crop_files; no interpreter lock held): crop i of `table`, coefficients from position table[i]["block"] of
+    `coef` (encode_crops), -> <root_dir>/<rel_paths[i]> on `threads` threads, directories created on the way.  Returns the number of files."""
+    lib = load_library()
+    table = np.ascontiguousarray(table, dtype=CROP_DTYPE)
+    coef = np.ascontiguousarray(coef, dtype=np.int16)
+    n = table.shape[0]
+    assert len(rel_paths) == n and (n == 0 or coef.shape[0] >= int((table["block"].astype(np.int64) + crop_blocks(table)).max()))
+    if n == 0:
+        return 0
+    arr = (C.c_char_p * n)(*[os.fsencode(p_) for p_ in rel_paths])
+    k = lib.aq_write_crop_files(os.fsencode(root_dir), arr, coef.ctypes.data, table.ctypes.data, n, int(threads), int(fsync))
+    if k < 0:
+        raise OSError(f"could not write the crop {rel_paths[-1 - k]} in {root_dir}")
     return int(k)
 
 

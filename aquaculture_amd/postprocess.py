@@ -85,6 +85,63 @@ def batch_rows(det_all: np.ndarray, counts: np.ndarray, img1_shape, img0_shape):
     return rows[rev], offsets
 
 
+def crop_rects(xyxy: np.ndarray, h0, w0) -> np.ndarray:
+    """--save-crop geometry [UPSTREAM utils/plots.py save_one_box(xyxy, im, gain=1.02, pad=10)] in fp32, one operation at a time as PyTorch's
+    CPU kernels run it: xyxy2xywh, ``b[:, 2:] * 1.02 + 10``, xywh2xyxy, ``.long()`` (truncation toward zero), clip_boxes to the image
+    (x in [0, w0], y in [0, h0]).  xyxy float32 [n, 4] = the rounded boxes in original pixels; h0 / w0 scalars or [n].  -> int64 [n, 4]
+    (x1, y1, x2, y2): the crop is ``im[y1:y2, x1:x2]``."""
+    b = np.asarray(xyxy, dtype=F32).reshape(-1, 4)
+    xc = (b[:, 0] + b[:, 2]) / F32(2)
+    yc = (b[:, 1] + b[:, 3]) / F32(2)
+    w = (b[:, 2] - b[:, 0]) * F32(1.02) + F32(10)
+    h = (b[:, 3] - b[:, 1]) * F32(1.02) + F32(10)
+    r = np.stack([xc - w / F32(2), yc - h / F32(2), xc + w / F32(2), yc + h / F32(2)], 1).astype(np.int64)
+    w0 = np.asarray(w0, dtype=np.int64)
+    h0 = np.asarray(h0, dtype=np.int64)
+    r[:, 0] = np.clip(r[:, 0], 0, w0)
+    r[:, 2] = np.clip(r[:, 2], 0, w0)
+    r[:, 1] = np.clip(r[:, 1], 0, h0)
+    r[:, 3] = np.clip(r[:, 3], 0, h0)
+    return r
+
+
+def batch_crops(det_all: np.ndarray, counts: np.ndarray, img1_shape, img0_shape):
+    """--save-crop for a whole batch of tiles of ONE original size in one pass: det_all [B, max_det, 6], counts [B] -> (tile int64 [N],
+    cls int64 [N], rects int64 [N, 4], ordinal int64 [N]), every tile's crops in upstream's order (``for *xyxy, conf, cls in reversed(det)``,
+    ascending confidence), tile after tile.  ordinal k counts the crops of one class in one tile from 1: upstream's increment_path names
+    them <stem>.jpg, <stem>2.jpg, ... in a fresh directory (crop_file_name)."""
+    counts = np.asarray(counts, dtype=np.int64)
+    B = counts.shape[0]
+    offsets = np.zeros(B + 1, np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    n = int(offsets[-1])
+    if n == 0:
+        z = np.zeros(0, np.int64)
+        return z, z.copy(), np.zeros((0, 4), np.int64), z.copy()
+    valid = np.arange(det_all.shape[1])[None, :] < counts[:, None]
+    det = np.asarray(det_all[:B], dtype=F32)[valid]                     # [N, 6], tile-major, descending confidence inside a tile
+    tile = np.repeat(np.arange(B), counts)
+    pos = np.arange(n)
+    rev = offsets[tile] + (counts[tile] - 1) - (pos - offsets[tile])     # reversed(det), per tile
+    det = det[rev]
+    xyxy = np.rint(scale_boxes(img1_shape, det[:, :4], img0_shape)).astype(F32)   # det[:, :4] = scale_boxes(...).round()
+    rects = crop_rects(xyxy, img0_shape[0], img0_shape[1])
+    cls = det[:, 5].astype(np.int64)
+    order = np.lexsort((pos, cls, tile))                                # stable: (tile, class), then upstream's order
+    key = tile[order] * (int(cls.max()) + 1) + cls[order]
+    first = np.r_[True, key[1:] != key[:-1]]
+    start = np.maximum.accumulate(np.where(first, np.arange(n), 0))
+    ordinal = np.empty(n, np.int64)
+    ordinal[order] = np.arange(n) - start + 1
+    return tile, cls, rects, ordinal
+
+
+def crop_file_name(stem: str, ordinal: int) -> str:
+    """<stem>.jpg for the first crop of a class in an image, <stem>2.jpg, <stem>3.jpg, ... for the next ([UPSTREAM increment_path] with
+    sep='' in a directory that holds no crops of this image yet)."""
+    return f"{stem}{ordinal if ordinal > 1 else ''}.jpg"
+
+
 def format_rows(rows: np.ndarray, save_conf: bool = True) -> str:
     """Text of one label file.  Each value through ``%g`` of the double that equals the fp32 value
     (one C-level format call for the whole file: the same conversions as upstream's per-line ``%``)."""

@@ -472,6 +472,24 @@ long aq_format_label_rows(const float* rows, int n, int save_conf, char* buf, si
 long aq_write_label_files(const char* dir, const char* const* stems, const float* rows, const long long* offsets, int n_tiles,
                           int save_conf, int do_fsync);
 
+/* --save-crop [UPSTREAM utils/plots.py save_one_box: Pillow, quality=95, subsampling=0]: one crop of a uint8 RGB image in device memory.
+ * Pixel (x, y) of its image is at base + y * pitch + 3 x; the crop is [x1, x2) x [y1, y2); block = its first 8x8 block position in the
+ * coefficient arena.  A block position holds 3 x 64 int16 (Y, Cb, Cr), each block in zigzag order; a crop has ceil(w / 8) ceil(h / 8)
+ * positions in raster order. */
+typedef struct aq_crop { int64_t base; int32_t pitch, x1, y1, x2, y2, block; } aq_crop;
+/* Device half of the crop encoder, bit-exact with libjpeg(-turbo) at quality 95, 4:4:4: edge replication, rgb_ycc_convert, level shift,
+ * jpeg_fdct_islow, quantisation.  crops_dev: n_crops crops sorted by block, back to back; coef_dev receives n_blocks positions, the first
+ * crop's first position at coef_dev.  A crop whose window leaves [images_dev, images_dev + image_bytes) gets zero coefficients. */
+int aq_crop_jpeg_coefs(const uint8_t* images_dev, long long image_bytes, const aq_crop* crops_dev, int n_crops, int n_blocks,
+                       int16_t* coef_dev, void* stream);
+/* Host half: the JFIF file of one w x h crop from its coefficient positions (the markers, tables and entropy coding Pillow's encoder
+ * writes).  Returns bytes written, or -(bytes needed). */
+long aq_crop_jpeg_bytes(const int16_t* coef, int w, int h, uint8_t* buf, size_t buflen);
+/* A batch of crop files on n_threads threads (no interpreter lock held): crop i, coefficients from position crops[i].block of coef (host
+ * memory), -> <dir>/<rel_paths[i]> (truncating; missing directories are created).  Returns files written, or -1 - i. */
+long aq_write_crop_files(const char* dir, const char* const* rel_paths, const int16_t* coef, const aq_crop* crops, int n_crops,
+                         int n_threads, int do_fsync);
+
 #ifdef __cplusplus
 }
 #endif
