@@ -733,6 +733,11 @@ void btl_tail_pack_w3(const float* w3, bf16_t* dst) {
 
 }  // namespace
 
+// 1 when aq_bottleneck takes this launch on a generated-assembly build (C = 48 or 96), 0 when it runs the HIP-source kernel.
+extern "C" int aq_bottleneck_asm_form(int C, int B, int H, int W, int in_ld, int out_ld) {
+    return btl_asm_fits(C, B, H, W, in_ld, out_ld) || btl96_asm_fits(C, B, H, W, in_ld, out_ld);
+}
+
 // AQ_C3TAIL=0 (the engine's A/B switch) is read by the engine; this query follows btl_asm_fits, plus the concat's 32-bit row offsets.
 extern "C" int aq_bottleneck_c3tail_supported(int B, int H, int W, int in_ld, int cat_ld, int out_ld) {
     if (!btl_asm_fits(48, B, H, W, in_ld, out_ld)) return 0;
@@ -855,9 +860,11 @@ extern "C" int aq_bottleneck(const void* in_dev, int in_ld, int in_choff, void* 
     BtlParams p{};
     p.in = (const char*)in_dev + (size_t)in_choff * 2; p.in_ld_b = in_ld * 2;
     p.out = (char*)out_dev + (size_t)out_choff * 2; p.out_ld_b = out_ld * 2;
-    {   // the kernel reads halos of pixels other workgroups write: refuse aliasing buffers
-        const char* i0 = (const char*)in_dev; const char* i1 = i0 + (size_t)B * H * W * in_ld * 2;
-        const char* o0 = (const char*)out_dev; const char* o1 = o0 + (size_t)B * H * W * out_ld * 2;
+    {   // the kernel reads halos of pixels other workgroups write: refuse aliasing buffers.  Spans run from the first to the last byte of
+        // each slice, as in aq_bottleneck_c3tail (full rows from the slice's first channel reach into the next buffer: a false overlap)
+        const size_t np = (size_t)B * H * W;
+        const char* i0 = (const char*)in_dev + (size_t)in_choff * 2; const char* i1 = i0 + ((np - 1) * in_ld + C) * 2;
+        const char* o0 = (const char*)out_dev + (size_t)out_choff * 2; const char* o1 = o0 + ((np - 1) * out_ld + C) * 2;
         AQ_REQUIRE(o1 <= i0 || i1 <= o0, "bottleneck: output overlaps input");
     }
     p.w = (const char*)packed_w_dev; p.bias = bias_dev;

@@ -208,6 +208,8 @@ void set_dims(aq_engine* e, int H, int W) {
 
 constexpr int kNmsRowLimit = 1 << 17;   // aq_nms: N < 2^17 rows per image
 
+int plan_unfit_op(const aq_engine* e, long long B, int H, int W, char* why, size_t why_len);
+
 // aug: the augmented layout -- activation tensors placed for the largest pass (pass 0, H x W) and reused by each pass in turn, the
 // prediction / candidate / NMS areas sized for N_aug, then the tap tables of the two scaled passes.
 int layout(aq_engine* e, int B, int H, int W, bool aug = false) {
@@ -226,6 +228,19 @@ int layout(aq_engine* e, int B, int H, int W, bool aug = false) {
         if (rc) return rc;
         AQ_REQUIRE(n_aug < kNmsRowLimit, "augment: %d x %d tiles give %d prediction rows per image; the NMS kernel takes fewer than %d",
                    H, W, n_aug, kNmsRowLimit);
+    }
+    {   // a batch some op cannot run is refused here, before anything is allocated or launched, not by that op's launcher mid-call
+        char why[256];
+        const int bad = plan_unfit_op(e, B, H, W, why, sizeof why);
+        if (bad >= 0) {
+            int lo = 0, hi = B - 1;                      // the largest batch that fits (every guard is monotone in B)
+            while (lo < hi) {
+                const int mid = lo + (hi - lo + 1) / 2;
+                if (plan_unfit_op(e, mid, H, W, nullptr, 0) < 0) lo = mid; else hi = mid - 1;
+            }
+            aq_set_error("batch %d of %d x %d tiles: plan op %d cannot run it (%s); the largest batch that fits is %d", B, H, W, bad, why, lo);
+            return AQ_ERR_INVALID;
+        }
     }
     e->lay_B = 0;                                        // (invalid until the layout below is complete)
     if (aug) memcpy(e->aug, passes, sizeof(passes));
@@ -424,6 +439,81 @@ bool heads_fused(const aq_engine* e) {
     return n_heads == 3;
 }
 
+// The size guards of the launchers, restated per op for a batch of B tiles of H x W: the first op that no kernel it can launch accepts
+// (-1: all fit), with the guard that refuses it in `why`.  A conv whose direct form (tuned table, aq_engine_set_conv_config) refuses the
+// batch falls back to the implicit-GEMM / halo kernel unless the form was forced (run_conv); the fp8 pairs fall back to that bf16 form.
+// Each term is the launcher's own AQ_REQUIRE / *_fits predicate; every one grows with B.
+int plan_unfit_op(const aq_engine* e, long long B, int H, int W, char* why, size_t why_len) {
+    char dummy[8];
+    if (!why) { why = dummy; why_len = sizeof dummy; }
+    const int eb = aq_elem_bytes(e->desc.precision);
+    const aq_engine::Tuned* tt = nullptr;
+    for (const aq_engine::Tuned& t : e->tuned)
+        if (t.H == H && t.W == W) tt = &t;
+    const bool fused = heads_fused(e);
+    auto dims = [&](int t, long long* h, long long* w) { *h = H / e->tensors[t].down; *w = W / e->tensors[t].down; };
+    auto fail = [&](int oi, const char* fmt, long long v) { snprintf(why, why_len, fmt, v); return oi; };
+    if (B > 65535) return fail((int)e->ops.size() - 1, "batch %lld > 65535: the decode and NMS grids", B);
+    for (int oi = 0; oi < (int)e->ops.size(); ++oi) {
+        const aq_op_desc& op = e->ops[oi];
+        long long hs = 0, ws = 0, hd = 0, wd = 0;
+        if (op.src.tensor >= 0) dims(op.src.tensor, &hs, &ws);
+        if (op.dst.tensor >= 0) dims(op.dst.tensor, &hd, &wd);
+        const long long ld_s = op.src.tensor >= 0 ? e->tensors[op.src.tensor].channels : 0;
+        const long long ld_d = op.dst.tensor >= 0 ? e->tensors[op.dst.tensor].channels : 0;
+        switch (op.kind) {
+        case AQ_OP_PREPROCESS:
+            if (B * (H / 2) * (W / 2) >= (1LL << 31)) return fail(oi, "preprocess: %lld output pixels >= 2^31", B * (H / 2) * (W / 2));
+            break;
+        case AQ_OP_STEM:
+            if (B * H * W * 3 >= (1LL << 32) || B * hd * wd >= (1LL << 31)) return fail(oi, "stem: %lld input bytes >= 2^32 or output pixels >= 2^31", B * H * W * 3);
+            break;
+        case AQ_OP_DOWNBLOCK:
+            if (B * hs * ws >= (1LL << 31)) return fail(oi, "down-block: %lld input pixels >= 2^31", B * hs * ws);
+            break;
+        case AQ_OP_BOTTLENECK:
+            if (B * hs * ws >= (1LL << 31)) return fail(oi, "Bottleneck: %lld pixels >= 2^31", B * hs * ws);
+            break;
+        case AQ_OP_SPPF_POOL:
+            if (B * hs * ws * (op.src.channels * eb / 16) >= (1LL << 31))
+                return fail(oi, "SPPF pool: %lld 16-byte groups >= 2^31", B * hs * ws * (op.src.channels * eb / 16));
+            break;
+        case AQ_OP_UPSAMPLE2X:
+            if (B * hs >= 65536) return fail(oi, "upsample2x: %lld input rows >= 65536", B * hs);
+            if (B * 4 * hs * ws * (op.src.channels * eb / 16) >= (1LL << 31))
+                return fail(oi, "upsample2x: %lld 16-byte groups >= 2^31", B * 4 * hs * ws * (op.src.channels * eb / 16));
+            break;
+        case AQ_OP_CONV: {
+            const long long npix = B * hd * wd;
+            if (op.level >= 0 && fused && npix >= (1LL << 30)) return fail(oi, "fused head + decode: %lld pixels >= 2^30", npix);
+            const bool igemm = npix < (1LL << 24);        // aq_launch_conv / aq_launch_conv_halo: the fast-index range
+            const int cfg = e->conv_cfg[oi] >= 0 ? e->conv_cfg[oi] : (tt ? tt->cfg[oi] : -1);
+            const long long ld_r = op.res.tensor >= 0 ? e->tensors[op.res.tensor].channels : 0;
+            bool form = false;
+            switch (cfg & ~AQ_CONV_CFG_ONE_TILE_PER_WG) {
+            case AQ_CONV_CFG_DIRECT1X1: form = npix < (1LL << 31); break;
+            case AQ_CONV_CFG_ASM1X1: form = npix * ld_s * 2 < (1LL << 31) - (1LL << 22) && npix * ld_d * 2 < (1LL << 32) - (1LL << 22); break;
+            case AQ_CONV_CFG_DIRECT3X3S2: form = B * hs * ws < (1LL << 31); break;
+            case AQ_CONV_CFG_PL3X3:
+                form = B * (hs + 1) * (ws + 1) + ws + 2 < (1LL << 23) && npix * ld_d * 2 < (1LL << 31) && npix * ld_r * 2 < (1LL << 31);
+                break;
+            case AQ_CONV_CFG_PL3X3S2:                      // (the query checks the index range; aq_conv3x3_pl_s2 the 31-bit byte offsets)
+                form = B <= INT32_MAX && aq_conv3x3_pl_s2_supported(op.src.channels, op.dst.channels, (int)B, (int)hs, (int)ws) &&
+                       npix * ld_d * 2 < (1LL << 31) && B * hs * ws * ld_s * 2 < (1LL << 31);
+                break;
+            default: form = false;
+            }
+            const bool forced = e->conv_cfg[oi] >= 0 && e->conv_cfg[oi] >= AQ_CONV_CFG_DIRECT1X1 && e->conv_cfg[oi] < AQ_CONV_CFG_ONE_TILE_PER_WG;
+            if (!(form || (!forced && igemm))) return fail(oi, "conv: implicit-GEMM pixel count %lld >= 2^24 and no other form takes it", npix);
+            break;
+        }
+        default:
+            break;
+        }
+    }
+    return -1;
+}
+
 // Does Bottleneck op oi run together with the next op, its C3 block's cv3, as ONE aq_bottleneck_c3tail launch?  Only where the two-launch form
 // runs cv3 on the direct 1x1 kernel -- the fused kernel reproduces that kernel's rounding, so the outputs are the same bits -- and only when
 // the range being run holds both ops (aq_engine_run_ops stepping one op at a time runs, and checks, the two-launch form).
@@ -579,9 +669,11 @@ int run_plan(aq_engine* e, const uint8_t* tiles, int B, int H, int W, void* ws, 
                               op.dst.channels, e->packed[oi].w, e->packed[oi].bias, B, H, W, op.act, prec, stream);
             break;
         case AQ_OP_BOTTLENECK: {
-            note_launch(e, oi, AQ_FAM_BOTTLENECK);
             const TensorPlace& pl = e->place[op.src.tensor];
+            note_launch(e, oi, AQ_FAM_BOTTLENECK, aq_bottleneck_asm_form(op.src.channels, B, pl.h, pl.w, e->tensors[op.src.tensor].channels,
+                                                                         e->tensors[op.dst.tensor].channels));
             if (c3tail_active(e, oi, last, B)) {
+                note_launch(e, oi, AQ_FAM_BOTTLENECK, 1);    // (the tail kernel is an assembly build)
                 // C3 tail: this Bottleneck and cv3 (the next op) as one launch; the Bottleneck's output is not written
                 const aq_op_desc& c = e->ops[oi + 1];
                 rc = aq_bottleneck_c3tail(tptr(e, ws, tiles, op.src.tensor), e->tensors[op.src.tensor].channels, op.src.ch_off,

@@ -185,6 +185,12 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
     if classes is not None or agnostic_nms:
         eng.set_nms_options(agnostic=agnostic_nms, classes=classes)            # [UPSTREAM non_max_suppression(pred, conf, iou, classes, agnostic_nms, max_det)]
     imgsz = check_img_size(list(imgsz), s=int(max(ck.stride)))
+    try:
+        # a batch some kernel cannot run is refused now, not by that kernel in the middle of the sweep; imgsz is the largest geometry the
+        # letterbox produces, and every size guard grows with the tile
+        eng.workspace_bytes(batch_size, *imgsz, augment=augment)
+    except RuntimeError as err:
+        raise SystemExit(f"--batch-size {batch_size}: {err}") from None
     if precision == "fp8":
         # e4m3 activation scales from THIS sweep's imagery and tile size (the engine's default calibrates on synthetic 640-px
         # tiles; real tiles beyond that range would saturate silently).  Rank 0 calibrates on tiles sampled across the whole file list, every

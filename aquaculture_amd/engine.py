@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -67,7 +68,7 @@ EXPORTS = (
     "aq_engine_infer", "aq_engine_run_ops", "aq_engine_candidates", "aq_engine_forward_raw", "aq_engine_tensor_ptr", "aq_engine_profile",
     "aq_engine_op_times", "aq_engine_num_ops", "aq_engine_set_conv_config", "aq_engine_autotune", "aq_engine_set_tuned_table",
     "aq_engine_get_conv_config", "aq_conv_num_configs", "aq_debug_conv_stamp", "aq_debug_mfma_peak",
-    "aq_conv_config_tiles", "aq_pack_conv_weights", "aq_pack_conv_weights_x3", "aq_conv2d", "aq_pack_stem_weights", "aq_stem_conv", "aq_pack_bottleneck_weights", "aq_bottleneck", "aq_bottleneck_c3tail_supported", "aq_pack_bottleneck_c3tail_weights", "aq_bottleneck_c3tail", "aq_pack_downblock_weights", "aq_downblock", "aq_stemdown_supported", "aq_stemdown", "aq_conv1x1_direct_supported", "aq_pack_conv1x1_direct", "aq_conv1x1_direct", "aq_conv1x1_asm_supported", "aq_pack_conv1x1_asm", "aq_conv1x1_asm", "aq_nms_opts", "aq_engine_set_nms_options",
+    "aq_conv_config_tiles", "aq_pack_conv_weights", "aq_pack_conv_weights_x3", "aq_conv2d", "aq_pack_stem_weights", "aq_stem_conv", "aq_pack_bottleneck_weights", "aq_bottleneck", "aq_bottleneck_asm_form", "aq_bottleneck_c3tail_supported", "aq_pack_bottleneck_c3tail_weights", "aq_bottleneck_c3tail", "aq_pack_downblock_weights", "aq_downblock", "aq_stemdown_supported", "aq_stemdown", "aq_conv1x1_direct_supported", "aq_pack_conv1x1_direct", "aq_conv1x1_direct", "aq_conv1x1_asm_supported", "aq_pack_conv1x1_asm", "aq_conv1x1_asm", "aq_nms_opts", "aq_engine_set_nms_options",
     "aq_conv3x3s2_direct_supported", "aq_pack_conv3x3s2_direct", "aq_conv3x3s2_direct",
     "aq_conv3x3_pl_supported", "aq_conv3x3_pl_asm_family", "aq_pack_conv3x3_pl", "aq_conv3x3_pl", "aq_conv3x3_pl_s2_supported", "aq_pack_conv3x3_pl_s2", "aq_conv3x3_pl_s2", "aq_jpeg_scratch_bytes", "aq_jpeg_idct_rgb", "aq_f32_to_e4m3", "aq_conv1x1_direct_f8out", "aq_absmax_bf16", "aq_engine_calibrate_amax", "aq_engine_set_fp8_scales", "aq_engine_last_launch", "aq_conv3x3_pl_f8_supported", "aq_pack_conv3x3_pl_f8", "aq_conv3x3_pl_f8", "aq_conv3x3_pl_w8_supported", "aq_pack_conv3x3_pl_w8", "aq_conv3x3_pl_w8", "aq_head_decode_supported", "aq_pack_head_weights", "aq_head_decode", "aq_head_counts_gather", "aq_preprocess_s2d", "aq_sppf_pool",
     "aq_upsample2x", "aq_letterbox_u8", "aq_letterbox_tiles_u8", "aq_format_label_rows", "aq_detect_decode", "aq_nms_scratch_bytes", "aq_nms", "aq_jpeg_huffman_decode", "aq_write_label_files",
@@ -132,6 +133,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_stem_conv.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.aq_pack_bottleneck_weights.argtypes = [C.POINTER(f32), C.POINTER(f32), i32, vp, C.POINTER(sz), vp]
     lib.aq_bottleneck.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]
+    lib.aq_bottleneck_asm_form.argtypes = [i32] * 6
     lib.aq_bottleneck_c3tail_supported.argtypes = [i32, i32, i32, i32, i32, i32]
     lib.aq_pack_bottleneck_c3tail_weights.argtypes = [C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), vp, C.POINTER(sz), vp]
     lib.aq_bottleneck_c3tail.argtypes = [vp, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp]
@@ -347,14 +349,27 @@ class Engine:
     # ---- workspace ----
     def workspace(self, B: int, H: int, W: int, slot: int = 0, augment: bool = False) -> torch.Tensor:
         """Workspace of in-flight batch ``slot``: batches issued on different streams must not share one."""
-        n = C.c_size_t()
-        _check((self.lib.aq_engine_workspace_bytes_augment if augment else self.lib.aq_engine_workspace_bytes)(self.handle, B, H, W, C.byref(n)))
+        n = self.workspace_bytes(B, H, W, augment)
         ws = self._slots.get(slot)
-        if ws is None or ws.numel() < n.value:
+        if ws is None or ws.numel() < n:
             self._slots.pop(slot, None)
-            ws = self._slots[slot] = torch.empty(n.value, dtype=torch.uint8, device=self.device)
+            ws = self._slots[slot] = torch.empty(n, dtype=torch.uint8, device=self.device)
         self._ws = ws
         return ws
+
+    def workspace_bytes(self, B: int, H: int, W: int, augment: bool = False) -> int:
+        """Workspace bytes for batches up to ``B`` of H x W tiles, allocating nothing.  A batch some op of the plan cannot run raises
+        RuntimeError naming the op (plan index and name) and the largest batch that fits."""
+        n = C.c_size_t()
+        try:
+            _check((self.lib.aq_engine_workspace_bytes_augment if augment else self.lib.aq_engine_workspace_bytes)(self.handle, B, H, W, C.byref(n)))
+        except RuntimeError as err:
+            m = re.search(r"plan op (\d+)", str(err))
+            if m is None:
+                raise
+            i = int(m.group(1))
+            raise RuntimeError(str(err).replace(m.group(0), f"{m.group(0)} ({self.plan.ops[i].name})", 1)) from None
+        return n.value
 
     def num_candidates(self, H: int, W: int, augment: bool = False) -> int:
         """Rows per image of the prediction: one pass, or the three clipped passes of --augment (augment.geometry)."""

@@ -103,7 +103,9 @@ int aq_version(void);
 /* Copies + packs the weights to the device (the only allocation the engine ever does). */
 int aq_engine_create(const aq_model_desc* desc, int device_ordinal, aq_engine** out);
 void aq_engine_destroy(aq_engine* e);
-/* Bytes of caller-provided workspace needed for batches up to max_batch of HxW tiles. */
+/* Bytes of caller-provided workspace needed for batches up to max_batch of HxW tiles.  Refuses (AQ_ERR_INVALID, nothing allocated) a batch
+ * that some plan op cannot run -- a kernel's size guard with no fallback form, checked with the launchers' own predicates -- with a
+ * message naming the op ("plan op N") and the largest batch that fits. */
 int aq_engine_workspace_bytes(aq_engine* e, int max_batch, int H, int W, size_t* bytes);
 /* tiles_dev: uint8 [B][H][W][3] RGB.  dets_dev: [B][max_det].  counts_dev: [B].
  * Replaces `pred = model(im); pred = non_max_suppression(pred, conf, iou, None, False, max_det)`. */
@@ -159,7 +161,7 @@ enum {
     AQ_FAM_DIRECT1X1 = 6,
     AQ_FAM_DIRECT1X1_F8OUT = 7,    /* producer of an fp8 pair: writes e4m3 codes */
     AQ_FAM_DIRECT3X3S2 = 8,
-    AQ_FAM_BOTTLENECK = 9,
+    AQ_FAM_BOTTLENECK = 9,         /* *cfg = 1: generated-assembly build (or the C3 tail launch), 0: HIP-source build (aq_bottleneck_asm_form) */
     AQ_FAM_DOWNBLOCK = 10,
     AQ_FAM_STEM = 11,
     AQ_FAM_HEAD_DECODE = 12,
@@ -215,6 +217,10 @@ int aq_stem_conv(const uint8_t* tiles_dev, void* out_dev, int out_ld, int out_ch
 int aq_pack_bottleneck_weights(const float* w1_host, const float* w2_host, int C, void* packed_dev, size_t* bytes, void* stream);
 int aq_bottleneck(const void* in_dev, int in_ld, int in_choff, void* out_dev, int out_ld, int out_choff, int C,
                   const void* packed_w_dev, const float* bias_dev, int B, int H, int W, int shortcut, void* stream);
+/* Which build aq_bottleneck runs for this launch: 1 = generated assembly (C = 48 or 96; 16 x 16 / 8 x 16 tiles, 32-bit buffer offsets:
+ * input under 2^30 bytes, output under 2^31), 0 = the HIP-source kernel (every other launch: AQ_BTL_ASM=0, AQ_BTL96_ASM=0, larger
+ * batches, images narrower than two tiles).  Both compute the same operation; they need not round alike. */
+int aq_bottleneck_asm_form(int C, int B, int H, int W, int in_ld, int out_ld);
 
 /* A C3 block's last Bottleneck (C = 48) with the block's cv3 1x1 in its epilogue (AQ_OP_BOTTLENECK followed by its AQ_OP_CONV; engines do
  * this on their own, AQ_C3TAIL=0 turns it off): out = SiLU(W3 [Bottleneck(x) | cat] + b3), 96 channels; the Bottleneck's output is not

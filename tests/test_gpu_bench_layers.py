@@ -61,6 +61,11 @@ CONFIGS = {
     "table_bf16_b128": Entry("yolov5m", "bf16", 128, 640, [0, 127], "shipped table", 101, "bench.py --batch 128"),
     "table_fp8_b64": Entry("yolov5m", "fp8", 64, 640, [0, 63], "shipped table", 37, "bench.py --precision fp8"),
     "configs4": Entry("yolov5x", "bf16", 16, 1280, [0, 7, 8, 15], "shipped table", 5, "bench.py --variant yolov5x --size 1280 --batch 16"),
+    # the engine's batch limits, on heuristic tile shapes: fp32 (detect.py's default precision) with out0 past 2^31 bytes (image 109 holds
+    # byte 2^31); bf16 across both points where Bottleneck launches leave the assembly builds (219: model.2.m.0, 437: the others at 2^30
+    # input bytes), so the ragged batch (217) runs the assembly builds and the full batch the HIP-source ones
+    "fp32_b128": Entry("yolov5m", "fp32", 128, 640, [0, 109, 127], None, 101, "detect.py --batch-size 128"),
+    "bf16_b448": Entry("yolov5m", "bf16", 448, 640, [0, 218, 219, 436, 437, 447], None, 217, "detect.py --half --batch-size 448, untuned"),
 }
 
 # conv tolerances (rel, abs) of the kernels' own parity tests: bf16 storage; fp32 (tests/test_gpu_conv.py); f16x3 = 4 x fp32
@@ -149,6 +154,15 @@ FAMILIES = {
         ('direct1x1_f8out', 1), ('pl3x3_f8', 1), ('direct1x1_f8out', 1), ('pl3x3_f8', 1), ('direct1x1', 1), ('pl3x3s2', 1),
         ('asm1x1', 1), ('direct1x1_f8out', 1), ('pl3x3_f8', 1), ('direct1x1_f8out', 1), ('pl3x3_f8', 1), ('asm1x1', 1),
         ('head_decode', 3), ('none', 2),
+    ],
+    "fp32_b128": [
+        ('stem', 1), ('igemm_or_halo', 41), ('none', 1), ('igemm_or_halo', 2), ('none', 1), ('igemm_or_halo', 7), ('none', 1),
+        ('igemm_or_halo', 23), ('none', 2),
+    ],
+    "bf16_b448": [
+        ('stem', 1), ('downblock', 1), ('bottleneck', 2), ('igemm_or_halo', 3), ('bottleneck', 4), ('igemm_or_halo', 24), ('none', 1),
+        ('igemm_or_halo', 2), ('none', 1), ('igemm_or_halo', 7), ('none', 1), ('igemm_or_halo', 1), ('bottleneck', 2),
+        ('igemm_or_halo', 15), ('head_decode', 3), ('none', 2),
     ],
     "configs4": [
         ('none', 1), ('igemm_or_halo', 70), ('none', 1), ('igemm_or_halo', 2), ('none', 1), ('igemm_or_halo', 11), ('none', 1),
@@ -737,6 +751,29 @@ def test_ragged_last_batch(setup):
     print(f"{setup.name}: {n_same} ops bit-identical to the full batch on images [0, {Bp}); total {time.perf_counter() - t0:.1f} s")
     excluded = [i for i in fullB if i in changed or ups[i] & set(changed)]
     assert n_same + len(excluded) == len(fullB) and (n_same > 0 or changed)
+
+
+def test_bottleneck_form_follows_its_guard(setup):
+    """Which build each Bottleneck launch ran (aq_engine_last_launch's cfg: 1 = generated assembly, 0 = HIP source) at the full and the
+    ragged batch equals the assembly builds' guard (32-bit offsets: input under 2^30 bytes, output under 2^31), so the switch points --
+    bf16_b448: model.2.m.0 at 219, the other assembly-eligible launches at 437 -- are asserted, not inferred from the family list."""
+    from oracle.guards import btl_asm_fits
+    eng, plan = setup.eng, setup.eng.plan
+    ops = [(i, o) for i, o in enumerate(plan.ops) if o.kind == OP_BOTTLENECK]
+    forms = {}
+    for Bx in (setup.B, setup.entry.ragged):
+        eng.infer(setup.x[:Bx], CONF, IOU, MAX_DET)
+        torch.cuda.synchronize()
+        fams = eng.last_launches()
+        for i, o in ops:
+            h = setup.size // plan.tensors[o.src.tensor].down
+            want = int(btl_asm_fits(o.src.channels, Bx, h, h, plan.tensors[o.src.tensor].channels, plan.tensors[o.dst.tensor].channels))
+            assert fams[i] == ("bottleneck", want), (o.name, Bx, fams[i], want)
+            forms[(o.name, Bx)] = want
+    print(f"\n{setup.name}: Bottleneck forms (1 = assembly) {forms}")
+    if setup.name == "bf16_b448":
+        assert forms[("model.2.m.0", 448)] == 0 and forms[("model.2.m.1", 448)] == 0 and forms[("model.4.m.1", 448)] == 1
+        assert all(forms[(o.name, 217)] == 1 for _, o in ops)
 
 
 def test_run_ops_pieces_equal_infer(setup):

@@ -112,8 +112,8 @@ def test_every_shipped_tuned_table_has_a_layer_check():
         covered[key] = ids[0]
     print(covered)
     assert sorted(c for c, e in L.CONFIGS.items() if e.tuning == "shipped table") == sorted(covered.values())
-    assert [c for c, e in L.CONFIGS.items() if e.tuning != "shipped table"] == ["parity_fp32"]
-    assert L.CONFIGS["parity_fp32"].tuning is None
+    assert [c for c, e in L.CONFIGS.items() if e.tuning != "shipped table"] == ["parity_fp32", "fp32_b128", "bf16_b448"]
+    assert L.CONFIGS["parity_fp32"].tuning is None and L.CONFIGS["fp32_b128"].tuning is None and L.CONFIGS["bf16_b448"].tuning is None
     assert set(L.FAMILIES) == set(L.CONFIGS)                   # every entry pins the kernel families its ops launch
     for cid, e in L.CONFIGS.items():
         assert 0 < e.ragged < e.batch and e.ragged % 2 == 1, cid
