@@ -35,7 +35,8 @@ SOURCES = [
     ("augment.hip", ["-ffp-contract=off"]),      # --augment: pass geometry, bilinear taps in PyTorch's CPU fp32 order, scaled preprocess
     ("jpeg_idct.hip", []),                       # device half of the split JPEG decode (IDCT, chroma upsampling, colour conversion)
     ("jpeg_huff.hip", []),                       # GPU entropy decode (round 4): the Huffman stage, one lane per restart segment
-    ("crop_jpeg.hip", []),                       # --save-crop: the encoder's pixel half (colour conversion, FDCT, quantisation); Huffman coding and files on the host
+    ("crop_jpeg.hip", []),                       # --save-crop: the encoder's pixel half (colour conversion, FDCT, quantisation); Huffman coding and files on the host; whole frames in 4:2:0 for the annotated images
+    ("annotate.hip", []),                        # boxes and labels drawn on a copy of the batch's images (upstream's Pillow-branch box_label)
     ("engine.cpp", ["-x", "hip"]),
 ]
 # -packed-fp32-ops: no v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 in compiled kernels.  The SiLU epilogues run beside other waves' MFMAs (two

@@ -11,6 +11,9 @@
 // Layout: crop i covers block positions [crops[i].block, crops[i].block + ceil(w / 8) ceil(h / 8)) of the coefficient arena, raster order;
 // a block position holds 3 x 64 int16 (Y, Cb, Cr), each block in zigzag order -- the order the entropy coder walks.
 // Kernel: one thread per (block position, component); the three threads of a position read the same 192 bytes of pixels.
+//
+// Whole frames (the annotated images of detect.py without --nosave) go through a second kernel further down: 4:2:0, what cv2.imwrite's
+// libjpeg writes for a .jpg, sharing fdct8, the tables and the host coder (a sampling argument) with the crops.
 #include "aq_common.h"
 #include <errno.h>
 #include <stdio.h>
@@ -143,6 +146,139 @@ __global__ __launch_bounds__(256) void crop_jpeg_kernel(const CropParams p) {
     }
 }
 
+
+// ---- whole frames, 4:2:0 (annotated images; cv2.imwrite's libjpeg defaults) ----
+//
+// One wave per 16 x 16 MCU, four MCUs per workgroup.  The wave's 64 lanes read the MCU's 256 pixels once (four neighbours each), convert them
+// and keep Y and the full-resolution Cb / Cr in LDS; h2v2_downsample (jcsample.c) makes the two chroma blocks there; 48 lanes run the row
+// pass and the column pass of the six blocks (one row or column each) through LDS, quantise into zigzag order, and 48 lanes store the MCU's
+// 768 bytes, 16 each.  What lies outside the image: pixels are replicated to the right and down (expand_right_edge, expand_bottom_edge),
+// the chroma rows below the last downsampled row repeat THAT row, and a Y block wholly outside the component's ceil(w / 8) x ceil(h / 8)
+// blocks is libjpeg's dummy block (jccoefct.c compress_data: all zero but the DC of the block before it in the MCU).
+
+struct FrameTab { unsigned short div[2][64]; unsigned char zz[64]; };   // natural order: quantisation divisor (q << 3), zigzag position
+constexpr FrameTab make_frame_tab() {
+    FrameTab t{};
+    for (int z = 0; z < 64; ++z) t.zz[kNatural[z]] = (unsigned char)z;
+    for (int n = 0; n < 64; ++n) { t.div[0][n] = (unsigned short)(8 * q95(kStdLuma[n])); t.div[1][n] = (unsigned short)(8 * q95(kStdChroma[n])); }
+    return t;
+}
+__constant__ FrameTab kFrameTab = make_frame_tab();
+
+struct FrameParams {
+    const unsigned char* img;
+    long long img_bytes;
+    const aq_frame* frames;
+    int n_frames;
+    int n_mcus;                   // of this piece
+    short* coef;                  // MCU frames[0].mcu of the batch is arena MCU 0
+};
+
+__global__ __launch_bounds__(256) void frame_jpeg_kernel(const FrameParams p) {
+    __shared__ int s_blk[4][6][8][9];                         // level-shifted samples, then row-pass values (rows padded: column reads spread over banks)
+    __shared__ unsigned char s_c[4][2][16][16];               // Cb, Cr at full resolution
+    __shared__ __attribute__((aligned(16))) short s_q[4][6][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int mcu0 = p.frames[0].mcu;
+    const int groups = (p.n_mcus + 3) >> 2;
+    for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {          // (the same trip count for all four waves: they share the barriers)
+        const int m = grp * 4 + wave;
+        const bool live = m < p.n_mcus;
+        const int g = mcu0 + m;
+        int lo = 0, hi = p.n_frames - 1;                      // the frame that holds MCU g: the last one that starts at or before it
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (p.frames[mid].mcu <= g) lo = mid; else hi = mid - 1;
+        }
+        const aq_frame f = p.frames[lo];
+        const int w = f.w, h = f.h, mw = (w + 15) >> 4, k = g - f.mcu, my = k / max(mw, 1), mx = k - my * mw;
+        const bool ok = live && w > 0 && h > 0 && f.base >= 0 && f.pitch >= 3LL * w && my < ((h + 15) >> 4) &&
+                        f.base + (long long)(h - 1) * f.pitch + 3LL * w <= p.img_bytes;
+        if (ok) {
+            // rgb_ycc_convert (jccolor.c): lane = (row, four pixels)
+            const int r = lane >> 2, c0 = (lane & 3) * 4;
+            const int y = min(16 * my + r, h - 1), x0 = 16 * mx + c0;
+            const unsigned char* row = p.img + f.base + (long long)y * f.pitch;
+            unsigned char px[12];
+            if (x0 + 3 < w && (((uintptr_t)(row + 3 * x0)) & 3) == 0) {
+                const uint3 v = *(const uint3*)(row + 3 * x0);
+                const unsigned u[3] = {v.x, v.y, v.z};
+#pragma unroll
+                for (int i = 0; i < 12; ++i) px[i] = (unsigned char)(u[i >> 2] >> (8 * (i & 3)));
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const unsigned char* q = row + 3 * min(x0 + e, w - 1);
+                    px[3 * e] = q[0]; px[3 * e + 1] = q[1]; px[3 * e + 2] = q[2];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int R = px[3 * e], G = px[3 * e + 1], B = px[3 * e + 2], c = c0 + e;
+                s_blk[wave][(r >> 3) * 2 + (c >> 3)][r & 7][c & 7] = ((19595 * R + 38470 * G + 7471 * B + 32768) >> 16) - 128;
+                s_c[wave][0][r][c] = (unsigned char)((-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16);
+                s_c[wave][1][r][c] = (unsigned char)((32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16);
+            }
+        }
+        __syncthreads();
+        if (ok) {
+            // h2v2_downsample: lane = (chroma row, chroma column); bias 1, 2, 1, 2 ... along the row
+            const int cy = lane >> 3, cx = lane & 7;
+            const int cyl = min(8 * my + cy, ((h + 1) >> 1) - 1) - 8 * my;      // below the last downsampled row: that row again
+            const int bias = 1 + (cx & 1);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const unsigned char* a = &s_c[wave][c][2 * cyl][2 * cx];
+                s_blk[wave][4 + c][cy][cx] = ((a[0] + a[1] + a[16] + a[17] + bias) >> 2) - 128;
+            }
+        }
+        __syncthreads();
+        const int b = lane >> 3, i = lane & 7;
+        if (ok && lane < 48) {                                // rows
+            int v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = s_blk[wave][b][i][e];
+            fdct8<1, false>(v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s_blk[wave][b][i][e] = v[e];
+        }
+        __syncthreads();
+        if (ok && lane < 48) {                                // columns, quantisation (divisor q << 3, half away from zero), zigzag order
+            int v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = s_blk[wave][b][e][i];
+            fdct8<1, true>(v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int n = 8 * e + i, div = kFrameTab.div[b >= 4][n];
+                const int a = ((v[e] < 0 ? -v[e] : v[e]) + (div >> 1)) / div;
+                s_q[wave][b][kFrameTab.zz[n]] = (short)(v[e] < 0 ? -a : a);
+            }
+        }
+        __syncthreads();
+        // dummy blocks of the Y component
+        const int wib = (w + 7) >> 3, hib = (h + 7) >> 3;
+        const bool row1 = 2 * my + 1 < hib, col1 = 2 * mx + 1 < wib;
+        if (ok) {
+            if (!col1) s_q[wave][1][lane] = 0;
+            if (!row1 || !col1) s_q[wave][3][lane] = 0;
+            if (!row1) s_q[wave][2][lane] = 0;
+        }
+        __syncthreads();
+        if (ok && lane == 0) {
+            if (!col1) s_q[wave][1][0] = s_q[wave][0][0];
+            if (!row1) { s_q[wave][2][0] = s_q[wave][1][0]; s_q[wave][3][0] = s_q[wave][1][0]; }
+            else if (!col1) s_q[wave][3][0] = s_q[wave][2][0];
+        }
+        __syncthreads();
+        if (live && lane < 48) {                              // (a frame the launcher would have refused: zeros, never a read outside the images)
+            const uint4 v = ok ? *(const uint4*)(&s_q[wave][0][0] + 8 * lane) : make_uint4(0, 0, 0, 0);
+            *(uint4*)(p.coef + (long long)m * 384 + 8 * lane) = v;
+        }
+        __syncthreads();
+    }
+}
+
 // ---- host half: Huffman coding and the JFIF stream (jchuff.c, jcmarker.c) ----
 
 // Annex K.3 tables: code counts per length 1..16, then the symbols
@@ -213,7 +349,8 @@ struct BitWriter {
 
 inline int nbits(int v) { return v ? 32 - __builtin_clz((unsigned)v) : 0; }
 
-void marker_header(std::vector<unsigned char>& o, int w, int h) {
+// h2v2: 4:2:0 (Y sampled 2 x 2) instead of 4:4:4
+void marker_header(std::vector<unsigned char>& o, int w, int h, bool h2v2) {
     auto u8 = [&](int v) { o.push_back((unsigned char)v); };
     auto u16 = [&](int v) { u8(v >> 8); u8(v & 255); };
     u16(0xFFD8);                                              // SOI
@@ -224,8 +361,8 @@ void marker_header(std::vector<unsigned char>& o, int w, int h) {
         u16(0xFFDB); u16(67); u8(t);
         for (int z = 0; z < 64; ++z) u8(q95(t ? kStdChroma[kNatural[z]] : kStdLuma[kNatural[z]]));
     }
-    u16(0xFFC0); u16(17); u8(8); u16(h); u16(w); u8(3);       // SOF0: components 1, 2, 3, 1x1 sampling, tables 0 / 1 / 1
-    for (int c = 0; c < 3; ++c) { u8(c + 1); u8(0x11); u8(c ? 1 : 0); }
+    u16(0xFFC0); u16(17); u8(8); u16(h); u16(w); u8(3);       // SOF0: components 1, 2, 3, sampling 1x1 each (or 2x2 / 1x1 / 1x1), tables 0 / 1 / 1
+    for (int c = 0; c < 3; ++c) { u8(c + 1); u8(h2v2 && c == 0 ? 0x22 : 0x11); u8(c ? 1 : 0); }
     const unsigned char* bits[4] = {kDcLumaBits, kAcLumaBits, kDcChromaBits, kAcChromaBits};
     const unsigned char* vals[4] = {kDcVals, kAcLumaVals, kDcVals, kAcChromaVals};
     const int cls[4] = {0x00, 0x10, 0x01, 0x11};
@@ -241,36 +378,41 @@ void marker_header(std::vector<unsigned char>& o, int w, int h) {
     u8(0); u8(63); u8(0);
 }
 
-// One crop: coef = its block positions (raster order, Y / Cb / Cr, zigzag) -> the whole file
-void encode_jpeg(const int16_t* coef, int w, int h, std::vector<unsigned char>& o) {
+// One block: DC difference, AC run lengths (jchuff.c encode_one_block)
+inline void encode_block(BitWriter& bw, const int16_t* blk, int& last_dc, const HuffCode& dc, const HuffCode& ac) {
+    int diff = blk[0] - last_dc;
+    last_dc = blk[0];
+    int nb = nbits(diff < 0 ? -diff : diff);
+    bw.put(dc.code[nb], dc.size[nb]);
+    if (nb) bw.put((unsigned)(diff < 0 ? diff - 1 : diff), nb);
+    int run = 0;
+    for (int k = 1; k < 64; ++k) {
+        const int v = blk[k];
+        if (v == 0) { ++run; continue; }
+        while (run > 15) { bw.put(ac.code[0xF0], ac.size[0xF0]); run -= 16; }   // ZRL
+        nb = nbits(v < 0 ? -v : v);
+        const int sym = (run << 4) + nb;
+        bw.put(ac.code[sym], ac.size[sym]);
+        bw.put((unsigned)(v < 0 ? v - 1 : v), nb);
+        run = 0;
+    }
+    if (run > 0) bw.put(ac.code[0], ac.size[0]);             // EOB
+}
+
+// One image -> the whole file.  4:4:4 (a crop): coef = its block positions, raster order, Y / Cb / Cr each.  h2v2 (a frame): coef = its
+// 16 x 16 MCUs, raster order, Y00 Y01 Y10 Y11 Cb Cr each: the interleaved scan's own order.  Blocks in zigzag order; DC prediction per component.
+void encode_jpeg(const int16_t* coef, int w, int h, std::vector<unsigned char>& o, bool h2v2 = false) {
     o.clear();
-    const long long nblk = (long long)((w + 7) / 8) * ((h + 7) / 8);
-    o.reserve(700 + (size_t)nblk * 96);
-    marker_header(o, w, h);
+    const int unit = h2v2 ? 16 : 8, per = h2v2 ? 6 : 3;
+    const long long n = (long long)((w + unit - 1) / unit) * ((h + unit - 1) / unit);
+    o.reserve(700 + (size_t)n * per * 32);
+    marker_header(o, w, h, h2v2);
     BitWriter bw(o);
     int last_dc[3] = {0, 0, 0};
-    for (long long b = 0; b < nblk; ++b) {
-        for (int c = 0; c < 3; ++c) {
-            const int16_t* blk = coef + (b * 3 + c) * 64;
-            const HuffCode& dc = kDc[c ? 1 : 0];
-            const HuffCode& ac = kAc[c ? 1 : 0];
-            int diff = blk[0] - last_dc[c];
-            last_dc[c] = blk[0];
-            int nb = nbits(diff < 0 ? -diff : diff);
-            bw.put(dc.code[nb], dc.size[nb]);
-            if (nb) bw.put((unsigned)(diff < 0 ? diff - 1 : diff), nb);
-            int run = 0;
-            for (int k = 1; k < 64; ++k) {
-                const int v = blk[k];
-                if (v == 0) { ++run; continue; }
-                while (run > 15) { bw.put(ac.code[0xF0], ac.size[0xF0]); run -= 16; }   // ZRL
-                nb = nbits(v < 0 ? -v : v);
-                const int sym = (run << 4) + nb;
-                bw.put(ac.code[sym], ac.size[sym]);
-                bw.put((unsigned)(v < 0 ? v - 1 : v), nb);
-                run = 0;
-            }
-            if (run > 0) bw.put(ac.code[0], ac.size[0]);     // EOB
+    for (long long u = 0; u < n; ++u) {
+        for (int b = 0; b < per; ++b) {
+            const int c = h2v2 ? (b < 4 ? 0 : b - 3) : b;
+            encode_block(bw, coef + (u * per + b) * 64, last_dc[c], kDc[c ? 1 : 0], kAc[c ? 1 : 0]);
         }
     }
     bw.flush();
@@ -290,6 +432,36 @@ bool make_parents(const std::string& dir, const char* rel) {
         }
     }
     return true;
+}
+
+// n files on threads of their own: encode(i, bytes) -> <dir>/<rel_paths[i]>, truncating; the directories on the way are created.  n_threads
+// threads take the files in turn; do_fsync: fsync every file before closing it.  Returns n, or -1 - i when file i could not be written.
+template <class Encode>
+long write_files(const char* dir, const char* const* rel_paths, int n, int n_threads, int do_fsync, Encode encode) {
+    const std::string root(dir);
+    std::atomic<int> next{0};
+    std::atomic<long> failed{-1};
+    auto work = [&]() {
+        std::vector<unsigned char> o;
+        std::string path;
+        for (int i; (i = next.fetch_add(1)) < n && failed.load() < 0;) {
+            if (!encode(i, o)) { failed = i; return; }
+            path.assign(root);
+            path += '/';
+            path += rel_paths[i];
+            FILE* f = fopen(path.c_str(), "wb");
+            if (!f && errno == ENOENT && make_parents(root, rel_paths[i])) f = fopen(path.c_str(), "wb");
+            if (!f) { failed = i; return; }
+            const bool ok = fwrite(o.data(), 1, o.size(), f) == o.size() && fflush(f) == 0 && (!do_fsync || fsync(fileno(f)) == 0);
+            if (fclose(f) != 0 || !ok) { failed = i; return; }
+        }
+    };
+    const int nt = n_threads < 1 ? 1 : (n_threads > 64 ? 64 : (n_threads > n ? (n > 0 ? n : 1) : n_threads));
+    std::vector<std::thread> ts;
+    for (int t = 1; t < nt; ++t) ts.emplace_back(work);
+    work();
+    for (auto& t : ts) t.join();
+    return failed.load() >= 0 ? -1 - failed.load() : (long)n;
 }
 
 }  // namespace
@@ -329,31 +501,63 @@ extern "C" long aq_crop_jpeg_bytes(const int16_t* coef, int w, int h, uint8_t* b
 extern "C" long aq_write_crop_files(const char* dir, const char* const* rel_paths, const int16_t* coef, const aq_crop* crops, int n_crops,
                                     int n_threads, int do_fsync) {
     if (!dir || !rel_paths || !coef || !crops || n_crops < 0) return -1;
-    const std::string root(dir);
-    std::atomic<int> next{0};
-    std::atomic<long> failed{-1};
-    auto work = [&]() {
-        std::vector<unsigned char> o;
-        std::string path;
-        for (int i; (i = next.fetch_add(1)) < n_crops && failed.load() < 0;) {
-            const aq_crop& c = crops[i];
-            const int w = c.x2 - c.x1, h = c.y2 - c.y1;
-            if (w <= 0 || h <= 0 || w > 65535 || h > 65535) { failed = i; return; }
-            encode_jpeg(coef + (size_t)c.block * 192, w, h, o);
-            path.assign(root);
-            path += '/';
-            path += rel_paths[i];
-            FILE* f = fopen(path.c_str(), "wb");
-            if (!f && errno == ENOENT && make_parents(root, rel_paths[i])) f = fopen(path.c_str(), "wb");
-            if (!f) { failed = i; return; }
-            const bool ok = fwrite(o.data(), 1, o.size(), f) == o.size() && fflush(f) == 0 && (!do_fsync || fsync(fileno(f)) == 0);
-            if (fclose(f) != 0 || !ok) { failed = i; return; }
-        }
-    };
-    const int nt = n_threads < 1 ? 1 : (n_threads > 64 ? 64 : (n_threads > n_crops ? (n_crops > 0 ? n_crops : 1) : n_threads));
-    std::vector<std::thread> ts;
-    for (int t = 1; t < nt; ++t) ts.emplace_back(work);
-    work();
-    for (auto& t : ts) t.join();
-    return failed.load() >= 0 ? -1 - failed.load() : (long)n_crops;
+    return write_files(dir, rel_paths, n_crops, n_threads, do_fsync, [&](int i, std::vector<unsigned char>& o) {
+        const aq_crop& c = crops[i];
+        const int w = c.x2 - c.x1, h = c.y2 - c.y1;
+        if (w <= 0 || h <= 0 || w > 65535 || h > 65535) return false;
+        encode_jpeg(coef + (size_t)c.block * 192, w, h, o);
+        return true;
+    });
+}
+// One piece of a batch's frames, 4:2:0: the MCUs of frames_dev[0 .. n_frames) into coef_dev (n_mcus MCUs of 6 x 64 int16, the first frame's
+// first MCU at coef_dev).  frames: sorted by mcu, back to back; frames_host = the same table in host memory, checked here: a frame that
+// leaves [images_dev, images_dev + image_bytes) is refused before anything is launched.
+extern "C" int aq_image_jpeg_coefs(const uint8_t* images_dev, long long image_bytes, const aq_frame* frames_dev, const aq_frame* frames_host,
+                                   int n_frames, int n_mcus, int16_t* coef_dev, void* stream) {
+    AQ_REQUIRE(images_dev && frames_dev && frames_host && coef_dev, "image_jpeg_coefs: null pointer");
+    AQ_REQUIRE(n_frames > 0 && n_mcus > 0 && image_bytes > 0, "image_jpeg_coefs: bad sizes (%d frames, %d MCUs)", n_frames, n_mcus);
+    AQ_REQUIRE(((uintptr_t)coef_dev & 15) == 0 && ((uintptr_t)frames_dev & 7) == 0, "image_jpeg_coefs: unaligned buffer");
+    long long next = frames_host[0].mcu;
+    for (int i = 0; i < n_frames; ++i) {
+        const aq_frame& f = frames_host[i];
+        AQ_REQUIRE(f.w > 0 && f.h > 0 && f.w <= 65535 && f.h <= 65535 && f.base >= 0 && f.pitch >= 3LL * f.w &&
+                   f.base + (long long)(f.h - 1) * f.pitch + 3LL * f.w <= image_bytes,
+                   "image_jpeg_coefs: frame %d (%d x %d, pitch %d, at byte %lld) is empty or leaves its buffer of %lld bytes", i, f.w, f.h, f.pitch,
+                   (long long)f.base, image_bytes);
+        AQ_REQUIRE(f.mcu == next, "image_jpeg_coefs: frame %d starts at MCU %d, not where frame %d ends (%lld)", i, f.mcu, i - 1, next);
+        next += (long long)((f.w + 15) / 16) * ((f.h + 15) / 16);
+    }
+    AQ_REQUIRE(next - frames_host[0].mcu == n_mcus, "image_jpeg_coefs: the frames hold %lld MCUs, not %d", next - frames_host[0].mcu, n_mcus);
+    int cus = 0;
+    AQ_CHECK_HIP(aq_cus(&cus));
+    FrameParams p;
+    p.img = images_dev; p.img_bytes = image_bytes; p.frames = frames_dev; p.n_frames = n_frames; p.n_mcus = n_mcus; p.coef = (short*)coef_dev;
+    const long long groups = ((long long)n_mcus + 3) / 4;
+    const unsigned grid = (unsigned)(groups < 32LL * cus ? groups : 32LL * cus);
+    hipLaunchKernelGGL(frame_jpeg_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+    AQ_CHECK_HIP(hipGetLastError());
+    return AQ_OK;
+}
+
+// The JPEG file of one w x h frame, 4:2:0, from its MCUs; bytes written, or -(bytes needed) when buflen is too small.
+extern "C" long aq_image_jpeg_bytes(const int16_t* coef, int w, int h, uint8_t* buf, size_t buflen) {
+    if (!coef || w <= 0 || h <= 0 || w > 65535 || h > 65535) return 0;
+    std::vector<unsigned char> o;
+    encode_jpeg(coef, w, h, o, true);
+    if (!buf || o.size() > buflen) return -(long)o.size();
+    memcpy(buf, o.data(), o.size());
+    return (long)o.size();
+}
+
+// A batch of frame files: frame i (coefficients from MCU frames[i].mcu of coef) -> <dir>/<rel_paths[i]>, as aq_write_crop_files writes crops.
+// Returns the number of files written, or -1 - i when frame i could not be written.
+extern "C" long aq_write_image_files(const char* dir, const char* const* rel_paths, const int16_t* coef, const aq_frame* frames, int n_frames,
+                                     int n_threads, int do_fsync) {
+    if (!dir || !rel_paths || !coef || !frames || n_frames < 0) return -1;
+    return write_files(dir, rel_paths, n_frames, n_threads, do_fsync, [&](int i, std::vector<unsigned char>& o) {
+        const aq_frame& f = frames[i];
+        if (f.w <= 0 || f.h <= 0 || f.w > 65535 || f.h > 65535) return false;
+        encode_jpeg(coef + (size_t)f.mcu * 384, f.w, f.h, o, true);
+        return true;
+    });
 }

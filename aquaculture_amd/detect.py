@@ -65,7 +65,9 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--save-crop", action="store_true",
                    help="save each detection's crop as <save_dir>/crops/<class>/<image stem>[k].jpg [UPSTREAM save_one_box]: pixels encoded on the GPU, "
                         "Huffman coding and files on host threads; byte-identical to Pillow's quality=95 4:4:4 JPEG of the same window")
-    p.add_argument("--nosave", action="store_true", help="do not save images/videos")
+    p.add_argument("--nosave", action="store_true",
+                   help="do not write <save_dir>/<source file name>: every image with its detections drawn on it (boxes and labels drawn and the "
+                        "JPEG's pixels encoded on the GPU; .jpg / .jpeg sources; quality 95, 4:2:0, as cv2.imwrite)")
     p.add_argument("--classes", nargs="+", type=int, help="filter by class: --classes 0, or --classes 0 2 3")
     p.add_argument("--agnostic-nms", action="store_true")
     p.add_argument("--augment", action="store_true",
@@ -75,9 +77,9 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--project", default=str(root / "runs/detect"), help="save results to project/name")
     p.add_argument("--name", default="exp", help="save results to project/name")
     p.add_argument("--exist-ok", action="store_true", help="existing project/name ok, do not increment")
-    p.add_argument("--line-thickness", default=3, type=int)
-    p.add_argument("--hide-labels", default=False, action="store_true")
-    p.add_argument("--hide-conf", default=False, action="store_true")
+    p.add_argument("--line-thickness", default=3, type=int, help="bounding box thickness (pixels) in the saved images")
+    p.add_argument("--hide-labels", default=False, action="store_true", help="no labels in the saved images")
+    p.add_argument("--hide-conf", default=False, action="store_true", help="no confidences in the labels of the saved images")
     p.add_argument("--half", action="store_true", help="reduced precision (bf16 on MI355X; upstream: fp16)")
     p.add_argument("--dnn", action="store_true")
     p.add_argument("--vid-stride", type=int, default=1)
@@ -115,7 +117,7 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
 
 
 def run_params(weights_id, conf_thres, iou_thres, max_det, imgsz, precision, save_conf, classes=None, agnostic_nms=False, augment=False,
-               save_crop=False) -> dict:
+               save_crop=False, save_img=None) -> dict:
     """What the label bytes depend on (run_params.json; --resume refuses a directory written with anything else).  The optional settings are
     recorded only when set, so that the record of a run without them stays what it always was."""
     return {"weights_sha256": weights_id, "conf_thres": float(conf_thres), "iou_thres": float(iou_thres), "max_det": int(max_det),
@@ -123,21 +125,23 @@ def run_params(weights_id, conf_thres, iou_thres, max_det, imgsz, precision, sav
             **({"classes": sorted(int(c) for c in classes)} if classes is not None else {}),
             **({"agnostic_nms": True} if agnostic_nms else {}),
             **({"augment": True} if augment else {}),
-            **({"save_crop": True} if save_crop else {})}
+            **({"save_crop": True} if save_crop else {}),
+            # annotated images are written (no --nosave): save_img = (line thickness, hide labels, hide confidences)
+            **({"save_img": True, "line_thickness": int(save_img[0]), "hide_labels": bool(save_img[1]), "hide_conf": bool(save_img[2])}
+               if save_img is not None else {})}
 
 
 def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_det=1000, device="",
         save_txt=False, save_conf=False, nosave=False, classes=None, agnostic_nms=False,
         project="runs/detect", name="exp", exist_ok=False, half=False, batch_size=64, precision=None,
         workers=8, decode_threads=False, quiet=False, geocode_bboxes=None, geocode_out=None, tile_scenes=0, autotune="auto", resume=False,
-        jpeg_decode="auto", augment=False, save_crop=False, log=print, **unsupported):
+        jpeg_decode="auto", augment=False, save_crop=False, line_thickness=3, hide_labels=False, hide_conf=False, log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb, jpeg_slots_to_rgb, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     for k in UNSUPPORTED:
         if unsupported.get(k):
             raise NotImplementedError(f"--{k.replace('_', '-')} is not part of the tile-sweep path (reference README.md:77)")
-    if not nosave:
-        log("note: annotated images are never written (the reference runs with --nosave)")
+    save_img = not nosave                                  # [UPSTREAM detect.py] save_img = not nosave and not source.endswith('.txt')
     weights = weights[0] if isinstance(weights, (list, tuple)) else weights
     precision = precision or ("bf16" if half else "fp32")
     if augment and precision == "fp8":
@@ -174,7 +178,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
     # a tile before rank 0 has accepted the directory, and a refusal reaches every rank.
     aqdist.on_rank0(lambda: None if tile_scenes else check_run_params(
         str(save_dir), run_params(file_digest(weights) if os.path.isfile(str(weights)) else str(weights), conf_thres, iou_thres, max_det, imgsz,
-                                  precision, save_conf, classes, agnostic_nms, augment, save_crop), resume))
+                                  precision, save_conf, classes, agnostic_nms, augment, save_crop,
+                                  (line_thickness, hide_labels, hide_conf) if save_img else None), resume))
     done_before = DoneManifest.load(str(save_dir)) if resume else set()
     manifest = DoneManifest(str(save_dir), rank)
     if not tile_scenes:
@@ -225,6 +230,11 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                              skip_stems=done_before)
         if resume:
             log(f"resume: {len(done_before)} tiles recorded as done in {save_dir}; rank {rank} skips {dataset.skipped} of its share")
+        if save_img:                                      # cv2.imwrite picks the format by the extension; JPEG is the one written here
+            other = [f for f in dataset.files if os.path.splitext(f)[1].lower() not in (".jpg", ".jpeg")]
+            if other:
+                raise ValueError(f"annotated images are written as JPEGs under the source's own file name: {other[0]}"
+                                 f"{f' and {len(other) - 1} more' if len(other) > 1 else ''} would not be one (use --nosave)")
 
     # Pipeline: decode threads -> [main thread: H2D, letterbox, engine, async D2H] -> [writer thread: rescale, format, files].
     # Up to `depth` batches are in flight, each with its own workspace slot, pinned result buffers and stream.
@@ -242,8 +252,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
 
     def writer():
         try:
-            if save_crop:
-                torch.cuda.set_device(dev)          # HIP's current device is per thread: the crop encode launches from here
+            if save_crop or save_img:
+                torch.cuda.set_device(dev)          # HIP's current device is per thread: the crop and image encodes launch from here
             while True:
                 item = q.get()
                 if item is None:
@@ -257,9 +267,12 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 H, W = hw
                 cnt = counts_h.numpy()
                 det_all = dets_h.numpy()
-                crops = None
+                crops = frames = None
                 if crop_src is not None:            # before the slot goes back: its stream and arenas carry the encode
-                    crops = encode_batch_crops(det_all, cnt[:len(paths)], (H, W), shapes0, paths, crop_src, slot_id)
+                    if save_crop:
+                        crops = encode_batch_crops(det_all, cnt[:len(paths)], (H, W), shapes0, paths, crop_src, slot_id)
+                    if save_img:                    # (after the crops: they are cut from the clean pixels, the drawing goes to a copy)
+                        frames = encode_batch_images(det_all, cnt[:len(paths)], (H, W), shapes0, paths, crop_src, slot_id)
                     crop_src = None                 # the batch's original images may go
                 written = []
                 same = all(sh == shapes0[0] for sh in shapes0)       # the pinned path: one original size per batch -> one numpy pass for all tiles
@@ -311,6 +324,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     slot_free[slot_id].release()
                 if crops is not None:
                     write_batch_crops(*crops)
+                if frames is not None:
+                    write_batch_images(*frames)
                 # the manifest line below vouches for these bytes: on disk first (files and their directory entries), then the record -- a
                 # node crash must not leave a recorded tile without its label file (it would look like "no detections" for good).
                 # One syncfs per batch; per-file fsync + directory fsync where that is unavailable.
@@ -384,6 +399,77 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             for d_ in sorted({os.path.dirname(r_) for r_ in rel}):
                 fsync_dir(os.path.join(str(save_dir), d_))
             fsync_dir(crops_dir)
+
+    img_scratch = [None] * depth                           # per slot: the batch's annotated copies (uint8 CUDA)
+    frame_arena = [None] * depth                           # per slot: (device int16, pinned int16) coefficient arenas of the frame encoder
+    label_atlas = [None]
+    checked_sizes = set()
+
+    def encode_batch_images(det_all, cnt, hw, shapes0, paths, img_src, slot_id):
+        """Annotated images, first half (slot held): upstream's boxes and labels for the batch as primitives binned per cell, the draw kernel
+        (source -> annotated copies in the slot's scratch), the 4:2:0 encode kernel on the copies, the coefficients back in host memory.
+        -> (coefficients, frame table, file names relative to save_dir)."""
+        from . import annotate
+        from .engine import (FRAME_ARENA_MCUS, PRIM_DTYPE, annotate_images, canvas_table, encode_frames, frame_mcus, frame_table,
+                             image_save_bytes)
+        images, bases, pitch = img_src
+        if label_atlas[0] is None:
+            label_atlas[0] = annotate.LabelAtlas(dev)
+        sizes = np.asarray([tuple(sh) for sh in shapes0], np.int64)
+        for sh in {tuple(sh) for sh in shapes0} - checked_sizes:      # a batch whose copies cannot be held is refused by name, once per size
+            checked_sizes.add(sh)
+            need, free = image_save_bytes(batch_size, *sh), torch.cuda.mem_get_info(dev)[0]
+            if img_scratch[slot_id] is None and need > free:
+                raise SystemExit(f"--batch-size {batch_size}: writing annotated {sh[1]}x{sh[0]} images takes {need >> 20} MiB per pipeline slot, "
+                                 f"{free >> 20} MiB are free (use a smaller batch or --nosave)")
+        groups = {}
+        for b, sh in enumerate(shapes0):                  # (one original size per batch in practice; tiles of another size in turn)
+            groups.setdefault(tuple(sh), []).append(b)
+        parts = []
+        for sh, idx in groups.items():
+            idx = np.asarray(idx)
+            tile, cls, conf, xyxy = postprocess.batch_boxes(det_all[idx], cnt[idx], hw, sh)
+            labels = None
+            if not hide_labels:
+                labels = label_atlas[0].lookup(postprocess.label_strings(ck.names, cls, conf, hide_conf), annotate.font_size(*sh))
+            parts.append(postprocess.annotation_prims(idx[tile], cls, xyxy, sizes, annotate.line_width(*sh, line_thickness), labels))
+        P = {f: np.concatenate([p_[0][f] for p_ in parts]) for f in postprocess.PRIM_FIELDS}
+        owner = np.concatenate([p_[1] for p_ in parts])
+        order = np.argsort(owner, kind="stable")          # (groups of sizes interleave in the batch; inside an image the order stays upstream's)
+        P, owner = {f: v[order] for f, v in P.items()}, owner[order]
+        cell_start, cell_prims = postprocess.bin_prims(P, owner, sizes)
+        canvases, nbytes = canvas_table(np.asarray(bases, np.int64), pitch, sizes)
+        table = frame_table(canvases["dst"], canvases["dst_pitch"], sizes)
+        need = max(FRAME_ARENA_MCUS, int(frame_mcus(table).max()))
+        with torch.cuda.stream(streams[slot_id]):
+            if img_scratch[slot_id] is None or img_scratch[slot_id].numel() < nbytes:
+                img_scratch[slot_id] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            if frame_arena[slot_id] is None or frame_arena[slot_id][0].numel() < need * 384:
+                frame_arena[slot_id] = (torch.empty(need * 384, dtype=torch.int16, device=dev), torch.empty(need * 384, dtype=torch.int16, pin_memory=True))
+            atlas = label_atlas[0].device_atlas()
+            annotate_images(images, canvases, postprocess.prims_array(P, PRIM_DTYPE), cell_start, cell_prims, atlas, nbytes, out=img_scratch[slot_id])
+            coef, table = encode_frames(img_scratch[slot_id], table, arena_mcus=frame_arena[slot_id][0].numel() // 384, arena=frame_arena[slot_id][0],
+                                        arena_host=frame_arena[slot_id][1])
+        return coef, table, [image_file_name(p_) for p_ in paths]
+
+    def image_file_name(path):
+        """[UPSTREAM detect.py] save_path = save_dir / p.name; a scene's tiles: the label file's stem + the extension of the reference's tile jpegs
+        (reference src/load_data/tile_tifs.py: tif_name.replace('.tif', '.jpeg'))."""
+        return os.path.splitext(os.path.basename(path))[0] + ".jpeg" if tile_scenes else os.path.basename(path)
+
+    def write_batch_images(coef, table, rel):
+        """Annotated images, second half (slot free): Huffman coding and files in one C call on four threads, then on disk before the manifest
+        records the batch, as the crops are."""
+        from .engine import write_image_files
+        write_image_files(str(save_dir), rel, coef, table, threads=4, fsync=durable and not can_syncfs[0])
+        if durable and not (can_syncfs[0] and sync_filesystem_of(str(save_dir))):
+            if can_syncfs[0]:
+                can_syncfs[0] = False
+                for r_ in rel:
+                    fd_ = os.open(os.path.join(str(save_dir), r_), os.O_RDONLY)
+                    os.fsync(fd_)
+                    os.close(fd_)
+            fsync_dir(str(save_dir))
 
     lock = threading.Lock()
     manifest_lock = threading.Lock()
@@ -561,8 +647,9 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 n_ += len(p_)
 
     def original_images(tiles0):
-        """--save-crop: the batch's decoded tiles (uint8 CUDA [B, H0, W0, 3]) as the crop encoder addresses them; None without the flag."""
-        if not save_crop:
+        """--save-crop and the annotated images: the batch's decoded tiles (uint8 CUDA [B, H0, W0, 3]) as the crop and frame encoders address
+        them; None when neither is written."""
+        if not (save_crop or save_img):
             return None
         B_, H0_, W0_, _ = tiles0.shape
         return tiles0.view(-1), [b_ * H0_ * W0_ * 3 for b_ in range(B_)], W0_ * 3
@@ -607,7 +694,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     else:
                         st.wait_event(scene_ev)            # another stream uploaded this scene
                     scene_dev.record_stream(st)
-                    if save_crop:                          # the crops are cut from the raster: tile b's pixel (x, y) at its origin + (x, y)
+                    if save_crop or save_img:              # the crops are cut from the raster: tile b's pixel (x, y) at its origin + (x, y)
                         row_b = int(scene_dev.shape[1]) * 3
                         crop_src = (scene_dev.view(-1), [y0 * row_b + x0 * 3 for x0, y0 in origins], row_b)
                     tiles = letterbox_scene_tiles(scene_dev, origins, thw, tuple(imgsz), int(max(ck.stride)), True)
@@ -722,8 +809,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             # tile-configuration timing, pipeline fill -- excluded): what a long sweep converges to
             t_end = t_start + (time.perf_counter() - t_start if world > 1 else elapsed)
             log(f"steady state: {(seen - 2 * batch_size) / max(t_end - t_steady[0], 1e-9):.1f} images/s on this GPU after the first two batches")
-        if save_txt:
-            log(f"Results saved to {save_dir}\n{labels_all} labels saved to {save_dir / 'labels'}")
+        if save_txt or save_img:                           # [UPSTREAM detect.py] the closing line names the run directory
+            log(f"Results saved to {save_dir}" + (f"\n{labels_all} labels saved to {save_dir / 'labels'}" if save_txt else ""))
         if geocode_bboxes:
             # the consumer's next step (reference src/process_yolo/geocode_results.py:106-197) on the label files just written
             if not save_txt or not save_conf:

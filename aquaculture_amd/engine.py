@@ -73,6 +73,7 @@ EXPORTS = (
     "aq_conv3x3_pl_supported", "aq_conv3x3_pl_asm_family", "aq_pack_conv3x3_pl", "aq_conv3x3_pl", "aq_conv3x3_pl_s2_supported", "aq_pack_conv3x3_pl_s2", "aq_conv3x3_pl_s2", "aq_jpeg_scratch_bytes", "aq_jpeg_idct_rgb", "aq_f32_to_e4m3", "aq_conv1x1_direct_f8out", "aq_absmax_bf16", "aq_engine_calibrate_amax", "aq_engine_set_fp8_scales", "aq_engine_last_launch", "aq_conv3x3_pl_f8_supported", "aq_pack_conv3x3_pl_f8", "aq_conv3x3_pl_f8", "aq_conv3x3_pl_w8_supported", "aq_pack_conv3x3_pl_w8", "aq_conv3x3_pl_w8", "aq_head_decode_supported", "aq_pack_head_weights", "aq_head_decode", "aq_head_counts_gather", "aq_preprocess_s2d", "aq_sppf_pool",
     "aq_upsample2x", "aq_letterbox_u8", "aq_letterbox_tiles_u8", "aq_format_label_rows", "aq_detect_decode", "aq_nms_scratch_bytes", "aq_nms", "aq_jpeg_huffman_decode", "aq_write_label_files",
     "aq_crop_jpeg_coefs", "aq_crop_jpeg_bytes", "aq_write_crop_files",
+    "aq_annotate_u8", "aq_image_jpeg_coefs", "aq_image_jpeg_bytes", "aq_write_image_files",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -117,6 +118,12 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_crop_jpeg_bytes.restype = C.c_long
     lib.aq_write_crop_files.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), vp, vp, i32, i32, i32]
     lib.aq_write_crop_files.restype = C.c_long
+    lib.aq_annotate_u8.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, C.c_longlong, vp]
+    lib.aq_image_jpeg_coefs.argtypes = [vp, C.c_longlong, vp, vp, i32, i32, vp, vp]
+    lib.aq_image_jpeg_bytes.argtypes = [vp, i32, i32, vp, sz]
+    lib.aq_image_jpeg_bytes.restype = C.c_long
+    lib.aq_write_image_files.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), vp, vp, i32, i32, i32]
+    lib.aq_write_image_files.restype = C.c_long
     lib.aq_engine_set_tuned_table.argtypes = [vp, i32, i32, i32, C.POINTER(i32), i32]
     lib.aq_engine_calibrate_amax.argtypes = [vp, vp, i32, i32, i32, vp, sz, C.POINTER(f32), i32, vp]
     lib.aq_engine_set_fp8_scales.argtypes = [vp, C.POINTER(f32), i32]
@@ -357,9 +364,12 @@ class Engine:
         self._ws = ws
         return ws
 
-    def workspace_bytes(self, B: int, H: int, W: int, augment: bool = False) -> int:
+    def workspace_bytes(self, B: int, H: int, W: int, augment: bool = False, save_img: Optional[Tuple[int, int]] = None) -> int:
         """Workspace bytes for batches up to ``B`` of H x W tiles, allocating nothing.  A batch some op of the plan cannot run raises
-        RuntimeError naming the op (plan index and name) and the largest batch that fits."""
+        RuntimeError naming the op (plan index and name) and the largest batch that fits.  save_img = (h0, w0): plus what writing annotated
+        images of that original size takes per pipeline slot (image_save_bytes)."""
+        if save_img is not None:
+            return self.workspace_bytes(B, H, W, augment) + image_save_bytes(B, *save_img)
         n = C.c_size_t()
         try:
             _check((self.lib.aq_engine_workspace_bytes_augment if augment else self.lib.aq_engine_workspace_bytes)(self.handle, B, H, W, C.byref(n)))
@@ -857,6 +867,182 @@ def write_crop_files(root_dir: str, rel_paths, coef: np.ndarray, table: np.ndarr
     if k < 0:
         raise OSError(f"could not write the crop {rel_paths[-1 - k]} in {root_dir}")
     return int(k)
+
+
+# ---- annotated images: aq_annotate_u8 (boxes and labels) and the whole-frame 4:2:0 encoder ----
+
+# aq_frame / aq_canvas / aq_prim (include/aq_engine.h)
+FRAME_DTYPE = np.dtype([("base", "<i8"), ("pitch", "<i4"), ("w", "<i4"), ("h", "<i4"), ("mcu", "<i4")])
+CANVAS_DTYPE = np.dtype([("src", "<i8"), ("dst", "<i8"), ("src_pitch", "<i4"), ("dst_pitch", "<i4"), ("w", "<i4"), ("h", "<i4"), ("cell", "<i4"), ("unit", "<i4")])
+PRIM_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("rgb", "<u4"), ("mask_w", "<i4"), ("mask", "<i8")])
+FRAME_ARENA_MCUS = 1 << 15         # 16 x 16 MCUs (768 bytes each) per encode piece: 25 MB of device arena and as much pinned (eight 1024-px frames)
+
+
+def frame_mcus(table: np.ndarray) -> np.ndarray:
+    """MCUs (16 x 16 pixels: four Y blocks, Cb, Cr) of each frame of a FRAME_DTYPE table."""
+    return ((table["w"].astype(np.int64) + 15) // 16) * ((table["h"].astype(np.int64) + 15) // 16)
+
+
+def frame_table(bases, pitch, sizes) -> np.ndarray:
+    """FRAME_DTYPE table of n frames: bases int64 [n] (byte offset of each image), pitch (row bytes; scalar or [n]), sizes int [n, 2] (h, w);
+    the frames' MCUs follow each other from 0."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    t = np.zeros(sizes.shape[0], FRAME_DTYPE)
+    t["base"], t["pitch"] = bases, pitch
+    t["h"], t["w"] = sizes.T
+    nm = frame_mcus(t)
+    if nm.sum() >= 1 << 31:
+        raise ValueError("frame table: more than 2^31 MCUs in one call")
+    t["mcu"][1:] = np.cumsum(nm)[:-1]
+    return t
+
+
+def image_save_bytes(B: int, h0: int, w0: int, arena_mcus: int = FRAME_ARENA_MCUS) -> int:
+    """Device bytes one pipeline slot holds for writing the annotated images of batches of B images of h0 x w0: the annotated copies and the
+    coefficient arena (as much again is pinned on the host)."""
+    per = ((h0 + 15) // 16) * ((w0 + 15) // 16)
+    return B * h0 * w0 * 3 + max(arena_mcus, per) * 768
+
+
+def encode_frames(images_dev: torch.Tensor, table: np.ndarray, arena_mcus: int = FRAME_ARENA_MCUS, arena: Optional[torch.Tensor] = None,
+                  arena_host: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """The device half of the whole-frame 4:2:0 encoder (aq_image_jpeg_coefs) on the current stream, shaped like encode_crops: the frames go
+    through an arena of `arena_mcus` MCUs in pieces (a frame never straddles two), each piece comes back through the pinned arena.  Returns
+    (coefficients int16 [MCUs, 384] in host memory, table)."""
+    _require_gpu()
+    lib = load_library()
+    assert images_dev.is_cuda and images_dev.dtype == torch.uint8 and images_dev.is_contiguous()
+    table = np.ascontiguousarray(table, dtype=FRAME_DTYPE)
+    n = table.shape[0]
+    if n == 0:
+        return np.zeros((0, 384), np.int16), table
+    nm = frame_mcus(table)
+    ends = table["mcu"].astype(np.int64) + nm
+    if table["mcu"][0] != 0 or np.any(table["mcu"][1:] != ends[:-1]):
+        raise ValueError("frame table: MCUs must follow each other from 0 (frame_table)")
+    w, h = table["w"].astype(np.int64), table["h"].astype(np.int64)
+    last = table["base"] + (h - 1) * table["pitch"] + 3 * w
+    bad = (w <= 0) | (h <= 0) | (w > 65535) | (h > 65535) | (table["base"] < 0) | (table["pitch"] < 3 * w) | (last > images_dev.numel())
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"frame {i} {table[i]} is empty or leaves its buffer ({images_dev.numel()} bytes)")
+    if int(nm.max()) > arena_mcus:
+        raise ValueError(f"a frame of {int(nm.max())} MCUs does not fit an arena of {arena_mcus}")
+    if arena is None or arena.numel() < arena_mcus * 384:
+        arena = torch.empty(arena_mcus * 384, dtype=torch.int16, device=images_dev.device)
+    if arena_host is None or arena_host.numel() < arena_mcus * 384:
+        arena_host = torch.empty(arena_mcus * 384, dtype=torch.int16, pin_memory=True)
+    table_dev = torch.from_numpy(table.view(np.uint8)).to(images_dev.device, non_blocking=False)
+    out = np.empty((int(ends[-1]), 384), np.int16)
+    stream = torch.cuda.current_stream()
+    c0 = 0
+    while c0 < n:
+        p0 = int(table["mcu"][c0])
+        c1 = int(np.searchsorted(ends, p0 + arena_mcus, side="right"))
+        used = int(ends[c1 - 1]) - p0
+        _check(lib.aq_image_jpeg_coefs(images_dev.data_ptr(), images_dev.numel(), table_dev.data_ptr() + c0 * FRAME_DTYPE.itemsize,
+                                       table.ctypes.data + c0 * FRAME_DTYPE.itemsize, c1 - c0, used, arena.data_ptr(), stream.cuda_stream))
+        arena_host[:used * 384].copy_(arena[:used * 384], non_blocking=True)
+        stream.synchronize()
+        out[p0:p0 + used] = arena_host[:used * 384].numpy().reshape(used, 384)
+        c0 = c1
+    return out, table
+
+
+def image_jpeg_bytes(coef: np.ndarray, w: int, h: int) -> bytes:
+    """The 4:2:0 JPEG file of one w x h frame from its MCUs (aq_image_jpeg_bytes; int16 [ceil(w/16) ceil(h/16), 384])."""
+    lib = load_library()
+    n = ((w + 15) // 16) * ((h + 15) // 16)
+    coef = np.ascontiguousarray(coef.reshape(-1)[:n * 384], dtype=np.int16)
+    assert coef.size == n * 384
+    buf = C.create_string_buffer(1024 + n * 384)
+    k = lib.aq_image_jpeg_bytes(coef.ctypes.data, int(w), int(h), buf, len(buf))
+    if k < 0:
+        buf = C.create_string_buffer(-k)
+        k = lib.aq_image_jpeg_bytes(coef.ctypes.data, int(w), int(h), buf, len(buf))
+    if k <= 0:
+        raise ValueError(f"image_jpeg_bytes: bad frame size {w} x {h}")
+    return buf.raw[:k]
+
+
+def write_image_files(root_dir: str, rel_paths, coef: np.ndarray, table: np.ndarray, threads: int = 4, fsync: bool = False) -> int:
+    """One C call per batch (aq_write_image_files; no interpreter lock held): frame i of `table`, coefficients from MCU table[i]["mcu"] of
+    `coef` (encode_frames), -> <root_dir>/<rel_paths[i]> on `threads` threads.  Returns the number of files."""
+    lib = load_library()
+    table = np.ascontiguousarray(table, dtype=FRAME_DTYPE)
+    coef = np.ascontiguousarray(coef, dtype=np.int16)
+    n = table.shape[0]
+    assert len(rel_paths) == n and (n == 0 or coef.size >= 384 * int((table["mcu"].astype(np.int64) + frame_mcus(table)).max()))
+    if n == 0:
+        return 0
+    arr = (C.c_char_p * n)(*[os.fsencode(p_) for p_ in rel_paths])
+    k = lib.aq_write_image_files(os.fsencode(root_dir), arr, coef.ctypes.data, table.ctypes.data, n, int(threads), int(fsync))
+    if k < 0:
+        raise OSError(f"could not write the image {rel_paths[-1 - k]} in {root_dir}")
+    return int(k)
+
+
+def canvas_table(src_bases, src_pitch, sizes) -> Tuple[np.ndarray, int]:
+    """CANVAS_DTYPE table of n images: src_bases int64 [n] / src_pitch (scalar or [n]) address the sources, sizes int [n, 2] (h, w); the
+    annotated copies lie back to back without row padding (each starting on a 4-byte boundary).  -> (table, bytes of the destination)."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    t = np.zeros(sizes.shape[0], CANVAS_DTYPE)
+    t["src"], t["src_pitch"] = src_bases, src_pitch
+    t["h"], t["w"] = sizes.T
+    t["dst_pitch"] = 3 * sizes[:, 1]
+    nbytes = (sizes[:, 0] * sizes[:, 1] * 3 + 3) // 4 * 4
+    cw, ch = (sizes[:, 1] + 15) // 16, (sizes[:, 0] + 15) // 16
+    t["dst"][1:] = np.cumsum(nbytes)[:-1]
+    t["cell"][1:] = np.cumsum(cw * ch)[:-1]
+    t["unit"][1:] = np.cumsum((cw + 3) // 4 * ch)[:-1]
+    return t, int(nbytes.sum())
+
+
+def annotate_images(src_dev: torch.Tensor, canvases: np.ndarray, prims: np.ndarray, cell_start: np.ndarray, cell_prims: np.ndarray,
+                    atlas_dev: Optional[torch.Tensor], dst_bytes: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """aq_annotate_u8 on the current stream: the images `canvases` (canvas_table) addresses in src_dev, each with the primitives of
+    `prims` (PRIM_DTYPE, postprocess.annotation_prims) binned per cell (postprocess.bin_prims) drawn on its copy.  Returns the destination
+    buffer (uint8 CUDA, `out` when it is large enough); src_dev is only read."""
+    _require_gpu()
+    lib = load_library()
+    assert src_dev.is_cuda and src_dev.dtype == torch.uint8 and src_dev.is_contiguous()
+    canvases = np.ascontiguousarray(canvases, dtype=CANVAS_DTYPE)
+    prims = np.ascontiguousarray(prims, dtype=PRIM_DTYPE)
+    cell_start = np.ascontiguousarray(cell_start, dtype=np.int32)
+    cell_prims = np.ascontiguousarray(cell_prims, dtype=np.int32)
+    w, h = canvases["w"].astype(np.int64), canvases["h"].astype(np.int64)
+    bad = (w <= 0) | (h <= 0) | (canvases["src"] < 0) | (canvases["src_pitch"] < 3 * w) | \
+          (canvases["src"] + (h - 1) * canvases["src_pitch"] + 3 * w > src_dev.numel())
+    if canvases.shape[0] == 0 or bad.any():
+        raise ValueError(f"image {int(np.nonzero(bad)[0][0]) if bad.any() else 0} is empty or leaves the source buffer ({src_dev.numel()} bytes)")
+    n_cells = int((((w + 15) // 16) * ((h + 15) // 16)).sum())
+    atlas_bytes = int(atlas_dev.numel()) if atlas_dev is not None else 0
+    m = prims["mask_w"] > 0
+    if cell_start.shape[0] != n_cells + 1 or cell_start[0] != 0 or cell_start[-1] != cell_prims.shape[0] or np.any(np.diff(cell_start) < 0) or \
+            (cell_prims.size and (cell_prims.min() < 0 or cell_prims.max() >= prims.shape[0])):
+        raise ValueError("annotate: the cell table does not fit the images and primitives (postprocess.bin_prims)")
+    if np.any(prims["mask"][m] < 0) or np.any(prims["mask"][m] + (prims["y1"][m].astype(np.int64) - prims["y0"][m]) * prims["mask_w"][m]
+                                              + (prims["x1"][m] - prims["x0"][m]) >= atlas_bytes):
+        raise ValueError("annotate: a label mask leaves the atlas")
+    if out is None or out.numel() < dst_bytes:
+        out = torch.empty(max(dst_bytes, 4), dtype=torch.uint8, device=src_dev.device)
+    # one upload for the four tables (8-byte aligned parts)
+    parts = [canvases.view(np.uint8), prims.view(np.uint8), cell_start.view(np.uint8), cell_prims.view(np.uint8)]
+    offs, total = [], 0
+    for a in parts:
+        offs.append(total)
+        total += (a.size + 7) // 8 * 8
+    host = np.zeros(max(total, 8), np.uint8)
+    for a, o in zip(parts, offs):
+        host[o:o + a.size] = a
+    tab = torch.from_numpy(host).to(src_dev.device)
+    base = tab.data_ptr()
+    _check(lib.aq_annotate_u8(src_dev.data_ptr(), src_dev.numel(), out.data_ptr(), out.numel(), base + offs[0], canvases.ctypes.data, canvases.shape[0],
+                              base + offs[1] if prims.shape[0] else None, prims.shape[0], base + offs[2], n_cells,
+                              base + offs[3] if prims.shape[0] else None, cell_prims.shape[0],
+                              atlas_dev.data_ptr() if atlas_bytes else None, atlas_bytes, _stream_ptr()))
+    tab.record_stream(torch.cuda.current_stream())
+    return out
 
 
 def stem_conv_nhwc(tiles_u8: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, act: bool = True, precision: str = "bf16") -> torch.Tensor:

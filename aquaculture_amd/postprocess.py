@@ -142,6 +142,125 @@ def crop_file_name(stem: str, ordinal: int) -> str:
     return f"{stem}{ordinal if ordinal > 1 else ''}.jpg"
 
 
+# ---- annotated images: upstream's Annotator.box_label (Pillow branch) as primitives for aq_annotate_u8 ----
+
+# [UPSTREAM utils/plots.py Colors]: the 20-entry palette, indexed cls % 20, as RGB
+PALETTE = np.array([[int(h_[i:i + 2], 16) for i in (0, 2, 4)] for h_ in (
+    "FF3838", "FF9D97", "FF701F", "FFB21D", "CFD231", "48F90A", "92CC17", "3DDB86", "1A9334", "00D4BB",
+    "2C99A8", "00C2FF", "344593", "6473FF", "0018EC", "8438FF", "520085", "CB38FF", "FF95C8", "FF37C7")], dtype=np.int64)
+PRIM_FIELDS = ("x0", "y0", "x1", "y1", "rgb", "mask_w", "mask")
+
+
+def batch_boxes(det_all: np.ndarray, counts: np.ndarray, img1_shape, img0_shape):
+    """The boxes upstream draws for a whole batch of tiles of ONE original size: det_all [B, max_det, 6], counts [B] -> (tile int64 [N],
+    cls int64 [N], conf float32 [N], xyxy int64 [N, 4]), every tile's detections in upstream's order (``reversed(det)``: ascending confidence,
+    the best box drawn last), tile after tile; xyxy = the rounded scale_boxes corners (a corner may equal the width or height)."""
+    counts = np.asarray(counts, dtype=np.int64)
+    B = counts.shape[0]
+    offsets = np.zeros(B + 1, np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    n = int(offsets[-1])
+    if n == 0:
+        z = np.zeros(0, np.int64)
+        return z, z.copy(), np.zeros(0, F32), np.zeros((0, 4), np.int64)
+    valid = np.arange(det_all.shape[1])[None, :] < counts[:, None]
+    det = np.asarray(det_all[:B], dtype=F32)[valid]
+    tile = np.repeat(np.arange(B), counts)
+    pos = np.arange(n)
+    det = det[offsets[tile] + (counts[tile] - 1) - (pos - offsets[tile])]     # reversed(det), per tile
+    xyxy = np.rint(scale_boxes(img1_shape, det[:, :4], img0_shape)).astype(np.int64)
+    return tile, det[:, 5].astype(np.int64), det[:, 4].copy(), xyxy
+
+
+def label_strings(names, cls: np.ndarray, conf: np.ndarray, hide_conf: bool = False):
+    """[UPSTREAM detect.py] ``names[c] if hide_conf else f'{names[c]} {conf:.2f}'`` per detection."""
+    if hide_conf:
+        return [names[int(c)] for c in cls]
+    return [f"{names[int(c)]} {float(v):.2f}" for c, v in zip(cls, conf)]
+
+
+def annotation_prims(image: np.ndarray, cls: np.ndarray, xyxy: np.ndarray, sizes, line_width: int, labels=None):
+    """[UPSTREAM utils/plots.py Annotator.box_label, Pillow branch] for N detections as aq_prim rows (engine.PRIM_DTYPE fields as a dict of
+    arrays) and the image index of each row, in drawing order.  image int [N] (index into sizes), cls int [N], xyxy int [N, 4], sizes int
+    [n_images, 2] (h, w), line_width = upstream's lw.  labels = None (--hide-labels) or int64 [N, 7]: (w, h) of ``font.getbbox(label)[2:]``,
+    the (width, height) of the label's 8-bit mask, its (x, y) offset, the mask's first byte in the atlas (annotate.LabelAtlas.lookup).
+
+    Per detection, in this order: the outline ``ImageDraw.rectangle(box, width=lw, outline=colour)`` -- ImagingDrawRectangle draws, for
+    i < lw, the rows y0 + i and y1 - i from x0 to x1 and the columns x0 + i and x1 - i from y0 + lw towards y1 - lw + 1, that
+    last row left out (upwards when the box is thinner than 2 lw - 1: such a box is painted beyond its corners), four rectangles --, the label's filled rectangle
+    ``(x0, y0 - h if outside else y0, x0 + w + 1, y0 + 1 if outside else y0 + h + 1)`` with ``outside = y0 - h >= 0``, and the text mask in
+    white at ``(x0, y0 - h if outside else y0)`` + the mask's offset.  Everything is clipped to the image; what is left empty is dropped."""
+    image = np.asarray(image, dtype=np.int64)
+    n = image.shape[0]
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    X0, Y0, X1, Y1 = (np.asarray(xyxy, dtype=np.int64).reshape(-1, 4)[:, i] for i in range(4))
+    lw = int(line_width)
+    colour = PALETTE[np.asarray(cls, dtype=np.int64) % 20]
+    rgb = colour[:, 0] | (colour[:, 1] << 8) | (colour[:, 2] << 16)
+    k = 4 if labels is None else 6
+    P = {f: np.zeros((n, k), np.int64) for f in PRIM_FIELDS}
+    a, b = Y0 + lw, Y1 - lw + 1                               # ImagingDrawLine, vertical: |b - a| points from a towards b, b itself left out
+    ya, yb = np.where(a < b, a, b + 1), np.where(a < b, b - 1, a)
+    for j, (a_, b_, c_, d_) in enumerate(((X0, Y0, X1, Y0 + lw - 1), (X0, Y1 - lw + 1, X1, Y1), (X1 - lw + 1, ya, X1, yb), (X0, ya, X0 + lw - 1, yb))):
+        P["x0"][:, j], P["y0"][:, j], P["x1"][:, j], P["y1"][:, j] = a_, b_, c_, d_
+    if lw <= 0:                                                # ImageDraw.rectangle draws no outline at width 0
+        P["x1"][:, :4] = P["x0"][:, :4] - 1
+    P["rgb"][:, :4] = rgb[:, None]
+    if labels is not None:
+        L = np.asarray(labels, dtype=np.int64).reshape(-1, 7)
+        w, h, mw, mh, ox, oy, off = (L[:, i] for i in range(7))
+        ty = np.where(Y0 - h >= 0, Y0 - h, Y0)
+        P["x0"][:, 4], P["y0"][:, 4], P["x1"][:, 4], P["y1"][:, 4], P["rgb"][:, 4] = X0, ty, X0 + w + 1, ty + h + 1, rgb
+        P["x0"][:, 5], P["y0"][:, 5], P["x1"][:, 5], P["y1"][:, 5], P["rgb"][:, 5] = X0 + ox, ty + oy, X0 + ox + mw - 1, ty + oy + mh - 1, 0xFFFFFF
+        P["mask_w"][:, 5], P["mask"][:, 5] = mw, off
+        P["x1"][:, 5] = np.where(mw > 0, P["x1"][:, 5], P["x0"][:, 5] - 1)   # (a label without ink, e.g. a blank: nothing to composite)
+    img = np.repeat(image, k)
+    P = {f: v.reshape(-1) for f, v in P.items()}
+    H, W = sizes[img, 0], sizes[img, 1]
+    cx0, cy0 = np.maximum(P["x0"], 0), np.maximum(P["y0"], 0)
+    P["mask"] = P["mask"] + (cy0 - P["y0"]) * P["mask_w"] + (cx0 - P["x0"])    # the mask byte of the first pixel kept
+    P["x0"], P["y0"], P["x1"], P["y1"] = cx0, cy0, np.minimum(P["x1"], W - 1), np.minimum(P["y1"], H - 1)
+    keep = (P["x1"] >= P["x0"]) & (P["y1"] >= P["y0"])
+    return {f: v[keep] for f, v in P.items()}, img[keep]
+
+
+def prims_array(P: dict, dtype) -> np.ndarray:
+    """annotation_prims' columns as one structured array (engine.PRIM_DTYPE)."""
+    out = np.zeros(P["x0"].shape[0], dtype)
+    for f in PRIM_FIELDS:
+        out[f] = P[f]
+    return out
+
+
+def bin_prims(P: dict, image: np.ndarray, sizes):
+    """The primitives of annotation_prims binned per 16 x 16-pixel cell: image i has ceil(w / 16) ceil(h / 16) cells in raster order, the
+    images' cells follow each other.  -> (cell_start int32 [cells + 1], cell_prims int32 [entries]): cell c applies the primitives
+    cell_prims[cell_start[c]:cell_start[c + 1]], ascending.  The work is that of the cells the primitives touch, not cells x primitives."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    cw, ch = (sizes[:, 1] + 15) // 16, (sizes[:, 0] + 15) // 16
+    first = np.zeros(sizes.shape[0] + 1, np.int64)
+    np.cumsum(cw * ch, out=first[1:])
+    n_cells = int(first[-1])
+    if n_cells >= 1 << 31:
+        raise ValueError("bin_prims: more than 2^31 cells")
+    cx0, cy0, cx1, cy1 = P["x0"] >> 4, P["y0"] >> 4, P["x1"] >> 4, P["y1"] >> 4
+    nx = cx1 - cx0 + 1
+    cnt = nx * (cy1 - cy0 + 1)
+    total = int(cnt.sum())
+    if total >= 1 << 31:
+        raise ValueError("bin_prims: more than 2^31 cell entries")
+    idx = np.repeat(np.arange(cnt.shape[0]), cnt)
+    start = np.cumsum(cnt) - cnt
+    local = np.arange(total) - start[idx]
+    nxi = nx[idx]
+    cell = first[image[idx]] + (cy0[idx] + local // nxi) * cw[image[idx]] + cx0[idx] + local % nxi
+    # by cell, ascending primitive index inside a cell: one sort of (cell, entry number) keys -- the entries are generated in primitive order
+    key = np.sort(cell * max(total, 1) + np.arange(total))
+    cell_start = np.zeros(n_cells + 1, np.int64)
+    np.cumsum(np.bincount(cell, minlength=n_cells), out=cell_start[1:])
+    return cell_start.astype(np.int32), idx[key % max(total, 1)].astype(np.int32)
+
+
 def format_rows(rows: np.ndarray, save_conf: bool = True) -> str:
     """Text of one label file.  Each value through ``%g`` of the double that equals the fp32 value
     (one C-level format call for the whole file: the same conversions as upstream's per-line ``%``)."""

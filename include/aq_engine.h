@@ -496,6 +496,34 @@ long aq_crop_jpeg_bytes(const int16_t* coef, int w, int h, uint8_t* buf, size_t 
 long aq_write_crop_files(const char* dir, const char* const* rel_paths, const int16_t* coef, const aq_crop* crops, int n_crops,
                          int n_threads, int do_fsync);
 
+/* Annotated images (detect.py without --nosave) [UPSTREAM utils/plots.py Annotator.box_label, Pillow branch; detect.py cv2.imwrite].
+ * aq_canvas: one w x h uint8 RGB image of a batch.  Its pixel (x, y) is at src + y * src_pitch + 3 x of the source buffer, the annotated copy at
+ * dst + y * dst_pitch + 3 x of the destination buffer; cell = its first 16 x 16-pixel cell in the cell table (ceil(w / 16) ceil(h / 16) cells,
+ * raster order), unit = its first draw unit (four cells side by side: ceil(ceil(w / 16) / 4) ceil(h / 16) units).
+ * aq_prim: pixels [x0, x1] x [y0, y1] (inclusive, inside the image).  mask_w == 0: filled with rgb (R | G << 8 | B << 16).  mask_w > 0: rgb
+ * composited through an 8-bit mask with Pillow's BLEND8; pixel (x, y) reads atlas byte mask + (y - y0) * mask_w + (x - x0). */
+typedef struct aq_canvas { int64_t src, dst; int32_t src_pitch, dst_pitch, w, h, cell, unit; } aq_canvas;
+typedef struct aq_prim { int32_t x0, y0, x1, y1; uint32_t rgb; int32_t mask_w; int64_t mask; } aq_prim;
+/* Out of place, pixel-centric: every pixel of every canvas = its source pixel with the primitives of its cell applied in table order.
+ * cell_start_dev: n_cells + 1 ascending offsets into cell_prims_dev (n_entries indices into prims_dev, ascending inside a cell).  canvases_host =
+ * canvases_dev's content in host memory: a canvas that leaves a buffer is refused before the launch. */
+int aq_annotate_u8(const uint8_t* src_dev, long long src_bytes, uint8_t* dst_dev, long long dst_bytes, const aq_canvas* canvases_dev,
+                   const aq_canvas* canvases_host, int n_canvases, const aq_prim* prims_dev, int n_prims, const int32_t* cell_start_dev,
+                   int n_cells, const int32_t* cell_prims_dev, int n_entries, const uint8_t* atlas_dev, long long atlas_bytes, void* stream);
+/* Whole-frame JPEG, what cv2.imwrite's libjpeg writes for a .jpg: quality 95, 4:2:0, standard Huffman tables; byte-identical to Pillow's
+ * save(quality=95, subsampling=2) of the same pixels (OpenCV's own header bytes are not pinned).  aq_frame: a w x h image at base (pixel (x, y)
+ * at base + y * pitch + 3 x); mcu = its first 16 x 16 MCU in the coefficient arena.  An MCU holds 6 x 64 int16: Y00 Y01 Y10 Y11 Cb Cr, the
+ * interleaved scan's order, each block in zigzag order; a frame has ceil(w / 16) ceil(h / 16) MCUs in raster order. */
+typedef struct aq_frame { int64_t base; int32_t pitch, w, h, mcu; } aq_frame;
+/* Device half: edge replication, rgb_ycc_convert, h2v2_downsample, level shift, jpeg_fdct_islow, quantisation, libjpeg's dummy blocks.
+ * frames: sorted by mcu, back to back; frames_host = the same table in host memory (a frame that leaves the buffer is refused). */
+int aq_image_jpeg_coefs(const uint8_t* images_dev, long long image_bytes, const aq_frame* frames_dev, const aq_frame* frames_host, int n_frames,
+                        int n_mcus, int16_t* coef_dev, void* stream);
+/* Host half, siblings of aq_crop_jpeg_bytes / aq_write_crop_files: one frame's file; a batch of files on n_threads threads. */
+long aq_image_jpeg_bytes(const int16_t* coef, int w, int h, uint8_t* buf, size_t buflen);
+long aq_write_image_files(const char* dir, const char* const* rel_paths, const int16_t* coef, const aq_frame* frames, int n_frames,
+                          int n_threads, int do_fsync);
+
 #ifdef __cplusplus
 }
 #endif
