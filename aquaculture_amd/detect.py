@@ -111,13 +111,18 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--tile-scenes", nargs="?", type=int, const=1024, default=0, metavar="TILESIZE",
                    help="opt-in scene mode: --source holds whole scene rasters (*.tif); they are cut into TILESIZE (default 1024) tiles "
                         "on the GPU, in the order and with the names of reference src/load_data/tile_tifs.py, skipping its jpeg step")
+    p.add_argument("--blank-key", nargs="?", const="", default=None, metavar="CSV",
+                   help="also classify every image of the sweep as blank / partly blank / complete (the reference's is_blank and is_partly_blank, "
+                        "src/utils.py:325-369) from the decoded pixels while they are on the GPU, and write the reference's "
+                        "data/image_boxes_blank_key.csv (default <save_dir>/image_boxes_blank_key.csv) with the statistics as extra columns; "
+                        "with --tile-scenes these are the raster's own pixels, not those of a JPEG round trip")
     opt = p.parse_args(argv)
     opt.imgsz *= 2 if len(opt.imgsz) == 1 else 1
     return opt
 
 
 def run_params(weights_id, conf_thres, iou_thres, max_det, imgsz, precision, save_conf, classes=None, agnostic_nms=False, augment=False,
-               save_crop=False, save_img=None) -> dict:
+               save_crop=False, save_img=None, blank_key=False) -> dict:
     """What the label bytes depend on (run_params.json; --resume refuses a directory written with anything else).  The optional settings are
     recorded only when set, so that the record of a run without them stays what it always was."""
     return {"weights_sha256": weights_id, "conf_thres": float(conf_thres), "iou_thres": float(iou_thres), "max_det": int(max_det),
@@ -128,14 +133,16 @@ def run_params(weights_id, conf_thres, iou_thres, max_det, imgsz, precision, sav
             **({"save_crop": True} if save_crop else {}),
             # annotated images are written (no --nosave): save_img = (line thickness, hide labels, hide confidences)
             **({"save_img": True, "line_thickness": int(save_img[0]), "hide_labels": bool(save_img[1]), "hide_conf": bool(save_img[2])}
-               if save_img is not None else {})}
+               if save_img is not None else {}),
+            **({"blank_key": True} if blank_key else {})}
 
 
 def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_det=1000, device="",
         save_txt=False, save_conf=False, nosave=False, classes=None, agnostic_nms=False,
         project="runs/detect", name="exp", exist_ok=False, half=False, batch_size=64, precision=None,
         workers=8, decode_threads=False, quiet=False, geocode_bboxes=None, geocode_out=None, tile_scenes=0, autotune="auto", resume=False,
-        jpeg_decode="auto", augment=False, save_crop=False, line_thickness=3, hide_labels=False, hide_conf=False, log=print, **unsupported):
+        jpeg_decode="auto", augment=False, save_crop=False, line_thickness=3, hide_labels=False, hide_conf=False, blank_key=None, log=print,
+        **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb, jpeg_slots_to_rgb, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     for k in UNSUPPORTED:
@@ -179,11 +186,18 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
     aqdist.on_rank0(lambda: None if tile_scenes else check_run_params(
         str(save_dir), run_params(file_digest(weights) if os.path.isfile(str(weights)) else str(weights), conf_thres, iou_thres, max_det, imgsz,
                                   precision, save_conf, classes, agnostic_nms, augment, save_crop,
-                                  (line_thickness, hide_labels, hide_conf) if save_img else None), resume))
+                                  (line_thickness, hide_labels, hide_conf) if save_img else None, blank_key is not None), resume))
     done_before = DoneManifest.load(str(save_dir)) if resume else set()
     manifest = DoneManifest(str(save_dir), rank)
     if not tile_scenes:
         manifest.open()
+    key_part = None
+    if blank_key is not None:                              # this rank's part of the white-space key, appended batch by batch
+        from . import blank as aqblank
+        if not resume:                                     # (a run directory used again with --exist-ok: the earlier run's parts are not this run's)
+            aqdist.on_rank0(lambda: [os.remove(str(old_)) for old_ in sorted(save_dir.glob("blank_key.rank*.csv"))] and None)
+        key_part = aqblank.PartFile(str(save_dir), rank)
+        key_part.open()
 
     ck = load_checkpoint(weights)
     eng = Engine(ck, precision, dev, fp8_calibration="defer")
@@ -258,7 +272,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 item = q.get()
                 if item is None:
                     return
-                ev, counts_h, dets_h, paths, shapes0, hw, gidx, t_inf, slot_id, crop_src = item
+                ev, counts_h, dets_h, paths, shapes0, hw, gidx, t_inf, slot_id, crop_src, blank_h = item
                 item = None
                 ev.synchronize()
                 t0 = time.perf_counter()
@@ -268,6 +282,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 cnt = counts_h.numpy()
                 det_all = dets_h.numpy()
                 crops = frames = None
+                key_lines = aqblank.key_rows(paths, blank_h.numpy()) if blank_h is not None else None      # (read before the slot goes back)
                 if crop_src is not None:            # before the slot goes back: its stream and arenas carry the encode
                     if save_crop:
                         crops = encode_batch_crops(det_all, cnt[:len(paths)], (H, W), shapes0, paths, crop_src, slot_id)
@@ -326,6 +341,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     write_batch_crops(*crops)
                 if frames is not None:
                     write_batch_images(*frames)
+                if key_lines is not None:                   # in the part file (and on disk) before the manifest records the batch
+                    key_part.append(gidx, key_lines, durable)
                 # the manifest line below vouches for these bytes: on disk first (files and their directory entries), then the record -- a
                 # node crash must not leave a recorded tile without its label file (it would look like "no detections" for good).
                 # One syncfs per batch; per-file fsync + directory fsync where that is unavailable.
@@ -647,12 +664,34 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 n_ += len(p_)
 
     def original_images(tiles0):
-        """--save-crop and the annotated images: the batch's decoded tiles (uint8 CUDA [B, H0, W0, 3]) as the crop and frame encoders address
-        them; None when neither is written."""
-        if not (save_crop or save_img):
+        """--save-crop, the annotated images and --blank-key: the batch's decoded tiles (uint8 CUDA [B, H0, W0, 3]) as the crop and frame
+        encoders and the statistics kernel address them; None when none of them is asked for."""
+        if not (save_crop or save_img or blank_key is not None):
             return None
         B_, H0_, W0_, _ = tiles0.shape
         return tiles0.view(-1), [b_ * H0_ * W0_ * 3 for b_ in range(B_)], W0_ * 3
+
+    blank_slot = [None] * depth                            # per slot: scratch, records, pinned records, frame table on the device and its bytes
+
+    def blank_batch(src, shapes0, slot):
+        """--blank-key: the statistics kernel over the batch's source images on the slot's stream, the records (36 bytes per image) on their
+        way to the slot's pinned buffer.  -> int32 pinned [B, 9], valid once the batch's event has passed."""
+        from .engine import BLANK_FIELDS, blank_frame_table, blank_stats
+        images, bases, pitch = src
+        table = blank_frame_table(np.asarray(bases, np.int64), pitch, np.asarray([tuple(sh) for sh in shapes0], np.int64))
+        n = table.shape[0]
+        need = int(eng.lib.aq_blank_stats_scratch_bytes(table.ctypes.data, n))
+        bs = blank_slot[slot]
+        if bs is None or bs["scratch"].numel() < need or bs["out"].shape[0] < n:
+            bs = blank_slot[slot] = {"scratch": torch.empty(max(need, 4), dtype=torch.uint8, device=dev),
+                                     "out": torch.empty((max(n, batch_size), len(BLANK_FIELDS)), dtype=torch.int32, device=dev),
+                                     "host": torch.empty((max(n, batch_size), len(BLANK_FIELDS)), dtype=torch.int32).pin_memory(),
+                                     "table": None, "table_bytes": None}
+        if bs["table_bytes"] != table.tobytes():           # (batch after batch of one tile size: the table is uploaded once per slot)
+            bs["table"], bs["table_bytes"] = torch.from_numpy(table.view(np.uint8).copy()).to(dev), table.tobytes()
+        out = blank_stats(images, table, scratch=bs["scratch"], out=bs["out"], frames_dev=bs["table"])
+        bs["host"][:n].copy_(out, non_blocking=True)
+        return bs["host"][:n]
 
     release_of = [None]
     split_note = [False]
@@ -694,7 +733,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     else:
                         st.wait_event(scene_ev)            # another stream uploaded this scene
                     scene_dev.record_stream(st)
-                    if save_crop or save_img:              # the crops are cut from the raster: tile b's pixel (x, y) at its origin + (x, y)
+                    if save_crop or save_img or blank_key is not None:     # the crops are cut from the raster: tile b's pixel (x, y) at its origin + (x, y)
                         row_b = int(scene_dev.shape[1]) * 3
                         crop_src = (scene_dev.view(-1), [y0 * row_b + x0 * 3 for x0, y0 in origins], row_b)
                     tiles = letterbox_scene_tiles(scene_dev, origins, thw, tuple(imgsz), int(max(ck.stride)), True)
@@ -723,6 +762,9 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                         tiles = jpeg_slots_to_rgb(tiles, h0_, w0_, scratch=jpeg_scratch[slot])
                     crop_src = original_images(tiles)
                     tiles = letterbox_device(tiles, tuple(imgsz), int(max(ck.stride)), True)
+                blank_h = blank_batch(crop_src, shapes0, slot) if blank_key is not None else None
+                if not (save_crop or save_img):
+                    crop_src = None                        # (only the statistics read the source: the writer gets the records, not the pixels)
                 if tune:                                   # once, before the pipeline fills
                     tune = False
                     geom = [int(tiles.shape[0]), int(tiles.shape[1]), int(tiles.shape[2])]
@@ -754,7 +796,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             H, W = int(tiles.shape[1]), int(tiles.shape[2])
             shape_str = f"(1, 3, {H}, {W})"
             t2 = time.perf_counter()
-            q.put((ev, counts_h, dets_h, paths, shapes0, (H, W), list(gidx), t2 - t1, slot, crop_src))
+            q.put((ev, counts_h, dets_h, paths, shapes0, (H, W), list(gidx), t2 - t1, slot, crop_src, blank_h))
             crop_src = None
             if diag is not None:
                 diag["put"] += time.perf_counter() - t2
@@ -778,6 +820,10 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         q.put(None)
     for w_ in wts:
         w_.join()
+    if key_part is not None:
+        # every row of this rank is in its part file now; rank 0 merges all parts of the directory after the counters' all-reduce below, which
+        # no rank passes before every rank has come this far (a resumed run finds the interrupted run's parts too)
+        key_part.close()
     if multi:                                          # collective tail; a failed rank takes the others down with it at once
         try:
             with gather_lock:
@@ -811,6 +857,15 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             log(f"steady state: {(seen - 2 * batch_size) / max(t_end - t_steady[0], 1e-9):.1f} images/s on this GPU after the first two batches")
         if save_txt or save_img:                           # [UPSTREAM detect.py] the closing line names the run directory
             log(f"Results saved to {save_dir}" + (f"\n{labels_all} labels saved to {save_dir / 'labels'}" if save_txt else ""))
+        if blank_key is not None:
+            key_out = blank_key or str(save_dir / aqblank.KEY_FILE)
+            listing = None
+            if not tile_scenes:
+                from .dataloader import list_images
+                listing = list_images(source)
+            n_key = aqblank.merge_parts(str(save_dir), key_out, listing)
+            log(f"blank key: {n_key[aqblank.BLANK]} blank, {n_key[aqblank.PARTLY_BLANK]} partly blank, {n_key[aqblank.COMPLETE]} complete "
+                f"images in {key_out}")
         if geocode_bboxes:
             # the consumer's next step (reference src/process_yolo/geocode_results.py:106-197) on the label files just written
             if not save_txt or not save_conf:

@@ -74,6 +74,7 @@ EXPORTS = (
     "aq_upsample2x", "aq_letterbox_u8", "aq_letterbox_tiles_u8", "aq_format_label_rows", "aq_detect_decode", "aq_nms_scratch_bytes", "aq_nms", "aq_jpeg_huffman_decode", "aq_write_label_files",
     "aq_crop_jpeg_coefs", "aq_crop_jpeg_bytes", "aq_write_crop_files",
     "aq_annotate_u8", "aq_image_jpeg_coefs", "aq_image_jpeg_bytes", "aq_write_image_files",
+    "aq_blank_stats_scratch_bytes", "aq_blank_stats_u8",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -124,6 +125,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_image_jpeg_bytes.restype = C.c_long
     lib.aq_write_image_files.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), vp, vp, i32, i32, i32]
     lib.aq_write_image_files.restype = C.c_long
+    lib.aq_blank_stats_scratch_bytes.argtypes = [vp, i32]
+    lib.aq_blank_stats_scratch_bytes.restype = sz
+    lib.aq_blank_stats_u8.argtypes = [vp, C.c_longlong, vp, vp, i32, vp, sz, vp, vp]
     lib.aq_engine_set_tuned_table.argtypes = [vp, i32, i32, i32, C.POINTER(i32), i32]
     lib.aq_engine_calibrate_amax.argtypes = [vp, vp, i32, i32, i32, vp, sz, C.POINTER(f32), i32, vp]
     lib.aq_engine_set_fp8_scales.argtypes = [vp, C.POINTER(f32), i32]
@@ -364,10 +368,14 @@ class Engine:
         self._ws = ws
         return ws
 
-    def workspace_bytes(self, B: int, H: int, W: int, augment: bool = False, save_img: Optional[Tuple[int, int]] = None) -> int:
+    def workspace_bytes(self, B: int, H: int, W: int, augment: bool = False, save_img: Optional[Tuple[int, int]] = None,
+                        blank_key: Optional[Tuple[int, int]] = None) -> int:
         """Workspace bytes for batches up to ``B`` of H x W tiles, allocating nothing.  A batch some op of the plan cannot run raises
         RuntimeError naming the op (plan index and name) and the largest batch that fits.  save_img = (h0, w0): plus what writing annotated
-        images of that original size takes per pipeline slot (image_save_bytes)."""
+        images of that original size takes per pipeline slot (image_save_bytes).  blank_key = (h0, w0): plus what --blank-key holds per
+        pipeline slot for images of that original size (blank_key_bytes)."""
+        if blank_key is not None:
+            return self.workspace_bytes(B, H, W, augment, save_img) + blank_key_bytes(B, *blank_key)
         if save_img is not None:
             return self.workspace_bytes(B, H, W, augment) + image_save_bytes(B, *save_img)
         n = C.c_size_t()
@@ -1043,6 +1051,60 @@ def annotate_images(src_dev: torch.Tensor, canvases: np.ndarray, prims: np.ndarr
                               atlas_dev.data_ptr() if atlas_bytes else None, atlas_bytes, _stream_ptr()))
     tab.record_stream(torch.cuda.current_stream())
     return out
+
+
+# ---- --blank-key: aq_blank_stats_u8 (grey extrema, blank rows and columns, non-blank pixels of every source image) ----
+
+BLANK_FIELDS = ("l_min", "l_max", "blank_rows", "blank_cols", "nonblank_px", "x0", "y0", "x1", "y1")      # aq_blank_stat
+
+
+def blank_frame_table(bases, pitch, sizes) -> np.ndarray:
+    """FRAME_DTYPE table of n images for blank_stats: bases int64 [n] (byte offset of each image), pitch (row bytes; scalar or [n]), sizes int
+    [n, 2] (h, w); `mcu` = the image's first word among the scratch's column sums (the images' columns follow each other from 0)."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    t = np.zeros(sizes.shape[0], FRAME_DTYPE)
+    t["base"], t["pitch"] = bases, pitch
+    t["h"], t["w"] = sizes.T
+    if sizes[:, 1].sum() >= 1 << 31:
+        raise ValueError("blank frame table: more than 2^31 columns in one call")
+    t["mcu"][1:] = np.cumsum(sizes[:, 1])[:-1]
+    return t
+
+
+def blank_key_bytes(B: int, h0: int, w0: int) -> int:
+    """Device bytes one pipeline slot holds for --blank-key with batches of B images of h0 x w0: the kernel's scratch (8 words per image and
+    one per column), the frame table and the records."""
+    return B * (8 + w0) * 4 + B * FRAME_DTYPE.itemsize + B * 4 * len(BLANK_FIELDS)
+
+
+def blank_stats(images_dev: torch.Tensor, frames: np.ndarray, stream: Optional[torch.cuda.Stream] = None, scratch: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None, frames_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """aq_blank_stats_u8 on `stream` (default: the current one): the statistics of the images `frames` (blank_frame_table) addresses in the
+    uint8 CUDA buffer images_dev -> int32 CUDA [n, 9] (BLANK_FIELDS), exactly blank.stats_numpy of each image.  `scratch` (uint8 CUDA),
+    `out` (int32 CUDA [>= n, 9]) and `frames_dev` (the table in device memory, uint8) are used when given and large enough: the call
+    itself allocates nothing then.  A frame that leaves the buffer raises before anything is launched."""
+    _require_gpu()
+    lib = load_library()
+    assert images_dev.is_cuda and images_dev.dtype == torch.uint8 and images_dev.is_contiguous()
+    frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+    n = frames.shape[0]
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        if out is None or out.shape[0] < n:
+            out = torch.empty((n, len(BLANK_FIELDS)), dtype=torch.int32, device=images_dev.device)
+        if n == 0:
+            _check(lib.aq_blank_stats_u8(images_dev.data_ptr(), images_dev.numel(), None, None, 0, None, 0, None, _stream_ptr()))
+            return out[:0]
+        need = int(lib.aq_blank_stats_scratch_bytes(frames.ctypes.data, n))
+        if scratch is None or scratch.numel() < need:
+            scratch = torch.empty(max(need, 4), dtype=torch.uint8, device=images_dev.device)
+        if frames_dev is None:
+            frames_dev = torch.from_numpy(frames.view(np.uint8)).to(images_dev.device)
+        assert frames_dev.numel() >= frames.nbytes
+        _check(lib.aq_blank_stats_u8(images_dev.data_ptr(), images_dev.numel(), frames_dev.data_ptr(), frames.ctypes.data, n, scratch.data_ptr(),
+                                     scratch.numel(), out.data_ptr(), _stream_ptr()))
+        for t_ in (scratch, frames_dev, out):
+            t_.record_stream(torch.cuda.current_stream())
+    return out[:n]
 
 
 def stem_conv_nhwc(tiles_u8: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, act: bool = True, precision: str = "bf16") -> torch.Tensor:

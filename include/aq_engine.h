@@ -524,6 +524,20 @@ long aq_image_jpeg_bytes(const int16_t* coef, int w, int h, uint8_t* buf, size_t
 long aq_write_image_files(const char* dir, const char* const* rel_paths, const int16_t* coef, const aq_frame* frames, int n_frames,
                           int n_threads, int do_fsync);
 
+/* --blank-key: what the reference's white-space key is made of (reference src/utils.py is_blank, is_partly_blank, the mask of
+ * correct_partly_blank_geom), per w x h uint8 RGB image, in integers.  L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 (Pillow's convert("L"));
+ * l_min, l_max = its extrema; blank_rows = rows whose 3 w bytes sum to >= 750 w, blank_cols = columns whose 3 h bytes sum to >= 750 h (an
+ * average >= 250.); nonblank_px = pixels with max(R, G, B) < 250 and [x0, x1] x [y0, y1] their bounding box (inclusive; none: w, h, -1, -1). */
+typedef struct aq_blank_stat { int32_t l_min, l_max, blank_rows, blank_cols, nonblank_px, x0, y0, x1, y1; } aq_blank_stat;
+/* Frames are addressed as the frame encoder's (aq_frame; any base and pitch, w and h <= 65535, w h < 2^31); here mcu = the frame's first word
+ * among the column sums of the scratch: the frames' columns follow each other from 0.  Scratch: 8 words per frame + one per column. */
+size_t aq_blank_stats_scratch_bytes(const aq_frame* frames_host, int n_frames);
+/* One read of every image on `stream`; the call initialises its scratch, allocates nothing and uses integer atomics only, so two calls give the
+ * same bytes.  frames_host = frames_dev's content in host memory: a frame that leaves [images_dev, images_dev + image_bytes) is refused before
+ * anything is launched.  n_frames = 0 does nothing. */
+int aq_blank_stats_u8(const uint8_t* images_dev, long long image_bytes, const aq_frame* frames_dev, const aq_frame* frames_host, int n_frames,
+                      void* scratch_dev, size_t scratch_bytes, aq_blank_stat* stats_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
