@@ -116,13 +116,21 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "src/utils.py:325-369) from the decoded pixels while they are on the GPU, and write the reference's "
                         "data/image_boxes_blank_key.csv (default <save_dir>/image_boxes_blank_key.csv) with the statistics as extra columns; "
                         "with --tile-scenes these are the raster's own pixels, not those of a JPEG round trip")
+    p.add_argument("--blank-geom", nargs="?", const="", default=None, metavar="GEOJSON",
+                   help="also outline the non-blank part of every partly blank image (the reference's correct_partly_blank_geom, src/utils.py:482-530: "
+                        "the largest 8-connected region of max(R, G, B) < 250) on the GPU and write one polygon per such image (default "
+                        "<save_dir>/image_boxes_partly_blank.geojson): in EPSG:3857 metres with --geocode-bboxes, else in pixels; implies --blank-key")
+    p.add_argument("--blank-geom-simplify", type=float, default=0.5, metavar="TOL",
+                   help="Douglas-Peucker tolerance in metres for the --blank-geom polygons in EPSG:3857 (the reference's simplify(0.5)); 0 disables it")
     opt = p.parse_args(argv)
+    if opt.blank_geom is not None and opt.blank_key is None:
+        opt.blank_key = ""
     opt.imgsz *= 2 if len(opt.imgsz) == 1 else 1
     return opt
 
 
 def run_params(weights_id, conf_thres, iou_thres, max_det, imgsz, precision, save_conf, classes=None, agnostic_nms=False, augment=False,
-               save_crop=False, save_img=None, blank_key=False) -> dict:
+               save_crop=False, save_img=None, blank_key=False, blank_geom=False) -> dict:
     """What the label bytes depend on (run_params.json; --resume refuses a directory written with anything else).  The optional settings are
     recorded only when set, so that the record of a run without them stays what it always was."""
     return {"weights_sha256": weights_id, "conf_thres": float(conf_thres), "iou_thres": float(iou_thres), "max_det": int(max_det),
@@ -134,17 +142,20 @@ def run_params(weights_id, conf_thres, iou_thres, max_det, imgsz, precision, sav
             # annotated images are written (no --nosave): save_img = (line thickness, hide labels, hide confidences)
             **({"save_img": True, "line_thickness": int(save_img[0]), "hide_labels": bool(save_img[1]), "hide_conf": bool(save_img[2])}
                if save_img is not None else {}),
-            **({"blank_key": True} if blank_key else {})}
+            **({"blank_key": True} if blank_key else {}),
+            **({"blank_geom": True} if blank_geom else {})}
 
 
 def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_det=1000, device="",
         save_txt=False, save_conf=False, nosave=False, classes=None, agnostic_nms=False,
         project="runs/detect", name="exp", exist_ok=False, half=False, batch_size=64, precision=None,
         workers=8, decode_threads=False, quiet=False, geocode_bboxes=None, geocode_out=None, tile_scenes=0, autotune="auto", resume=False,
-        jpeg_decode="auto", augment=False, save_crop=False, line_thickness=3, hide_labels=False, hide_conf=False, blank_key=None, log=print,
-        **unsupported):
+        jpeg_decode="auto", augment=False, save_crop=False, line_thickness=3, hide_labels=False, hide_conf=False, blank_key=None, blank_geom=None,
+        blank_geom_simplify=0.5, log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb, jpeg_slots_to_rgb, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
+    if blank_geom is not None and blank_key is None:     # the outlines are made for the images the key calls partly blank
+        blank_key = ""
     for k in UNSUPPORTED:
         if unsupported.get(k):
             raise NotImplementedError(f"--{k.replace('_', '-')} is not part of the tile-sweep path (reference README.md:77)")
@@ -186,7 +197,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
     aqdist.on_rank0(lambda: None if tile_scenes else check_run_params(
         str(save_dir), run_params(file_digest(weights) if os.path.isfile(str(weights)) else str(weights), conf_thres, iou_thres, max_det, imgsz,
                                   precision, save_conf, classes, agnostic_nms, augment, save_crop,
-                                  (line_thickness, hide_labels, hide_conf) if save_img else None, blank_key is not None), resume))
+                                  (line_thickness, hide_labels, hide_conf) if save_img else None, blank_key is not None, blank_geom is not None),
+        resume))
     done_before = DoneManifest.load(str(save_dir)) if resume else set()
     manifest = DoneManifest(str(save_dir), rank)
     if not tile_scenes:
@@ -198,6 +210,16 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             aqdist.on_rank0(lambda: [os.remove(str(old_)) for old_ in sorted(save_dir.glob("blank_key.rank*.csv"))] and None)
         key_part = aqblank.PartFile(str(save_dir), rank)
         key_part.open()
+    geom_part = geom_bboxes = None
+    if blank_geom is not None:                             # and of the partly blank images' polygons
+        from . import blank_geom as aqgeom
+        if not resume:
+            aqdist.on_rank0(lambda: [os.remove(str(old_)) for old_ in sorted(save_dir.glob("blank_geom.rank*.jsonl"))] and None)
+        if geocode_bboxes:
+            from . import geocode
+            geom_bboxes = geocode.load_wanted_bboxes(geocode_bboxes)
+        geom_part = aqgeom.PartFile(str(save_dir), rank)
+        geom_part.open()
 
     ck = load_checkpoint(weights)
     eng = Engine(ck, precision, dev, fp8_calibration="defer")
@@ -266,8 +288,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
 
     def writer():
         try:
-            if save_crop or save_img:
-                torch.cuda.set_device(dev)          # HIP's current device is per thread: the crop and image encodes launch from here
+            if save_crop or save_img or blank_geom is not None:
+                torch.cuda.set_device(dev)          # HIP's current device is per thread: the crop and image encodes and the outlines launch from here
             while True:
                 item = q.get()
                 if item is None:
@@ -283,6 +305,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 det_all = dets_h.numpy()
                 crops = frames = None
                 key_lines = aqblank.key_rows(paths, blank_h.numpy()) if blank_h is not None else None      # (read before the slot goes back)
+                geom_lines = geom_batch(paths, shapes0, gidx, blank_h.numpy(), crop_src, slot_id) if blank_geom is not None else None
                 if crop_src is not None:            # before the slot goes back: its stream and arenas carry the encode
                     if save_crop:
                         crops = encode_batch_crops(det_all, cnt[:len(paths)], (H, W), shapes0, paths, crop_src, slot_id)
@@ -343,6 +366,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     write_batch_images(*frames)
                 if key_lines is not None:                   # in the part file (and on disk) before the manifest records the batch
                     key_part.append(gidx, key_lines, durable)
+                if geom_lines is not None:
+                    geom_part.append(*geom_lines, durable)
                 # the manifest line below vouches for these bytes: on disk first (files and their directory entries), then the record -- a
                 # node crash must not leave a recorded tile without its label file (it would look like "no detections" for good).
                 # One syncfs per batch; per-file fsync + directory fsync where that is unavailable.
@@ -370,6 +395,32 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             while True:              # keep draining so q.put() cannot block either
                 if q.get() is None:
                     return
+
+    geom_scratch = [None]                                  # one scratch for all slots (at most engine.GEOM_GROUP_SLOTS x 9 bytes), made on first use
+    geom_lock = threading.Lock()
+
+    def geom_batch(paths, shapes0, gidx, stats, src, slot_id):
+        """--blank-geom (slot held): the batch's partly blank images -- known from the key's records, so a batch without one launches
+        nothing -- through the component kernels on the slot's stream, in groups that bound the scratch; the winners' outer edges back in
+        host memory, chained into rings.  -> (orders, part lines) of the partly blank images."""
+        from .engine import blank_components, blank_geom_frame_table, blank_geom_groups, blank_ring_edges
+        partly = [b for b, st in enumerate(aqblank.status(stats)) if st == aqblank.PARTLY_BLANK]
+        if not partly:
+            return [], []
+        feats = {b: None for b in partly}                  # (no pixel below 250: "actually blank", nothing to examine)
+        todo = [b for b in partly if stats[b][aqblank.FIELDS.index("nonblank_px")] > 0]
+        images, bases, pitch = src
+        with geom_lock, torch.cuda.stream(streams[slot_id]):
+            for group in blank_geom_groups([tuple(shapes0[b]) for b in todo]):
+                idx = [todo[k] for k in group]
+                table = blank_geom_frame_table(np.asarray(bases, np.int64)[idx], pitch, [tuple(shapes0[b]) for b in idx])
+                rec_dev, geom_scratch[0], table_dev = blank_components(images, table, scratch=geom_scratch[0])
+                rec = rec_dev.cpu().numpy()
+                edges = blank_ring_edges(table, rec, rec_dev, geom_scratch[0], table_dev)     # (waits for the stream: the scratch is free again)
+                for b, r, e in zip(idx, rec, edges):
+                    if r[1] > 0:
+                        feats[b] = aqgeom.feature(paths[b], r, aqgeom.ring_from_edges(e, int(shapes0[b][1])), geom_bboxes, blank_geom_simplify)
+        return [gidx[b] for b in partly], aqgeom.part_rows([paths[b] for b in partly], [feats[b] for b in partly])
 
     crops_dir = str(save_dir / "crops")
     crop_arena = [None] * depth                            # per slot: (device int16, pinned int16) coefficient arenas, made on first use
@@ -763,7 +814,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     crop_src = original_images(tiles)
                     tiles = letterbox_device(tiles, tuple(imgsz), int(max(ck.stride)), True)
                 blank_h = blank_batch(crop_src, shapes0, slot) if blank_key is not None else None
-                if not (save_crop or save_img):
+                if not (save_crop or save_img or blank_geom is not None):
                     crop_src = None                        # (only the statistics read the source: the writer gets the records, not the pixels)
                 if tune:                                   # once, before the pipeline fills
                     tune = False
@@ -824,6 +875,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         # every row of this rank is in its part file now; rank 0 merges all parts of the directory after the counters' all-reduce below, which
         # no rank passes before every rank has come this far (a resumed run finds the interrupted run's parts too)
         key_part.close()
+    if geom_part is not None:
+        geom_part.close()
     if multi:                                          # collective tail; a failed rank takes the others down with it at once
         try:
             with gather_lock:
@@ -866,6 +919,11 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             n_key = aqblank.merge_parts(str(save_dir), key_out, listing)
             log(f"blank key: {n_key[aqblank.BLANK]} blank, {n_key[aqblank.PARTLY_BLANK]} partly blank, {n_key[aqblank.COMPLETE]} complete "
                 f"images in {key_out}")
+        if blank_geom is not None:
+            geom_out = blank_geom or str(save_dir / aqgeom.GEOM_FILE)
+            n_geom = aqgeom.merge_parts(str(save_dir), geom_out, listing, crs="urn:ogc:def:crs:EPSG::3857" if geom_bboxes is not None else None)
+            log(f"blank geom: {n_geom['features']} polygons of partly blank images in {geom_out}; {len(n_geom['actually_blank'])} actually blank"
+                + (": " + " ".join(n_geom["actually_blank"]) if n_geom["actually_blank"] else ""))
         if geocode_bboxes:
             # the consumer's next step (reference src/process_yolo/geocode_results.py:106-197) on the label files just written
             if not save_txt or not save_conf:

@@ -75,6 +75,7 @@ EXPORTS = (
     "aq_crop_jpeg_coefs", "aq_crop_jpeg_bytes", "aq_write_crop_files",
     "aq_annotate_u8", "aq_image_jpeg_coefs", "aq_image_jpeg_bytes", "aq_write_image_files",
     "aq_blank_stats_scratch_bytes", "aq_blank_stats_u8",
+    "aq_blank_geom_scratch_bytes", "aq_blank_components_u8", "aq_blank_ring_edges_u8",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -128,6 +129,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_blank_stats_scratch_bytes.argtypes = [vp, i32]
     lib.aq_blank_stats_scratch_bytes.restype = sz
     lib.aq_blank_stats_u8.argtypes = [vp, C.c_longlong, vp, vp, i32, vp, sz, vp, vp]
+    lib.aq_blank_geom_scratch_bytes.argtypes = [vp, i32]
+    lib.aq_blank_geom_scratch_bytes.restype = sz
+    lib.aq_blank_components_u8.argtypes = [vp, C.c_longlong, vp, vp, i32, vp, vp, sz, vp, vp, vp]
+    lib.aq_blank_ring_edges_u8.argtypes = [vp, vp, i32, vp, sz, vp, vp, vp, vp, C.c_longlong, vp]
     lib.aq_engine_set_tuned_table.argtypes = [vp, i32, i32, i32, C.POINTER(i32), i32]
     lib.aq_engine_calibrate_amax.argtypes = [vp, vp, i32, i32, i32, vp, sz, C.POINTER(f32), i32, vp]
     lib.aq_engine_set_fp8_scales.argtypes = [vp, C.POINTER(f32), i32]
@@ -1105,6 +1110,113 @@ def blank_stats(images_dev: torch.Tensor, frames: np.ndarray, stream: Optional[t
         for t_ in (scratch, frames_dev, out):
             t_.record_stream(torch.cuda.current_stream())
     return out[:n]
+
+
+# ---- --blank-geom: aq_blank_components_u8 / aq_blank_ring_edges_u8 (components of the non-blank mask, the largest one, its outer edges) ----
+
+GEOM_FIELDS = ("examined", "n_components", "label", "px", "area_px", "x0", "y0", "x1", "y1", "n_edges", "edge_px", "reserved")      # aq_blank_geom
+GEOM_GROUP_SLOTS = 16 << 20        # scratch slots (9 bytes each: 151 MB) blank_geom_groups gives one call: sixteen 1024-px tiles
+
+
+def blank_geom_slots(sizes) -> np.ndarray:
+    """Scratch slots of images of the sizes int [n, 2] (h, w): (w + 1) h + 2, rounded up to a multiple of 4."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    return ((sizes[:, 1] + 1) * sizes[:, 0] + 2 + 3) // 4 * 4
+
+
+def blank_geom_frame_table(bases, pitch, sizes) -> np.ndarray:
+    """FRAME_DTYPE table of n images for blank_components (arguments as blank_frame_table's); `mcu` = the image's first scratch slot."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    t = np.zeros(sizes.shape[0], FRAME_DTYPE)
+    t["base"], t["pitch"] = bases, pitch
+    t["h"], t["w"] = sizes.T
+    slots = blank_geom_slots(sizes)
+    if slots.sum() >= 1 << 31:
+        raise ValueError("blank geom frame table: more than 2^31 scratch slots in one call")
+    t["mcu"][1:] = np.cumsum(slots)[:-1]
+    return t
+
+
+def blank_geom_groups(sizes, limit: int = GEOM_GROUP_SLOTS) -> List[List[int]]:
+    """Images of the sizes int [n, 2] (h, w) in groups, in order, whose scratch slots stay within `limit` (an image larger than that is a
+    group of its own): what bounds the scratch of --blank-geom to 9 bytes x limit whatever the batch."""
+    groups, room = [], 0
+    for k, s in enumerate(blank_geom_slots(sizes).tolist()):
+        if not groups or room < s:
+            groups.append([])
+            room = limit
+        groups[-1].append(k)
+        room -= s
+    return groups
+
+
+def blank_components(images_dev: torch.Tensor, frames: np.ndarray, stats_dev: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                     scratch: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, frames_dev: Optional[torch.Tensor] = None,
+                     labels: bool = False):
+    """aq_blank_components_u8 on `stream` (default: the current one): per image `frames` (blank_geom_frame_table) addresses in the uint8 CUDA
+    buffer images_dev its aq_blank_geom record -> int32 CUDA [n, 12] (GEOM_FIELDS), exactly blank_geom.components_numpy's.  stats_dev = the
+    images' blank_stats records (int32 CUDA [n, 9]): only partly blank images with a non-blank pixel are examined then.  labels=True:
+    -> (records, int32 CUDA [2 x slots]: per image its two label maps from 2 mcu).  Returns (records, scratch, frames_dev[, labels]): the
+    scratch and the device table are what blank_ring_edges reads.  A frame that leaves the buffer raises before anything is launched."""
+    _require_gpu()
+    lib = load_library()
+    assert images_dev.is_cuda and images_dev.dtype == torch.uint8 and images_dev.is_contiguous()
+    frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+    n = frames.shape[0]
+    dev = images_dev.device
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        if out is None or out.shape[0] < n:
+            out = torch.empty((n, len(GEOM_FIELDS)), dtype=torch.int32, device=dev)
+        if n == 0:
+            _check(lib.aq_blank_components_u8(images_dev.data_ptr(), images_dev.numel(), None, None, 0, None, None, 0, None, None, _stream_ptr()))
+            return (out[:0], scratch, frames_dev) + ((torch.empty(0, dtype=torch.int32, device=dev),) if labels else ())
+        need = int(lib.aq_blank_geom_scratch_bytes(frames.ctypes.data, n))
+        if scratch is None or scratch.numel() < need:
+            scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+        if frames_dev is None:
+            frames_dev = torch.from_numpy(frames.view(np.uint8)).to(dev)
+        assert frames_dev.numel() >= frames.nbytes
+        if stats_dev is not None:
+            assert stats_dev.is_cuda and stats_dev.dtype == torch.int32 and stats_dev.is_contiguous() and tuple(stats_dev.shape) == (n, len(BLANK_FIELDS))
+        maps = None
+        if labels:
+            maps = torch.full((2 * int(blank_geom_slots(np.stack([frames["h"], frames["w"]], 1)).sum()),), -3, dtype=torch.int32, device=dev)
+        _check(lib.aq_blank_components_u8(images_dev.data_ptr(), images_dev.numel(), frames_dev.data_ptr(), frames.ctypes.data, n,
+                                          stats_dev.data_ptr() if stats_dev is not None else None, scratch.data_ptr(), scratch.numel(),
+                                          out.data_ptr(), maps.data_ptr() if labels else None, _stream_ptr()))
+        for t_ in (scratch, frames_dev, out) + ((stats_dev,) if stats_dev is not None else ()) + ((maps,) if labels else ()):
+            t_.record_stream(torch.cuda.current_stream())
+    return (out[:n], scratch, frames_dev) + ((maps,) if labels else ())
+
+
+def blank_ring_edges(frames: np.ndarray, records: np.ndarray, records_dev: torch.Tensor, scratch: torch.Tensor, frames_dev: torch.Tensor,
+                     stream: Optional[torch.cuda.Stream] = None) -> List[np.ndarray]:
+    """aq_blank_ring_edges_u8 after blank_components on the same table: records = its records on the host (they size the slices),
+    records_dev / scratch / frames_dev = what it returned.  -> per image int32 [edge_px, 2] (pixel index, side mask), sorted by pixel
+    index, so that the result does not depend on the order the kernel wrote them in.  Synchronises the stream."""
+    _require_gpu()
+    lib = load_library()
+    frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+    n = frames.shape[0]
+    records = np.asarray(records).reshape(n, len(GEOM_FIELDS))
+    at = np.zeros(n + 1, np.int64)
+    at[1:] = np.cumsum(records[:, GEOM_FIELDS.index("edge_px")].astype(np.int64))
+    total = int(at[-1])
+    if n == 0 or total == 0:
+        return [np.zeros((0, 2), np.int32) for _ in range(n)]
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        at_dev = torch.from_numpy(at).to(scratch.device)
+        edges = torch.full((total, 2), -1, dtype=torch.int32, device=scratch.device)
+        _check(lib.aq_blank_ring_edges_u8(frames_dev.data_ptr(), frames.ctypes.data, n, scratch.data_ptr(), scratch.numel(), records_dev.data_ptr(),
+                                          at_dev.data_ptr(), at.ctypes.data, edges.data_ptr(), total, _stream_ptr()))
+        for t_ in (scratch, frames_dev, records_dev, at_dev, edges):
+            t_.record_stream(torch.cuda.current_stream())
+        host = edges.cpu().numpy()                          # (waits for the stream)
+    out = []
+    for k in range(n):
+        e = host[at[k]:at[k + 1]]
+        out.append(e[np.argsort(e[:, 0], kind="stable")])
+    return out
 
 
 def stem_conv_nhwc(tiles_u8: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, act: bool = True, precision: str = "bf16") -> torch.Tensor:

@@ -538,6 +538,37 @@ size_t aq_blank_stats_scratch_bytes(const aq_frame* frames_host, int n_frames);
 int aq_blank_stats_u8(const uint8_t* images_dev, long long image_bytes, const aq_frame* frames_dev, const aq_frame* frames_host, int n_frames,
                       void* scratch_dev, size_t scratch_bytes, aq_blank_stat* stats_dev, void* stream);
 
+/* --blank-geom: the largest non-blank region of a partly blank tile (reference src/utils.py:482-530, correct_partly_blank_geom), in integers.
+ * m = max(R, G, B) < 250.  Components: 8-connected on m; regions: 4-connected on ~m, every region that touches the frame's border being part
+ * of one "outside" region.  A label is the row-major index y w + x of the first pixel (outside: -1).  An outer edge is a unit edge between a
+ * pixel of m and the outside region or the frame's border; E(C) = sum over pixels (x, y) of C of (x + 1) [right neighbour outside] -
+ * x [left neighbour outside] is the area inside C's exterior ring unless another component encloses C (then it is less than the encloser's).
+ * The winner is arg max E, ties to the smallest label (the reference's tie order is rasterio's emission order, which is not pinned).
+ * Record: examined (0: skipped, the rest as for no component); n_components; the winner's label (-1: none), pixel count, E, inclusive box
+ * (none: w, h, -1, -1), outer edges and pixels with at least one outer edge. */
+typedef struct aq_blank_geom { int32_t examined, n_components, label, px, area_px, x0, y0, x1, y1, n_edges, edge_px, reserved; } aq_blank_geom;
+/* Frames as aq_blank_stats_u8 takes them (any base and pitch, w and h <= 65535, w h < 2^31 - 1); here mcu = the frame's first slot in the
+ * scratch, a frame taking (w + 1) h + 2 slots rounded up to a multiple of 4, the frames' slots following each other from 0.  Scratch: 64
+ * bytes per frame + 9 per slot (4 parent, 4 area accumulators, 1 mask), for every frame of the table, examined or not: 9.4 MB per 1024-px
+ * tile, at most 2^31 slots per call.  A caller bounds it by examining the qualifying frames of a batch in groups. */
+size_t aq_blank_geom_scratch_bytes(const aq_frame* frames_host, int n_frames);
+/* Records of n_frames images of one buffer, on `stream`.  stats_dev (or null: every frame is examined) = the frames' aq_blank_stat records:
+ * a frame is examined only if they say partly blank (not blank, blank_rows + blank_cols > 0) with nonblank_px > 0; the others are skipped on
+ * the device.  labels_out_dev (or null): 2 int32 per slot, frame i's foreground map [h][w] at 2 mcu (label; -1 off the mask) and its
+ * background map behind it (label; -1 outside region; -2 on the mask); examined frames only.  The same checks as aq_blank_stats_u8, before
+ * anything is launched; the call initialises its scratch, allocates nothing and uses integer min / max / add atomics only, so two calls give
+ * the same bytes.  n_frames = 0 does nothing. */
+int aq_blank_components_u8(const uint8_t* images_dev, long long image_bytes, const aq_frame* frames_dev, const aq_frame* frames_host, int n_frames,
+                           const aq_blank_stat* stats_dev, void* scratch_dev, size_t scratch_bytes, aq_blank_geom* records_dev,
+                           int32_t* labels_out_dev, void* stream);
+/* The winners' outer edges, from the scratch and the records aq_blank_components_u8 left for the same table: per winner pixel with an outer
+ * edge two int32, (pixel index y w + x, side mask: 1 N, 2 E, 4 S, 8 W).  Frame i's go to pairs [edge_at[i], edge_at[i + 1]) of edges_dev (room
+ * for edges_room pairs): edge_at = the running sum of the records' edge_px, given in device and in host memory.  The order inside a slice
+ * depends on scheduling; the set does not. */
+int aq_blank_ring_edges_u8(const aq_frame* frames_dev, const aq_frame* frames_host, int n_frames, const void* scratch_dev, size_t scratch_bytes,
+                           const aq_blank_geom* records_dev, const long long* edge_at_dev, const long long* edge_at_host, int32_t* edges_dev,
+                           long long edges_room, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
