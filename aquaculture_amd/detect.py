@@ -122,7 +122,16 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "<save_dir>/image_boxes_partly_blank.geojson): in EPSG:3857 metres with --geocode-bboxes, else in pixels; implies --blank-key")
     p.add_argument("--blank-geom-simplify", type=float, default=0.5, metavar="TOL",
                    help="Douglas-Peucker tolerance in metres for the --blank-geom polygons in EPSG:3857 (the reference's simplify(0.5)); 0 disables it")
+    p.add_argument("--facilities", nargs="?", const="", default=None, metavar="GEOJSON",
+                   help="after the sweep and its geocoding, cluster the detections into candidate facilities (the reference's "
+                        "src/process_yolo/calc_net_areas.py and src/cluster_facilities.py: per-cage area estimates, then DBSCAN of the cages' "
+                        "EPSG:3035 centroids per year or image pass, on the GPU) and write them (default <save_dir>/facilities.geojson) with "
+                        "their member detections beside them (<name>_detections.geojson); needs --geocode-bboxes")
+    from .facilities import add_options as _facility_options
+    _facility_options(p)
     opt = p.parse_args(argv)
+    if opt.facilities is not None and not opt.geocode_bboxes:
+        p.error("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if opt.blank_geom is not None and opt.blank_key is None:
         opt.blank_key = ""
     opt.imgsz *= 2 if len(opt.imgsz) == 1 else 1
@@ -151,11 +160,14 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         project="runs/detect", name="exp", exist_ok=False, half=False, batch_size=64, precision=None,
         workers=8, decode_threads=False, quiet=False, geocode_bboxes=None, geocode_out=None, tile_scenes=0, autotune="auto", resume=False,
         jpeg_decode="auto", augment=False, save_crop=False, line_thickness=3, hide_labels=False, hide_conf=False, blank_key=None, blank_geom=None,
-        blank_geom_simplify=0.5, log=print, **unsupported):
+        blank_geom_simplify=0.5, facilities=None, facilities_conf=0.5, facilities_eps=10.0, facilities_min_cages=5, facilities_by="year",
+        log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb, jpeg_slots_to_rgb, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     if blank_geom is not None and blank_key is None:     # the outlines are made for the images the key calls partly blank
         blank_key = ""
+    if facilities is not None and not geocode_bboxes:
+        raise ValueError("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     for k in UNSUPPORTED:
         if unsupported.get(k):
             raise NotImplementedError(f"--{k.replace('_', '-')} is not part of the tile-sweep path (reference README.md:77)")
@@ -384,6 +396,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     with manifest_lock:
                         manifest.add(Path(p).stem for p in paths)
                 with lock:
+                    if facilities is not None:              # the circle areas' border test wants every image's own size
+                        image_hw.update((Path(p).stem, (int(sh[0]), int(sh[1]))) for p, sh in zip(paths, shapes0))
                     stats["seen"] += len(paths)
                     stats["labels"] += nlab
                     stats["dets"] += ndet
@@ -396,6 +410,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 if q.get() is None:
                     return
 
+    image_hw = {}                                          # --facilities: stem -> (h, w) of the images this rank's sweep saw
     geom_scratch = [None]                                  # one scratch for all slots (at most engine.GEOM_GROUP_SLOTS x 9 bytes), made on first use
     geom_lock = threading.Lock()
 
@@ -933,6 +948,17 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             out = geocode_out or str(save_dir / "detections.geojson")
             table = geocode.geocode_label_dir(labels_dir, geocode_bboxes, out)
             log(f"{table['image'].shape[0]} detections geocoded to {out} in {time.perf_counter() - t_g:.2f}s")
+            if facilities is not None:
+                # the steps after it (reference src/process_yolo/calc_net_areas.py, src/cluster_facilities.py).  An image this rank's sweep
+                # did not see (another rank's, or one a resumed run had finished) counts as the 1024-px tile the geocoding assumes anyway.
+                from . import facilities as aqfac
+                t_f = time.perf_counter()
+                hw = np.asarray([image_hw.get(str(s_), (geocode.IM_HEIGHT, geocode.IM_WIDTH)) for s_ in table["stems"]], np.int64).reshape(-1, 2)
+                fac_out = facilities or str(save_dir / "facilities.geojson")
+                fac = aqfac.facilities_from_table(table, fac_out, facilities_by, facilities_conf, facilities_eps, facilities_min_cages,
+                                                  hw[table["image"], 1], hw[table["image"], 0])
+                log(f"{len(fac['facility_index'])} facilities of {int((fac['_members'] >= 0).sum())} cages in {fac_out} "
+                    f"in {time.perf_counter() - t_f:.2f}s")
     manifest.close()
     eng.close()
     return save_dir

@@ -76,6 +76,7 @@ EXPORTS = (
     "aq_annotate_u8", "aq_image_jpeg_coefs", "aq_image_jpeg_bytes", "aq_write_image_files",
     "aq_blank_stats_scratch_bytes", "aq_blank_stats_u8",
     "aq_blank_geom_scratch_bytes", "aq_blank_components_u8", "aq_blank_ring_edges_u8",
+    "aq_facility_scratch_bytes", "aq_facility_dbscan_f64",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -133,6 +134,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_blank_geom_scratch_bytes.restype = sz
     lib.aq_blank_components_u8.argtypes = [vp, C.c_longlong, vp, vp, i32, vp, vp, sz, vp, vp, vp]
     lib.aq_blank_ring_edges_u8.argtypes = [vp, vp, i32, vp, sz, vp, vp, vp, vp, C.c_longlong, vp]
+    lib.aq_facility_scratch_bytes.argtypes = [C.c_longlong]
+    lib.aq_facility_scratch_bytes.restype = sz
+    lib.aq_facility_dbscan_f64.argtypes = [vp, vp, vp, vp, C.c_longlong, C.c_double, i32, vp, sz, vp, vp, vp]
     lib.aq_engine_set_tuned_table.argtypes = [vp, i32, i32, i32, C.POINTER(i32), i32]
     lib.aq_engine_calibrate_amax.argtypes = [vp, vp, i32, i32, i32, vp, sz, C.POINTER(f32), i32, vp]
     lib.aq_engine_set_fp8_scales.argtypes = [vp, C.POINTER(f32), i32]
@@ -1217,6 +1221,83 @@ def blank_ring_edges(frames: np.ndarray, records: np.ndarray, records_dev: torch
         e = host[at[k]:at[k + 1]]
         out.append(e[np.argsort(e[:, 0], kind="stable")])
     return out
+
+
+# ---- --facilities: aq_facility_dbscan_f64 (DBSCAN of the detections' centroids, as sklearn labels them) ----
+
+FACILITY_CELL_BITS = 21                    # AQ_FACILITY_CELL_BITS: key = group << 42 | cell_y << 21 | cell_x
+FACILITY_CELL_FACTOR = 1.0 + 2.0 ** -20    # cell edge = eps x this
+
+
+def facility_sort_keys(xy: torch.Tensor, group: torch.Tensor, eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The sort aq_facility_dbscan_f64 takes: xy float64 [n, 2] and group int32 [n] (dense ids) on one device -> (keys int64 [n] ascending,
+    perm int32 [n]: the original index of every sorted position).  key = group << 42 | cell_y << 21 | cell_x with
+    cell = floor((v - min v) / h) + 1 per axis, h = eps (1 + 2^-20).
+
+    Two points within eps never lie two cells apart.  With t = (v - min v) / h exact, |v_a - v_b| <= eps (1 + 2^-51) for every pair the
+    kernel's rounded test dx dx + dy dy <= eps eps can accept (the differences, the products, the sum and eps eps are each rounded once, by at
+    most 2^-53 of the value; along one axis that is at most six roundings of a squared length, under 2^-51 of the length), so
+    t_a - t_b <= (1 + 2^-51) / (1 + 2^-20) < 1 - 2^-21.  The computed t carries two roundings (the subtraction and the division): a relative
+    error below 2^-52, and t < 2^21 (checked), so an absolute error below 2^-31 each.  The computed difference is therefore below
+    1 - 2^-21 + 2^-30 < 1, and floor values of two numbers less than 1 apart differ by at most 1.  (torch.floor of a finite double is
+    exact.)  A coordinate that is not finite, a grid of more than 2^21 - 2 cells along an axis or a group outside [0, 2^21) raises."""
+    assert xy.dtype == torch.float64 and xy.ndim == 2 and xy.shape[1] == 2 and group.dtype == torch.int32 and group.shape == (xy.shape[0],)
+    if not eps > 0:
+        raise ValueError(f"facilities: eps = {eps} (it has to be positive)")
+    h = float(eps) * FACILITY_CELL_FACTOR
+    top = (1 << FACILITY_CELL_BITS) - 2
+    cell = torch.floor((xy - xy.min(dim=0).values) / h) + 1.0
+    lo, hi = cell.aminmax()
+    g_lo, g_hi = group.aminmax()
+    lo, hi, g_lo, g_hi = (float(v) for v in torch.stack([lo, hi, g_lo.double(), g_hi.double()]).tolist())
+    if not (lo >= 1.0 and hi <= top):                       # (NaN fails too)
+        raise ValueError(f"facilities: the points span more than {top} cells of {h:g} m along an axis, or a coordinate is not finite")
+    if g_lo < 0 or g_hi >= 1 << FACILITY_CELL_BITS:
+        raise ValueError(f"facilities: group ids have to lie in [0, 2^{FACILITY_CELL_BITS})")
+    cell = cell.to(torch.int64)
+    key = (group.to(torch.int64) << (2 * FACILITY_CELL_BITS)) | (cell[:, 1] << FACILITY_CELL_BITS) | cell[:, 0]
+    keys, perm = torch.sort(key)
+    return keys, perm.to(torch.int32)
+
+
+def facility_dbscan(xy: torch.Tensor, group: torch.Tensor, eps: float, min_samples: int, stream: Optional[torch.cuda.Stream] = None,
+                    scratch: Optional[torch.Tensor] = None, times: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """aq_facility_dbscan_f64 on `stream` (default: the current one): xy float64 CUDA [n, 2] (metres), group int32 CUDA [n] (dense ids; points
+    of different groups never interact) -> (core uint8 CUDA [n], root int32 CUDA [n]) in the caller's order: root = the smallest original
+    index among the core points of the point's cluster, -1 for noise (facilities.dbscan_numpy gives the same).  The sort is torch's
+    (facility_sort_keys), the neighbour search, the union-find and the border pass are the kernels'.  times = a dict that receives
+    "sort_ms" and "kernel_ms" (HIP events; the call then waits for them)."""
+    _require_gpu()
+    lib = load_library()
+    assert xy.is_cuda and group.is_cuda and xy.dtype == torch.float64 and group.dtype == torch.int32
+    xy, group = xy.contiguous(), group.contiguous()
+    n = xy.shape[0]
+    if not eps > 0 or int(min_samples) < 1:                 # the library refuses these too; here before the sort
+        raise ValueError(f"facilities: eps = {eps}, min_samples = {min_samples} (eps > 0 and min_samples >= 1)")
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        core = torch.empty(n, dtype=torch.uint8, device=xy.device)
+        root = torch.empty(n, dtype=torch.int32, device=xy.device)
+        if n == 0:
+            _check(lib.aq_facility_dbscan_f64(None, None, None, None, 0, float(eps), int(min_samples), None, 0, None, None, _stream_ptr()))
+            return core, root
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
+        if ev:
+            ev[0].record()
+        keys, perm = facility_sort_keys(xy, group, eps)
+        need = int(lib.aq_facility_scratch_bytes(n))
+        if scratch is None or scratch.numel() < need:
+            scratch = torch.empty(need, dtype=torch.uint8, device=xy.device)
+        if ev:
+            ev[1].record()
+        _check(lib.aq_facility_dbscan_f64(keys.data_ptr(), perm.data_ptr(), xy.data_ptr(), group.data_ptr(), n, float(eps), int(min_samples),
+                                          scratch.data_ptr(), scratch.numel(), core.data_ptr(), root.data_ptr(), _stream_ptr()))
+        if ev:
+            ev[2].record()
+            ev[2].synchronize()
+            times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+        for t_ in (keys, perm, xy, group, scratch, core, root):
+            t_.record_stream(torch.cuda.current_stream())
+    return core, root
 
 
 def stem_conv_nhwc(tiles_u8: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, act: bool = True, precision: str = "bf16") -> torch.Tensor:

@@ -16,7 +16,9 @@ Pinned against the reference's own output for the pixel -> EPSG:3857 -> EPSG:432
 EPSG:3035 columns follow the published IOGP formulas and are checked against the published worked examples only (pyproj is not
 available here): they are returned as explicit easting / northing, because which of the reference's `xmin_m`/`ymin_m` columns
 receives which depends on pyproj's axis-order handling for EPSG:3035 (northing-first by authority), which cannot be checked
-without pyproj.  Out of scope, as in the reference's later steps: the land filter, de-duplication, facility clustering.
+without pyproj.  The reverse directions (lonlat_to_mercator, laea_europe_to_lonlat) serve facilities.py, which holds the reference's
+area estimates and facility clustering.  Out of scope, as in the reference's later steps: the land filter and de-duplication (both are
+polygon overlays).
 """
 from __future__ import annotations
 
@@ -110,6 +112,40 @@ def lonlat_to_laea_europe(lon_deg: np.ndarray, lat_deg: np.ndarray) -> Tuple[np.
     east = LAEA_FE + b * d * (np.cos(beta) * np.sin(lam - LAEA_LON0))
     north = LAEA_FN + (b / d) * (np.cos(beta0) * np.sin(beta) - np.sin(beta0) * np.cos(beta) * np.cos(lam - LAEA_LON0))
     return east, north
+
+
+def lonlat_to_mercator(lon_deg: np.ndarray, lat_deg: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """EPSG:4326 -> EPSG:3857 (IOGP GN7-2 method 1024, forward)."""
+    x = WGS84_A * np.radians(lon_deg)
+    y = WGS84_A * np.log(np.tan(np.pi / 4.0 + np.radians(lat_deg) / 2.0))
+    return x, y
+
+
+def laea_europe_to_lonlat(east: np.ndarray, north: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """EPSG:3035 (easting, northing) -> EPSG:4326 (lon, lat): IOGP GN7-2 method 9820, reverse.  The guidance note's series for the latitude
+    from the authalic latitude stops at e^6 (about a millimetre); two Newton steps on q(phi) = qp sin(beta') (Snyder 3-16) follow it, so
+    that the pair with lonlat_to_laea_europe closes to rounding."""
+    e2 = GRS80_F * (2.0 - GRS80_F)
+    e = np.sqrt(e2)
+    qp = _laea_q(1.0, e)
+    q0 = _laea_q(np.sin(LAEA_LAT0), e)
+    beta0 = np.arcsin(q0 / qp)
+    rq = GRS80_A * np.sqrt(qp / 2.0)
+    d = GRS80_A * (np.cos(LAEA_LAT0) / np.sqrt(1.0 - e2 * np.sin(LAEA_LAT0) ** 2)) / (rq * np.cos(beta0))
+    x, y = np.asarray(east, np.float64) - LAEA_FE, np.asarray(north, np.float64) - LAEA_FN
+    rho = np.sqrt((x / d) ** 2 + (d * y) ** 2)
+    c = 2.0 * np.arcsin(rho / (2.0 * rq))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sin_b = np.where(rho > 0, np.cos(c) * np.sin(beta0) + (d * y * np.sin(c) * np.cos(beta0)) / rho, np.sin(beta0))
+    beta = np.arcsin(sin_b)
+    lam = LAEA_LON0 + np.arctan2(x * np.sin(c), d * rho * np.cos(beta0) * np.cos(c) - d * d * y * np.sin(beta0) * np.sin(c))
+    phi = (beta + (e2 / 3.0 + 31.0 * e2 ** 2 / 180.0 + 517.0 * e2 ** 3 / 5040.0) * np.sin(2.0 * beta)
+           + (23.0 * e2 ** 2 / 360.0 + 251.0 * e2 ** 3 / 3780.0) * np.sin(4.0 * beta) + (761.0 * e2 ** 3 / 45360.0) * np.sin(6.0 * beta))
+    q = qp * sin_b
+    for _ in range(2):
+        s = np.sin(phi)
+        phi = phi + (1.0 - e2 * s * s) ** 2 / (2.0 * np.cos(phi)) * (q / (1.0 - e2) - _laea_q(s, e) / (1.0 - e2))
+    return np.degrees(lam), np.degrees(phi)
 
 
 def geocode_detections(stems: Sequence[str], counts: Sequence[int], rows: np.ndarray,

@@ -569,6 +569,29 @@ int aq_blank_ring_edges_u8(const aq_frame* frames_dev, const aq_frame* frames_ho
                            const aq_blank_geom* records_dev, const long long* edge_at_dev, const long long* edge_at_host, int32_t* edges_dev,
                            long long edges_room, void* stream);
 
+/* --facilities: DBSCAN of n points in metres, as sklearn.cluster.DBSCAN(eps, min_samples) labels them (reference src/cluster_facilities.py),
+ * per dense group id: points of different groups never interact.  core = at least min_samples points of the group, the point itself
+ * included, at dx dx + dy dy <= eps eps, evaluated in fp64 in exactly that form; a cluster = a connected component of core points; root =
+ * the smallest original index among the cluster's core points; a point that is not core takes the smallest root among its core neighbours
+ * and is noise (root -1) without one.  sklearn's label of a point is the rank of its root among the distinct roots of its group.
+ * The points are addressed through a sort the caller made: key = group << 42 | cell_y << 21 | cell_x of a square grid whose cell edge is
+ * above eps by enough that two points within eps never lie two cells apart, cell indices in [1, 2^21 - 2] (a free ring, so that the cells
+ * cx - 1 .. cx + 1 of a row are one run of the sorted keys), group in [0, 2^21); keys_sorted_dev = the keys ascending, perm_dev = the original
+ * index of every sorted position.  xy_dev ([n][2] doubles, 16-byte aligned) and group_dev stay in the caller's original order, as do the
+ * outputs core_dev (uint8 [n]) and root_dev (int32 [n]). */
+#define AQ_FACILITY_CELL_BITS 21
+#define AQ_FACILITY_CELL_MASK ((1LL << AQ_FACILITY_CELL_BITS) - 1)
+/* Scratch: 41 bytes per point (16 coordinates in sorted order, 24 key runs, 1 core flag), each array rounded up to 16 bytes; 0 for n <= 0 or
+ * n >= 2^31. */
+size_t aq_facility_scratch_bytes(long long n);
+/* On `stream`; the call initialises its scratch, allocates nothing and uses integer min atomics only, so two calls give the same bytes.
+ * n = 0 does nothing.  n >= 2^31, a null pointer, eps <= 0 (or not finite), min_samples < 1 and too little scratch are refused before
+ * anything is launched.  An entry of perm_dev outside [0, n) is skipped on the device (its point stays unwritten); keys that are not
+ * sorted or not those of the points, and a perm_dev that is no permutation, give wrong labels but no access outside the arrays. */
+int aq_facility_dbscan_f64(const long long* keys_sorted_dev, const int32_t* perm_dev, const double* xy_dev, const int32_t* group_dev, long long n,
+                           double eps, int min_samples, void* scratch_dev, size_t scratch_bytes, uint8_t* core_dev, int32_t* root_dev,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
