@@ -129,9 +129,17 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "their member detections beside them (<name>_detections.geojson); needs --geocode-bboxes")
     from .facilities import add_options as _facility_options
     _facility_options(p)
+    p.add_argument("--land-filter", default=None, metavar="GEOJSON",
+                   help="after the sweep and its geocoding, drop the detections whose boxes intersect the land polygons of GEOJSON (the reference's "
+                        "remove_land_detections, src/process_yolo/geocode_results.py:200-218; its france_final_land_filter.shp as GeoJSON), the "
+                        "box-against-polygon test on the GPU, and write what is left as the reference's ocean_detections.geojson; with "
+                        "--facilities the ocean detections are clustered, as the reference does; needs --geocode-bboxes")
+    p.add_argument("--ocean-out", default=None, metavar="GEOJSON", help="where --land-filter writes (default <save_dir>/ocean_detections.geojson)")
     opt = p.parse_args(argv)
     if opt.facilities is not None and not opt.geocode_bboxes:
         p.error("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if opt.land_filter is not None and not opt.geocode_bboxes:
+        p.error("--land-filter filters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if opt.blank_geom is not None and opt.blank_key is None:
         opt.blank_key = ""
     opt.imgsz *= 2 if len(opt.imgsz) == 1 else 1
@@ -161,13 +169,15 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         workers=8, decode_threads=False, quiet=False, geocode_bboxes=None, geocode_out=None, tile_scenes=0, autotune="auto", resume=False,
         jpeg_decode="auto", augment=False, save_crop=False, line_thickness=3, hide_labels=False, hide_conf=False, blank_key=None, blank_geom=None,
         blank_geom_simplify=0.5, facilities=None, facilities_conf=0.5, facilities_eps=10.0, facilities_min_cages=5, facilities_by="year",
-        log=print, **unsupported):
+        land_filter=None, ocean_out=None, log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb, jpeg_slots_to_rgb, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     if blank_geom is not None and blank_key is None:     # the outlines are made for the images the key calls partly blank
         blank_key = ""
     if facilities is not None and not geocode_bboxes:
         raise ValueError("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if land_filter is not None and not geocode_bboxes:
+        raise ValueError("--land-filter filters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     for k in UNSUPPORTED:
         if unsupported.get(k):
             raise NotImplementedError(f"--{k.replace('_', '-')} is not part of the tile-sweep path (reference README.md:77)")
@@ -948,6 +958,16 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             out = geocode_out or str(save_dir / "detections.geojson")
             table = geocode.geocode_label_dir(labels_dir, geocode_bboxes, out)
             log(f"{table['image'].shape[0]} detections geocoded to {out} in {time.perf_counter() - t_g:.2f}s")
+            ocean = None
+            if land_filter is not None:
+                # the step between them (reference geocode_results.py:200-218, :267-271): detections.geojson stays as it is
+                from . import land as aqland
+                t_l = time.perf_counter()
+                segs = aqland.load_land_geojson(land_filter)
+                ocean = aqland.ocean_rows(table, segs)
+                ocean_path = ocean_out or str(save_dir / "ocean_detections.geojson")
+                n_ocean = aqland.write_ocean_geojson(ocean_path, table["stems"], table, ocean)
+                log(f"{n_ocean} of {ocean.shape[0]} detections at sea ({segs.shape[0]} land edges) in {ocean_path} in {time.perf_counter() - t_l:.2f}s")
             if facilities is not None:
                 # the steps after it (reference src/process_yolo/calc_net_areas.py, src/cluster_facilities.py).  An image this rank's sweep
                 # did not see (another rank's, or one a resumed run had finished) counts as the 1024-px tile the geocoding assumes anyway.
@@ -956,7 +976,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 hw = np.asarray([image_hw.get(str(s_), (geocode.IM_HEIGHT, geocode.IM_WIDTH)) for s_ in table["stems"]], np.int64).reshape(-1, 2)
                 fac_out = facilities or str(save_dir / "facilities.geojson")
                 fac = aqfac.facilities_from_table(table, fac_out, facilities_by, facilities_conf, facilities_eps, facilities_min_cages,
-                                                  hw[table["image"], 1], hw[table["image"], 0])
+                                                  hw[table["image"], 1], hw[table["image"], 0], keep=ocean)
                 log(f"{len(fac['facility_index'])} facilities of {int((fac['_members'] >= 0).sum())} cages in {fac_out} "
                     f"in {time.perf_counter() - t_f:.2f}s")
     manifest.close()

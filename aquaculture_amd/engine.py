@@ -77,6 +77,7 @@ EXPORTS = (
     "aq_blank_stats_scratch_bytes", "aq_blank_stats_u8",
     "aq_blank_geom_scratch_bytes", "aq_blank_components_u8", "aq_blank_ring_edges_u8",
     "aq_facility_scratch_bytes", "aq_facility_dbscan_f64",
+    "aq_land_scratch_bytes", "aq_land_filter_f64",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -137,6 +138,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_facility_scratch_bytes.argtypes = [C.c_longlong]
     lib.aq_facility_scratch_bytes.restype = sz
     lib.aq_facility_dbscan_f64.argtypes = [vp, vp, vp, vp, C.c_longlong, C.c_double, i32, vp, sz, vp, vp, vp]
+    lib.aq_land_scratch_bytes.argtypes = [C.c_longlong]
+    lib.aq_land_scratch_bytes.restype = sz
+    lib.aq_land_filter_f64.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp, i32, C.c_double, C.c_double, vp, C.c_longlong, vp, sz, vp, vp]
     lib.aq_engine_set_tuned_table.argtypes = [vp, i32, i32, i32, C.POINTER(i32), i32]
     lib.aq_engine_calibrate_amax.argtypes = [vp, vp, i32, i32, i32, vp, sz, C.POINTER(f32), i32, vp]
     lib.aq_engine_set_fp8_scales.argtypes = [vp, C.POINTER(f32), i32]
@@ -1298,6 +1302,95 @@ def facility_dbscan(xy: torch.Tensor, group: torch.Tensor, eps: float, min_sampl
         for t_ in (keys, perm, xy, group, scratch, core, root):
             t_.record_stream(torch.cuda.current_stream())
     return core, root
+
+
+# ---- --land-filter: aq_land_filter_f64 (detection boxes against the segments of the land polygons) ----
+
+LAND_MAX_BANDS = 65536                     # default band count: min(this, max(1, E // 8))
+
+
+def _land_bands(y: torch.Tensor, y0: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
+    """floor((y - Y0) / h) as float64, unclamped: the kernel's expression.  y0 and h are 0-dim tensors on y's device, so that the division is a
+    division (with a Python number torch multiplies by the reciprocal on the GPU, which rounds differently at a band's edge)."""
+    return torch.floor((y - y0) / h)
+
+
+def land_band_table(segs: torch.Tensor, band_height: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor, int, float, float]:
+    """The band table aq_land_filter_f64 takes: segs float64 [E, 4] (ax, ay, bx, by), E >= 1, on any device -> (entry_seg int32 [entries],
+    band_start int32 [nbands + 1], nbands, Y0, h).  Y0 = the smallest y; band(y) = floor((y - Y0) / h); nbands = band(largest y) + 1, so no
+    segment is clamped; every segment is entered in each band from band(min y) to band(max y); the entries are sorted by band (stable: by
+    segment inside a band).  band_height = None: the y-extent divided by min(65536, max(1, E // 8)), doubled until there are at most
+    8 E + nbands entries (long segments across many thin bands); a given band_height is taken as it is.  2^31 entries or more raise."""
+    assert segs.dtype == torch.float64 and segs.ndim == 2 and segs.shape[1] == 4 and segs.shape[0] >= 1
+    E = segs.shape[0]
+    ylo, yhi = torch.minimum(segs[:, 1], segs[:, 3]), torch.maximum(segs[:, 1], segs[:, 3])
+    y0_t, top_t = ylo.min(), yhi.max()
+    Y0, top = float(y0_t), float(top_t)
+    if not (np.isfinite(Y0) and np.isfinite(top) and bool(torch.isfinite(segs).all())):
+        raise ValueError("land filter: a segment coordinate is not finite")
+    if band_height is None:
+        h = (top - Y0) / min(LAND_MAX_BANDS, max(1, E // 8))
+        if not h > 0:
+            h = 1.0                                         # every segment on one horizontal line: one band
+    else:
+        h = float(band_height)
+        if not (h > 0 and np.isfinite(h)):
+            raise ValueError(f"land filter: band height = {band_height} (it has to be positive and finite)")
+    while True:
+        h_t = torch.tensor(h, dtype=torch.float64, device=segs.device)
+        lo, hi = _land_bands(ylo, y0_t, h_t), _land_bands(yhi, y0_t, h_t)
+        nbands_f = float(hi.max()) + 1.0
+        entries_f = float((hi - lo + 1.0).sum())            # (whole numbers in fp64: exact far beyond 2^31)
+        if band_height is not None or entries_f <= 8 * E + nbands_f:
+            break
+        h *= 2.0
+    if nbands_f >= 2.0 ** 31 or entries_f >= 2.0 ** 31:
+        raise ValueError(f"land filter: {entries_f:.0f} band entries in {nbands_f:.0f} bands of {h:g} m for {E} segments (fewer than 2^31 "
+                         f"of each in one call): use a larger band height")
+    nbands, entries = int(nbands_f), int(entries_f)
+    counts = (hi - lo).to(torch.int64) + 1
+    seg_of = torch.repeat_interleave(torch.arange(E, device=segs.device), counts)
+    first = torch.cumsum(counts, 0) - counts
+    band_of = lo.to(torch.int64)[seg_of] + (torch.arange(entries, device=segs.device) - first[seg_of])
+    band_sorted, order = torch.sort(band_of, stable=True)
+    band_start = torch.searchsorted(band_sorted, torch.arange(nbands + 1, device=segs.device))
+    return seg_of[order].to(torch.int32), band_start.to(torch.int32), nbands, Y0, h
+
+
+def land_flags(boxes: torch.Tensor, segs: torch.Tensor, band_height: Optional[float] = None, times: Optional[dict] = None) -> torch.Tensor:
+    """aq_land_filter_f64 on the current stream: boxes float64 CUDA [N, 4] (x0, y0, x1, y1; x0 <= x1, y0 <= y1), segs float64 CUDA [E, 4]
+    (ax, ay, bx, by: every edge of every ring of the land) -> uint8 CUDA [N]: bit 0 = an edge meets the closed box, bit 1 = the corner
+    (x0, y0) is inside the land; not 0 = on land (land.land_flags_numpy gives the same bytes).  The band table is torch's
+    (land_band_table), the gather and the tests are the kernels'.  times = a dict that receives "table_ms" and "kernel_ms" (HIP events; the
+    call then waits for them), "entries", "nbands" and "band_height"."""
+    _require_gpu()
+    lib = load_library()
+    assert boxes.is_cuda and segs.is_cuda and boxes.dtype == torch.float64 and segs.dtype == torch.float64
+    assert boxes.ndim == 2 and boxes.shape[1] == 4 and segs.ndim == 2 and segs.shape[1] == 4
+    boxes, segs = boxes.contiguous(), segs.contiguous()
+    N, E = boxes.shape[0], segs.shape[0]
+    flags = torch.empty(N, dtype=torch.uint8, device=boxes.device)
+    if N == 0 or E == 0:
+        _check(lib.aq_land_filter_f64(None, E, None, 0, None, 1, 0.0, 1.0, None, N, None, 0, flags.data_ptr(), _stream_ptr()))
+        flags.record_stream(torch.cuda.current_stream())
+        return flags
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
+    if ev:
+        ev[0].record()
+    entry_seg, band_start, nbands, Y0, h = land_band_table(segs, band_height)
+    entries = entry_seg.shape[0]
+    scratch = torch.empty(int(lib.aq_land_scratch_bytes(entries)), dtype=torch.uint8, device=boxes.device)
+    if ev:
+        ev[1].record()
+    _check(lib.aq_land_filter_f64(segs.data_ptr(), E, entry_seg.data_ptr(), entries, band_start.data_ptr(), nbands, Y0, h, boxes.data_ptr(), N,
+                                  scratch.data_ptr(), scratch.numel(), flags.data_ptr(), _stream_ptr()))
+    if ev:
+        ev[2].record()
+        ev[2].synchronize()
+        times.update(table_ms=ev[0].elapsed_time(ev[1]), kernel_ms=ev[1].elapsed_time(ev[2]), entries=entries, nbands=nbands, band_height=h)
+    for t_ in (boxes, segs, entry_seg, band_start, scratch, flags):
+        t_.record_stream(torch.cuda.current_stream())
+    return flags
 
 
 def stem_conv_nhwc(tiles_u8: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, act: bool = True, precision: str = "bf16") -> torch.Tensor:

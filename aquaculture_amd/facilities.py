@@ -194,19 +194,25 @@ def _wkt_multipolygon(table, members: np.ndarray) -> str:
 
 
 def cluster(table: Dict[str, np.ndarray], by: str = "year", conf_thresh: float = 0.5, eps: float = 10.0, min_cages: int = 5,
-            widths=geocode.IM_WIDTH, heights=geocode.IM_HEIGHT, labels_fn: Optional[Callable] = None) -> Dict[str, list]:
+            widths=geocode.IM_WIDTH, heights=geocode.IM_HEIGHT, labels_fn: Optional[Callable] = None, keep=None) -> Dict[str, list]:
     """The reference's facility table (predictions_cluster) as columns: num_square_farms, num_circle_farms, num_rectangle_farms, `by`
     (``year`` or ``pass``: the image pass of the year), noise_points (of the facility's group), square_/circle_/rectangle_farm_geoms
     (MULTIPOLYGON WKT, EPSG:3857), cage_ids (row numbers in `table`: the reference's ``index``), area, area_var, min_area, max_area
     (sums over the members, NaN skipped as pandas skips them), facility_index, x_3857 / y_3857 (the Point: the mean of the members'
     EPSG:3035 centroids, delivered in EPSG:3857) and, beside the reference's, x_3035 / y_3035.  Facilities are ordered by group in
-    order of first appearance, then by label.  Detections with det_conf >= conf_thresh take part.  labels_fn(xy, group, eps,
-    min_samples) -> (labels, core[, ...]); default dbscan_labels (the GPU).  The result also carries ``_members``: per detection of
+    order of first appearance, then by label.  Detections with det_conf >= conf_thresh take part; with keep (bool per detection: the
+    land filter's ocean rows) only those of them with keep[k] -- cage_ids and ``_members`` stay row numbers of the full table.
+    labels_fn(xy, group, eps, min_samples) -> (labels, core[, ...]); default dbscan_labels (the GPU).  The result also carries ``_members``: per detection of
     `table` its facility_index or -1, and ``_areas``: net_areas of the whole table."""
     if by not in ("year", "pass"):
         raise ValueError(f"facilities: cluster by 'year' or 'pass', not {by!r}")
     n_all = np.asarray(table["det_conf"]).shape[0]
-    keep = np.nonzero(np.asarray(table["det_conf"], np.float64) >= conf_thresh)[0]
+    take = np.asarray(table["det_conf"], np.float64) >= conf_thresh
+    if keep is not None:
+        if np.asarray(keep).shape != (n_all,):
+            raise ValueError(f"facilities: keep has shape {np.asarray(keep).shape}, the table {n_all} detections")
+        take &= np.asarray(keep, bool)
+    keep = np.nonzero(take)[0]
     years = np.asarray(table["year"], np.int64)[keep]
     values = [int(y) for y in years] if by == "year" else [image_pass(int(y)) for y in years]
     order: Dict[object, int] = {}
@@ -291,9 +297,10 @@ def write_facility_detections_geojson(path: str, table: Dict[str, np.ndarray], f
 
 
 def facilities_from_table(table: Dict[str, np.ndarray], out_geojson: str, by: str = "year", conf_thresh: float = 0.5, eps: float = 10.0,
-                          min_cages: int = 5, widths=geocode.IM_WIDTH, heights=geocode.IM_HEIGHT, cpu: bool = False) -> Dict[str, list]:
-    """cluster() and both files: `out_geojson` and <out>_detections.geojson.  cpu = labels from dbscan_numpy instead of the GPU."""
-    fac = cluster(table, by, conf_thresh, eps, min_cages, widths, heights, labels_fn=dbscan_numpy if cpu else None)
+                          min_cages: int = 5, widths=geocode.IM_WIDTH, heights=geocode.IM_HEIGHT, cpu: bool = False, keep=None) -> Dict[str, list]:
+    """cluster() and both files: `out_geojson` and <out>_detections.geojson.  cpu = labels from dbscan_numpy instead of the GPU; keep =
+    cluster()'s (the land filter's ocean rows)."""
+    fac = cluster(table, by, conf_thresh, eps, min_cages, widths, heights, labels_fn=dbscan_numpy if cpu else None, keep=keep)
     write_facilities_geojson(out_geojson, fac)
     write_facility_detections_geojson(detections_path(out_geojson), table, fac)
     return fac

@@ -17,8 +17,8 @@ EPSG:3035 columns follow the published IOGP formulas and are checked against the
 available here): they are returned as explicit easting / northing, because which of the reference's `xmin_m`/`ymin_m` columns
 receives which depends on pyproj's axis-order handling for EPSG:3035 (northing-first by authority), which cannot be checked
 without pyproj.  The reverse directions (lonlat_to_mercator, laea_europe_to_lonlat) serve facilities.py, which holds the reference's
-area estimates and facility clustering.  Out of scope, as in the reference's later steps: the land filter and de-duplication (both are
-polygon overlays).
+area estimates and facility clustering; land.py holds the land filter that the reference runs in between.  Out of scope, as in the
+reference's later steps: the de-duplication (a polygon overlay).
 """
 from __future__ import annotations
 
@@ -210,24 +210,29 @@ def label_dir_rows(labels_dir: str) -> Tuple[List[str], List[int], np.ndarray]:
 def write_geojson(path: str, stems: Sequence[str], table: Dict[str, np.ndarray]) -> int:
     """FeatureCollection in EPSG:4326 with the reference's property names where they are unambiguous (image, xmin, xmax, ymin,
     ymax, type, year, det_conf) and explicit e/n names for the EPSG:3035 corners.  Returns the number of features."""
-    feats = []
     n = table["image"].shape[0]
-    for k in range(n):
-        x0, x1, y0, y1 = (float(table[c][k]) for c in ("lon_min", "lon_max", "lat_min", "lat_max"))
-        feats.append({"type": "Feature",
-                      "properties": {"image": stems[int(table["image"][k])] + ".jpeg",
-                                     "xmin": int(table["xmin"][k]), "xmax": int(table["xmax"][k]),
-                                     "ymin": int(table["ymin"][k]), "ymax": int(table["ymax"][k]),
-                                     "e_min_3035": float(table["e_min_3035"][k]), "e_max_3035": float(table["e_max_3035"][k]),
-                                     "n_min_3035": float(table["n_min_3035"][k]), "n_max_3035": float(table["n_max_3035"][k]),
-                                     "type": REVERSE_CLASS_MAPPING[int(table["cls"][k])], "year": int(table["year"][k]),
-                                     "det_conf": float(table["det_conf"][k])},
-                      # shapely.geometry.box(minx, miny, maxx, maxy) ring order: (maxx, miny), (maxx, maxy), (minx, maxy), (minx, miny)
-                      "geometry": {"type": "Polygon", "coordinates": [[[x1, y0], [x1, y1], [x0, y1], [x0, y0], [x1, y0]]]}})
+    feats = [feature(stems, table, k) for k in range(n)]
     with open(path, "w") as f:
-        json.dump({"type": "FeatureCollection", "crs": {"type": "name", "properties": {"name": "urn:ogc:def:crs:OGC:1.3:CRS84"}},
-                   "features": feats}, f)
+        json.dump({"type": "FeatureCollection", "crs": CRS84, "features": feats}, f)
     return n
+
+
+CRS84 = {"type": "name", "properties": {"name": "urn:ogc:def:crs:OGC:1.3:CRS84"}}
+
+
+def feature(stems: Sequence[str], table: Dict[str, np.ndarray], k: int) -> dict:
+    """Detection k of `table` as write_geojson writes it (land.write_ocean_geojson writes the same features for the rows it keeps)."""
+    x0, x1, y0, y1 = (float(table[c][k]) for c in ("lon_min", "lon_max", "lat_min", "lat_max"))
+    return {"type": "Feature",
+            "properties": {"image": stems[int(table["image"][k])] + ".jpeg",
+                           "xmin": int(table["xmin"][k]), "xmax": int(table["xmax"][k]),
+                           "ymin": int(table["ymin"][k]), "ymax": int(table["ymax"][k]),
+                           "e_min_3035": float(table["e_min_3035"][k]), "e_max_3035": float(table["e_max_3035"][k]),
+                           "n_min_3035": float(table["n_min_3035"][k]), "n_max_3035": float(table["n_max_3035"][k]),
+                           "type": REVERSE_CLASS_MAPPING[int(table["cls"][k])], "year": int(table["year"][k]),
+                           "det_conf": float(table["det_conf"][k])},
+            # shapely.geometry.box(minx, miny, maxx, maxy) ring order: (maxx, miny), (maxx, maxy), (minx, maxy), (minx, miny)
+            "geometry": {"type": "Polygon", "coordinates": [[[x1, y0], [x1, y1], [x0, y1], [x0, y0], [x1, y0]]]}}
 
 
 def geocode_label_dir(labels_dir: str, wanted_bboxes_csv: str, out_geojson: str | None = None) -> Dict[str, np.ndarray]:

@@ -592,6 +592,28 @@ int aq_facility_dbscan_f64(const long long* keys_sorted_dev, const int32_t* perm
                            double eps, int min_samples, void* scratch_dev, size_t scratch_bytes, uint8_t* core_dev, int32_t* root_dev,
                            void* stream);
 
+/* --land-filter: which of N boxes (x0, y0, x1, y1; x0 <= x1, y0 <= y1) lie on land (reference src/process_yolo/geocode_results.py:200-218:
+ * sjoin with the predicate `intersects`), against the E segments (ax, ay, bx, by) of all rings of the land polygons, exterior and holes
+ * alike; everything fp64, EPSG:3857 metres.  One byte per box: bit 0 = some segment meets the closed box (the bounding boxes overlap, closed,
+ * and the box's four corners are not all strictly on one side of the segment's line), bit 1 = the corner (x0, y0) is inside the land under
+ * the even-odd rule (crossings of the ray towards +x, half-open in y: (ay <= y0) != (by <= y0), the corner strictly left of an upward
+ * segment or strictly right of a downward one).  Both use the sign of orient(a, b, c) = (bx - ax) (cy - ay) - (by - ay) (cx - ax) in exactly
+ * that form.  The box is on land when the byte is not 0; touching counts.
+ * The segments are addressed through a band table the caller made: band(y) = floor((y - Y0) / h) clamped to [0, nbands), every segment
+ * entered in each band from band(min y) to band(max y); entry_seg_dev = the entries' segment indices band by band, band_start_dev
+ * [nbands + 1] = each band's first entry, band_start_dev[nbands] = entries.  A box wholly below Y0 or with floor((y0 - Y0) / h) >= nbands
+ * gets 0: the table has to cover every segment without clamping (floor((max y - Y0) / h) < nbands), as engine.land_flags builds it. */
+/* Scratch: 32 bytes per entry (the segments' coordinates in entry order); 0 for entries <= 0 or entries >= 2^31. */
+size_t aq_land_scratch_bytes(long long entries);
+/* On `stream`; the call initialises its scratch, allocates nothing and uses no atomics, so two calls give the same bytes.  N = 0 does nothing;
+ * E = 0 (or entries = 0) zeroes flags_dev.  E, N or entries >= 2^31, h <= 0, h or Y0 not finite, nbands < 1, a null pointer, seg_dev, boxes_dev
+ * or scratch_dev not 32-byte aligned and too little scratch are refused before anything is launched.  An entry outside [0, E) meets nothing
+ * and band starts are kept inside [0, entries] on the device, so a table the caller got wrong gives wrong flags but no access outside the
+ * arrays. */
+int aq_land_filter_f64(const double* seg_dev, long long E, const int32_t* entry_seg_dev, long long entries, const int32_t* band_start_dev,
+                       int nbands, double Y0, double h, const double* boxes_dev, long long N, void* scratch_dev, size_t scratch_bytes,
+                       uint8_t* flags_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
