@@ -6,10 +6,8 @@
 //   cluster  a connected component of core points under that relation; its root is the smallest original index among its core points
 //   border   a point that is not core takes the smallest root among its core neighbours (sklearn grows clusters in label order, so that
 //            cluster reaches the point first); without a core neighbour it is noise: root -1
-// The caller sorts the points by a key that packs (group, cell row, cell column) of a grid whose cell edge is a little above eps, so that
-// every neighbour of a point lies in the 3 x 3 cells around its own, and the three cells cx - 1 .. cx + 1 of one cell row are ONE run of the
-// sorted keys: two binary searches per row, no hash table, no O(n^2) memory.  One thread per point, in sorted order, so that the threads of
-// a wave read the same runs.  Launches of one call, all on the caller's stream:
+// The neighbour search (the caller's sort by grid cell, the three key runs of every point, one thread per point in sorted order) is
+// facility_runs.h, which evaluate.hip shares.  Launches of one call, all on the caller's stream:
 //   gather   the points' coordinates in sorted order (the runs are read contiguously from here on), the three runs of every point
 //   count    neighbours in the runs -> core (also by sorted position); root = the point itself for a core point, else -1
 //   unite    every core-core pair once (from its later point): find, then atomicMin on the larger root until both agree, in the forest that
@@ -18,20 +16,13 @@
 //   border   the minimum root among the core neighbours of every point that is not core
 // Only integer min atomics, whose result does not depend on their order: two calls give the same bytes.  Unbounded loops: find (parents
 // decrease strictly) and unite (the larger of the two roots decreases strictly).
-#include "aq_common.h"
+#include "facility_runs.h"
 #include <limits.h>
 
 namespace {
 
-struct FacParams {
-    const long long* keys;     // [n] ascending
-    const int* perm;           // [n] sorted position -> original index
-    const double* xy;          // [n][2], original order
-    const int* group;          // [n], original order
-    int n, min_samples;
-    double eps2;
-    double2* sxy;              // scratch [n]: coordinates by sorted position
-    int2* runs;                // scratch [n][3]: [first, end) sorted positions of the cell rows cy - 1, cy, cy + 1
+struct FacParams : FacRuns {   // (the sorted keys, the points and the scratch of the gather: facility_runs.h)
+    int min_samples;
     unsigned char* score;      // scratch [n]: core, by sorted position
     unsigned char* core;       // out [n]
     int* root;                 // out [n]; the forest meanwhile
@@ -56,66 +47,17 @@ __device__ void unite(int* parent, int a, int b) {
     }
 }
 
-// first position in [0, n) whose key is >= k (upper = false) or > k (upper = true); n if none
-__device__ __forceinline__ int bound(const long long* keys, int n, long long k, bool upper) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        const long long v = keys[mid];
-        if (upper ? v <= k : v < k) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// original index of the point at sorted position k, or -1 for an entry that is no index (a permutation the caller did not check)
-__device__ __forceinline__ int orig(const FacParams& p, int k) {
-    const int o = p.perm[k];
-    return (unsigned)o < (unsigned)p.n ? o : -1;
-}
-
 __global__ __launch_bounds__(256) void fac_gather_kernel(const FacParams p) {
     const long long i = blockIdx.x * 256LL + threadIdx.x;
-    if (i >= p.n) return;
-    const int o = orig(p, (int)i);
-    double2 v = {0.0, 0.0};
-    if (o >= 0) v = *(const double2*)(p.xy + 2LL * o);
-    p.sxy[i] = v;
-    const long long key = p.keys[i];
-    const long long cx = key & AQ_FACILITY_CELL_MASK, cy = (key >> AQ_FACILITY_CELL_BITS) & AQ_FACILITY_CELL_MASK;
-    const long long g = o >= 0 ? (long long)p.group[o] : 0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        int2 run = {0, 0};                                                      // a cell at the grid's edge (the caller leaves a free ring) or a bad entry: no run
-        if (o >= 0 && g >= 0 && g <= AQ_FACILITY_CELL_MASK && cx >= 1 && cx < AQ_FACILITY_CELL_MASK && cy + r >= 1 && cy + r - 1 <= AQ_FACILITY_CELL_MASK) {
-            const long long row = (g << (2 * AQ_FACILITY_CELL_BITS)) | ((cy + r - 1) << AQ_FACILITY_CELL_BITS);
-            run.x = bound(p.keys, p.n, row | (cx - 1), false);
-            run.y = bound(p.keys, p.n, row | (cx + 1), true);
-        }
-        p.runs[3 * i + r] = run;
-    }
-}
-
-// f(k) for the sorted positions k of the points within eps in the runs of sorted position i, the point itself included
-template <typename F>
-__device__ __forceinline__ void neighbours(const FacParams& p, long long i, F f) {
-    const double2 a = p.sxy[i];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const int2 run = p.runs[3 * i + r];
-        for (int k = run.x; k < run.y; ++k) {
-            const double2 b = p.sxy[k];
-            const double dx = b.x - a.x, dy = b.y - a.y;
-            if (dx * dx + dy * dy <= p.eps2) f(k);
-        }
-    }
+    if (i < p.n) fac_gather(p, i);
 }
 
 __global__ __launch_bounds__(256) void fac_count_kernel(const FacParams p) {
     const long long i = blockIdx.x * 256LL + threadIdx.x;
     if (i >= p.n) return;
-    const int o = orig(p, (int)i);
+    const int o = fac_orig(p, (int)i);
     int cnt = 0;
-    neighbours(p, i, [&](int) { ++cnt; });
+    fac_neighbours(p, i, [&](int) { ++cnt; });
     const bool c = o >= 0 && cnt >= p.min_samples;
     p.score[i] = c ? 1 : 0;
     if (o >= 0) {
@@ -127,27 +69,27 @@ __global__ __launch_bounds__(256) void fac_count_kernel(const FacParams p) {
 __global__ __launch_bounds__(256) void fac_unite_kernel(const FacParams p) {
     const long long i = blockIdx.x * 256LL + threadIdx.x;
     if (i >= p.n || !p.score[i]) return;
-    const int o = orig(p, (int)i);
-    neighbours(p, i, [&](int k) {
-        if (k < i && p.score[k]) unite(p.root, o, orig(p, k));                  // (core entries have an index: count made sure)
+    const int o = fac_orig(p, (int)i);
+    fac_neighbours(p, i, [&](int k) {
+        if (k < i && p.score[k]) unite(p.root, o, fac_orig(p, k));                  // (core entries have an index: count made sure)
     });
 }
 
 __global__ __launch_bounds__(256) void fac_flatten_kernel(const FacParams p) {
     const long long i = blockIdx.x * 256LL + threadIdx.x;
     if (i >= p.n || !p.score[i]) return;
-    const int o = orig(p, (int)i);
+    const int o = fac_orig(p, (int)i);
     __hip_atomic_store(p.root + o, find(p.root, o), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (still an ancestor for whoever reads it meanwhile)
 }
 
 __global__ __launch_bounds__(256) void fac_border_kernel(const FacParams p) {
     const long long i = blockIdx.x * 256LL + threadIdx.x;
     if (i >= p.n || p.score[i]) return;
-    const int o = orig(p, (int)i);
+    const int o = fac_orig(p, (int)i);
     if (o < 0) return;
     int best = INT_MAX;
-    neighbours(p, i, [&](int k) {
-        if (p.score[k]) best = min(best, p.root[orig(p, k)]);                   // flat: a core point's root is its cluster's
+    fac_neighbours(p, i, [&](int k) {
+        if (p.score[k]) best = min(best, p.root[fac_orig(p, k)]);                   // flat: a core point's root is its cluster's
     });
     if (best != INT_MAX) p.root[o] = best;                                      // (nobody reads the root of a point that is not core)
 }

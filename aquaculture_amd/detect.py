@@ -135,11 +135,27 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "box-against-polygon test on the GPU, and write what is left as the reference's ocean_detections.geojson; with "
                         "--facilities the ocean detections are clustered, as the reference does; needs --geocode-bboxes")
     p.add_argument("--ocean-out", default=None, metavar="GEOJSON", help="where --land-filter writes (default <save_dir>/ocean_detections.geojson)")
+    p.add_argument("--evaluate", default=None, metavar="TRUTH_GEOJSON",
+                   help="after the sweep, its geocoding, the land filter and the facilities, score the circle and square detections against the "
+                        "human labels of TRUTH_GEOJSON (the reference's output/humanlabels.geojson) over the tuning grid of confidence threshold x "
+                        "DBSCAN distance x minimum cluster size (the reference's src/get_kfold_cluster_performance.py), the neighbour search and "
+                        "the box joins on the GPU, and write cluster_performance.csv and evaluation.json (the best rows, and the numbers at "
+                        "--facilities-conf / -eps / -min-cages); with --land-filter the ocean detections are scored; needs --geocode-bboxes")
+    from .evaluate import add_options as _evaluate_options
+    _evaluate_options(p)
     opt = p.parse_args(argv)
     if opt.facilities is not None and not opt.geocode_bboxes:
         p.error("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if opt.land_filter is not None and not opt.geocode_bboxes:
         p.error("--land-filter filters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if opt.evaluate is not None and not opt.geocode_bboxes:
+        p.error("--evaluate scores geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if opt.evaluate is not None:
+        from .evaluate import grids_from_options
+        try:
+            grids_from_options(opt.evaluate_conf, opt.evaluate_eps, opt.evaluate_min_cages)
+        except ValueError as e:
+            p.error(str(e))
     if opt.blank_geom is not None and opt.blank_key is None:
         opt.blank_key = ""
     opt.imgsz *= 2 if len(opt.imgsz) == 1 else 1
@@ -169,7 +185,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         workers=8, decode_threads=False, quiet=False, geocode_bboxes=None, geocode_out=None, tile_scenes=0, autotune="auto", resume=False,
         jpeg_decode="auto", augment=False, save_crop=False, line_thickness=3, hide_labels=False, hide_conf=False, blank_key=None, blank_geom=None,
         blank_geom_simplify=0.5, facilities=None, facilities_conf=0.5, facilities_eps=10.0, facilities_min_cages=5, facilities_by="year",
-        land_filter=None, ocean_out=None, log=print, **unsupported):
+        land_filter=None, ocean_out=None, evaluate=None, evaluate_out=None, evaluate_conf=None, evaluate_eps=None, evaluate_min_cages=None,
+        evaluate_images=None, log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb, jpeg_slots_to_rgb, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     if blank_geom is not None and blank_key is None:     # the outlines are made for the images the key calls partly blank
@@ -178,6 +195,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         raise ValueError("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if land_filter is not None and not geocode_bboxes:
         raise ValueError("--land-filter filters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if evaluate is not None and not geocode_bboxes:
+        raise ValueError("--evaluate scores geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     for k in UNSUPPORTED:
         if unsupported.get(k):
             raise NotImplementedError(f"--{k.replace('_', '-')} is not part of the tile-sweep path (reference README.md:77)")
@@ -979,6 +998,15 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                                                   hw[table["image"], 1], hw[table["image"], 0], keep=ocean)
                 log(f"{len(fac['facility_index'])} facilities of {int((fac['_members'] >= 0).sum())} cages in {fac_out} "
                     f"in {time.perf_counter() - t_f:.2f}s")
+            if evaluate is not None:
+                # the reference's tuning step (src/get_kfold_cluster_performance.py) on the same table, the ocean rows when there are any
+                from . import evaluate as aqeval
+                t_e = time.perf_counter()
+                grids = aqeval.grids_from_options(evaluate_conf, evaluate_eps, evaluate_min_cages)
+                ev_out = evaluate_out or str(save_dir)
+                ev = aqeval.evaluate_table(table, evaluate, ev_out, *grids, op=(facilities_conf, facilities_eps, facilities_min_cages), keep=ocean,
+                                           images=aqeval.read_image_list(evaluate_images) if evaluate_images else None)
+                log(f"{aqeval.describe(ev)} in {ev_out} in {time.perf_counter() - t_e:.2f}s")
     manifest.close()
     eng.close()
     return save_dir

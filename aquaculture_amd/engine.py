@@ -78,6 +78,7 @@ EXPORTS = (
     "aq_blank_geom_scratch_bytes", "aq_blank_components_u8", "aq_blank_ring_edges_u8",
     "aq_facility_scratch_bytes", "aq_facility_dbscan_f64",
     "aq_land_scratch_bytes", "aq_land_filter_f64",
+    "aq_eval_scratch_bytes", "aq_eval_member_conf_f64", "aq_box_match_f64",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -141,6 +142,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_land_scratch_bytes.argtypes = [C.c_longlong]
     lib.aq_land_scratch_bytes.restype = sz
     lib.aq_land_filter_f64.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp, i32, C.c_double, C.c_double, vp, C.c_longlong, vp, sz, vp, vp]
+    lib.aq_eval_scratch_bytes.argtypes = [C.c_longlong, i32]
+    lib.aq_eval_scratch_bytes.restype = sz
+    lib.aq_eval_member_conf_f64.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, C.c_double, i32, vp, sz, vp, vp]
+    lib.aq_box_match_f64.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, vp, i32, vp, i32, vp, vp, vp]
     lib.aq_engine_set_tuned_table.argtypes = [vp, i32, i32, i32, C.POINTER(i32), i32]
     lib.aq_engine_calibrate_amax.argtypes = [vp, vp, i32, i32, i32, vp, sz, C.POINTER(f32), i32, vp]
     lib.aq_engine_set_fp8_scales.argtypes = [vp, C.POINTER(f32), i32]
@@ -1302,6 +1307,101 @@ def facility_dbscan(xy: torch.Tensor, group: torch.Tensor, eps: float, min_sampl
         for t_ in (keys, perm, xy, group, scratch, core, root):
             t_.record_stream(torch.cuda.current_stream())
     return core, root
+
+
+# ---- --evaluate: aq_eval_member_conf_f64 and aq_box_match_f64 (the precision / recall grid without a DBSCAN run per grid point) ----
+
+EVAL_MAX_K = 16
+
+
+def eval_member_conf(xy: torch.Tensor, group: torch.Tensor, conf: torch.Tensor, eps: float, K: int, times: Optional[dict] = None) -> torch.Tensor:
+    """aq_eval_member_conf_f64 on the current stream: xy float64 CUDA [n, 2] (metres), group int32 CUDA [n] (dense ids), conf float64 CUDA [n]
+    -> M float64 CUDA [n, K] in the caller's order: M[i, m - 1] = the largest confidence threshold at which DBSCAN(eps, min_samples = m) over
+    the points of at least that confidence makes point i a member of a cluster (-inf: none); evaluate.member_conf_numpy gives the same
+    bytes.  The sort is torch's (facility_sort_keys).  times = a dict that receives "sort_ms" and "kernel_ms" (HIP events; the call then
+    waits for them)."""
+    _require_gpu()
+    lib = load_library()
+    assert xy.is_cuda and group.is_cuda and conf.is_cuda and xy.dtype == torch.float64 and group.dtype == torch.int32 and conf.dtype == torch.float64
+    xy, group, conf = xy.contiguous(), group.contiguous(), conf.contiguous()
+    n = xy.shape[0]
+    assert xy.shape == (n, 2) and group.shape == (n,) and conf.shape == (n,)
+    if not eps > 0 or not 1 <= int(K) <= EVAL_MAX_K:        # the library refuses these too; here before the sort
+        raise ValueError(f"evaluate: eps = {eps}, K = {K} (eps > 0 and 1 <= K <= {EVAL_MAX_K})")
+    M = torch.empty((n, int(K)), dtype=torch.float64, device=xy.device)
+    if n == 0:
+        _check(lib.aq_eval_member_conf_f64(None, None, None, None, None, 0, float(eps), int(K), None, 0, None, _stream_ptr()))
+        return M
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
+    if ev:
+        ev[0].record()
+    keys, perm = facility_sort_keys(xy, group, eps)
+    scratch = torch.empty(int(lib.aq_eval_scratch_bytes(n, int(K))), dtype=torch.uint8, device=xy.device)
+    if ev:
+        ev[1].record()
+    _check(lib.aq_eval_member_conf_f64(keys.data_ptr(), perm.data_ptr(), xy.data_ptr(), group.data_ptr(), conf.data_ptr(), n, float(eps), int(K),
+                                       scratch.data_ptr(), scratch.numel(), M.data_ptr(), _stream_ptr()))
+    if ev:
+        ev[2].record()
+        ev[2].synchronize()
+        times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+    for t_ in (keys, perm, xy, group, conf, scratch, M):
+        t_.record_stream(torch.cuda.current_stream())
+    return M
+
+
+def box_match_sort(kbox: torch.Tensor, kgroup: torch.Tensor, G: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The key order aq_box_match_f64 takes: kbox float64 [N, 4], kgroup int32 [N] with ids in [0, G) -> (order int64 [N]: by (group, x0),
+    stable; group_start int32 [G + 1])."""
+    by_x = torch.sort(kbox[:, 0], stable=True).indices
+    order = by_x[torch.sort(kgroup[by_x], stable=True).indices]
+    start = torch.searchsorted(kgroup[order].to(torch.int64), torch.arange(G + 1, device=kbox.device))
+    return order, start.to(torch.int32)
+
+
+def box_match(qbox: torch.Tensor, qgroup: torch.Tensor, kbox: torch.Tensor, kgroup: torch.Tensor, G: int, payload: Optional[torch.Tensor] = None,
+              times: Optional[dict] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """aq_box_match_f64 on the current stream: qbox float64 CUDA [Q, 4] (x0, y0, x1, y1), qgroup int32 CUDA [Q], kbox float64 CUDA [N, 4],
+    kgroup int32 CUDA [N] with ids in [0, G), in any order (box_match_sort sorts them), payload float64 CUDA [N, K] or None ->
+    (hit uint8 CUDA [Q]: the query's closed box meets the closed box of a key of its group; out float64 CUDA [Q, K]: the elementwise
+    maximum of the payload over those keys, -inf without one -- None without a payload).  evaluate.box_match_numpy gives the same bytes.
+    times = a dict that receives "sort_ms" and "kernel_ms"."""
+    _require_gpu()
+    lib = load_library()
+    assert qbox.is_cuda and qbox.dtype == torch.float64 and kbox.dtype == torch.float64 and qgroup.dtype == torch.int32 and kgroup.dtype == torch.int32
+    qbox, qgroup = qbox.contiguous(), qgroup.contiguous()
+    Q, N, G = qbox.shape[0], kbox.shape[0], int(G)
+    assert qbox.shape == (Q, 4) and kbox.shape == (N, 4) and qgroup.shape == (Q,) and kgroup.shape == (N,)
+    if G < 0 or (N and not (0 <= int(kgroup.min()) and int(kgroup.max()) < G)):
+        raise ValueError(f"box match: the keys' group ids have to lie in [0, {G})")
+    K = 0
+    if payload is not None:
+        assert payload.is_cuda and payload.dtype == torch.float64 and payload.ndim == 2 and payload.shape[0] == N
+        K = payload.shape[1]
+        if not 1 <= K <= EVAL_MAX_K:
+            raise ValueError(f"box match: {K} payload columns (1 to {EVAL_MAX_K})")
+    hit = torch.empty(Q, dtype=torch.uint8, device=qbox.device)
+    out = torch.empty((Q, K), dtype=torch.float64, device=qbox.device) if payload is not None else None
+    if Q == 0:
+        return hit, out
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
+    if ev:
+        ev[0].record()
+    order, start = box_match_sort(kbox, kgroup, G)
+    kb = kbox[order].contiguous()
+    pl = payload[order].contiguous() if payload is not None else None
+    if ev:
+        ev[1].record()
+    _check(lib.aq_box_match_f64(qbox.data_ptr(), qgroup.data_ptr(), Q, kb.data_ptr() if N else None, N, start.data_ptr(), G,
+                                pl.data_ptr() if pl is not None and N else None, K, hit.data_ptr(), out.data_ptr() if out is not None else None,
+                                _stream_ptr()))
+    if ev:
+        ev[2].record()
+        ev[2].synchronize()
+        times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+    for t_ in (qbox, qgroup, kb, start, hit) + ((pl, out) if pl is not None else ()):
+        t_.record_stream(torch.cuda.current_stream())
+    return hit, out
 
 
 # ---- --land-filter: aq_land_filter_f64 (detection boxes against the segments of the land polygons) ----

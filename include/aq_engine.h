@@ -592,6 +592,30 @@ int aq_facility_dbscan_f64(const long long* keys_sorted_dev, const int32_t* perm
                            double eps, int min_samples, void* scratch_dev, size_t scratch_bytes, uint8_t* core_dev, int32_t* root_dev,
                            void* stream);
 
+/* ---- --evaluate (evaluate.hip): the device steps of the cage-level precision / recall grid (reference src/get_kfold_cluster_performance.py) ----
+ * aq_eval_member_conf_f64: for the points, sort and groups of aq_facility_dbscan_f64 and a confidence per point (conf_dev, [n] doubles, original
+ * order), member_conf_dev[i][m - 1] (doubles [n][K], original order) = the largest confidence threshold c at which sklearn's DBSCAN(eps,
+ * min_samples = m) over the points of confidence >= c gives point i a label >= 0: min(c_i, max over the points j within eps of i of
+ * min(c_j, m-th largest confidence within eps of j)), -inf where no threshold does.  Every value is one of the inputs, bit for bit. */
+/* Scratch: 48 + 8 K bytes per point (coordinates, key runs, confidences in sorted order and the core thresholds), each array rounded up to
+ * 16 bytes; 0 for n <= 0, n >= 2^31 or K outside 1 .. 16. */
+size_t aq_eval_scratch_bytes(long long n, int K);
+/* On `stream`; the call initialises its scratch, allocates nothing and uses no atomics, so two calls give the same bytes.  n = 0 does nothing.
+ * n >= 2^31, K outside 1 .. 16, a null pointer, eps <= 0 (or not finite), an unaligned array and too little scratch are refused before
+ * anything is launched.  Keys and a perm_dev the caller got wrong give wrong values but no access outside the arrays (as above). */
+int aq_eval_member_conf_f64(const long long* keys_sorted_dev, const int32_t* perm_dev, const double* xy_dev, const int32_t* group_dev,
+                            const double* conf_dev, long long n, double eps, int K, void* scratch_dev, size_t scratch_bytes,
+                            double* member_conf_dev, void* stream);
+/* aq_box_match_f64: Q query boxes (qbox_dev [Q][4] doubles x0, y0, x1, y1, 32-byte aligned; qgroup_dev [Q]) against N key boxes (kbox_dev [N][4],
+ * 32-byte aligned) sorted by (group, x0), group_start_dev [G + 1] = each group's first key, group_start_dev[G] = N.  hit_dev[q] (uint8) = 1 if
+ * the closed box of query q intersects the closed box of a key of its group (touching edges and corners count), else 0; a group outside
+ * [0, G) matches nothing.  With payload_dev ([N][K] doubles, K in 1 .. 16) out_dev[q][m] = the maximum of payload[k][m] over the matching
+ * keys k, -inf when none match; without one (K = 0) neither pointer is used.  On `stream`, no atomics, one launch; Q = 0 does nothing.
+ * Q or N >= 2^31, G < 0, K out of range, a null pointer and an unaligned array are refused before anything is launched; group starts are
+ * kept inside [0, N] on the device. */
+int aq_box_match_f64(const double* qbox_dev, const int32_t* qgroup_dev, long long Q, const double* kbox_dev, long long N,
+                     const int32_t* group_start_dev, int G, const double* payload_dev, int K, uint8_t* hit_dev, double* out_dev, void* stream);
+
 /* --land-filter: which of N boxes (x0, y0, x1, y1; x0 <= x1, y0 <= y1) lie on land (reference src/process_yolo/geocode_results.py:200-218:
  * sjoin with the predicate `intersects`), against the E segments (ax, ay, bx, by) of all rings of the land polygons, exterior and holes
  * alike; everything fp64, EPSG:3857 metres.  One byte per box: bit 0 = some segment meets the closed box (the bounding boxes overlap, closed,
