@@ -1821,18 +1821,16 @@ def jpeg_slots_to_rgb(slots: torch.Tensor, H: int, W: int, scratch: Optional[tor
     return jpeg_idct_rgb(slots.view(torch.int16).reshape(-1), off, qt, H, W, scratch=scratch)
 
 
-def head_decode_level(x: torch.Tensor, w_oi: torch.Tensor, bias: torch.Tensor, cand_off: int, stride: float, anchors_px, nc: int,
-                      conf_thres: float, cap: int):
-    """One Detect level through aq_head_decode (tests): x bf16 NHWC [B, ny, nx, cin] (may be a channel slice), w [na * (nc + 5), cin].
-    Returns (counts [B] int32, cand [B, cap] int32, rows [B, cap, nc + 5] float32); the order within an image is unspecified."""
-    _require_gpu()
+def _head_level_buffers(x: torch.Tensor, w_oi: torch.Tensor, bias: torch.Tensor, anchors_px, nc: int, cap: int, count_stride: int,
+                        counts, cand, rows):
+    """Packed weights, anchors and the output buffers of one aq_head_decode[_aug] call (tests).  Without caller-supplied buffers: zeroed
+    counters [(B - 1) * count_stride + 1], cand [B, cap] filled with -1, zeroed rows [B, cap, nc + 5]; supplied ones are appended to."""
     lib = load_library()
     assert x.dtype == torch.bfloat16 and x.stride(3) == 1
     B, ny, nx, cin = x.shape
     ld = x.stride(2)
     assert x.stride(1) == nx * ld and x.stride(0) == ny * nx * ld
-    na = len(anchors_px)
-    cout = na * (nc + 5)
+    cout = len(anchors_px) * (nc + 5)
     w = np.ascontiguousarray(w_oi.float().cpu().numpy().reshape(cout, cin))
     bh = np.ascontiguousarray(bias.float().cpu().numpy())
     n = C.c_size_t()
@@ -1840,15 +1838,47 @@ def head_decode_level(x: torch.Tensor, w_oi: torch.Tensor, bias: torch.Tensor, c
     _check(lib.aq_pack_head_weights(w.ctypes.data_as(fp), bh.ctypes.data_as(fp), cin, cout, None, C.byref(n), None))
     wbuf = torch.empty(n.value, dtype=torch.uint8, device=x.device)
     _check(lib.aq_pack_head_weights(w.ctypes.data_as(fp), bh.ctypes.data_as(fp), cin, cout, C.c_void_p(wbuf.data_ptr()), C.byref(n), C.c_void_p(_stream_ptr())))
-    counts = torch.zeros(B, dtype=torch.int32, device=x.device)
-    cand = torch.full((B, cap), -1, dtype=torch.int32, device=x.device)
-    rows = torch.zeros((B, cap, nc + 5), dtype=torch.float32, device=x.device)
+    assert count_stride >= 1
+    if counts is None:
+        counts = torch.zeros((B - 1) * count_stride + 1, dtype=torch.int32, device=x.device)
+    if cand is None:
+        cand = torch.full((B, cap), -1, dtype=torch.int32, device=x.device)
+    if rows is None:
+        rows = torch.zeros((B, cap, nc + 5), dtype=torch.float32, device=x.device)
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= (B - 1) * count_stride + 1
+    assert cand.dtype == torch.int32 and cand.is_contiguous() and cand.numel() >= B * cap
+    assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.numel() >= B * cap * (nc + 5)
     anch = np.ascontiguousarray(np.asarray(anchors_px, np.float32).reshape(-1))
-    _check(lib.aq_head_decode(C.c_void_p(x.data_ptr()), ld, 0, cin, C.c_void_p(wbuf.data_ptr()), B, ny, nx, cand_off, C.c_float(stride),
-                              anch.ctypes.data_as(fp), nc, na, C.c_float(conf_thres), C.c_void_p(cand.data_ptr()), C.c_void_p(rows.data_ptr()),
-                              C.c_void_p(counts.data_ptr()), 1, cap, C.c_void_p(_stream_ptr())))
+    return wbuf, anch, counts, cand, rows
+
+
+def head_decode_level(x: torch.Tensor, w_oi: torch.Tensor, bias: torch.Tensor, cand_off: int, stride: float, anchors_px, nc: int,
+                      conf_thres: float, cap: int, count_stride: int = 1, counts: Optional[torch.Tensor] = None,
+                      cand: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None):
+    """One Detect level through aq_head_decode (tests): x bf16 NHWC [B, ny, nx, cin] (may be a channel slice), w [na * (nc + 5), cin].
+    Returns (counts int32, cand [B, cap] int32, rows [B, cap, nc + 5] float32); the order within an image is unspecified.  Image b's
+    counter is counts[b * count_stride].  ``counts`` / ``cand`` / ``rows``: the caller's buffers, appended to (several levels into one
+    list, as the engine runs them); by default fresh ones."""
+    _require_gpu()
+    lib = load_library()
+    B, ny, nx, cin = x.shape
+    wbuf, anch, counts, cand, rows = _head_level_buffers(x, w_oi, bias, anchors_px, nc, cap, count_stride, counts, cand, rows)
+    _check(lib.aq_head_decode(C.c_void_p(x.data_ptr()), x.stride(2), 0, cin, C.c_void_p(wbuf.data_ptr()), B, ny, nx, cand_off, C.c_float(stride),
+                              anch.ctypes.data_as(C.POINTER(C.c_float)), nc, len(anchors_px), C.c_float(conf_thres), C.c_void_p(cand.data_ptr()),
+                              C.c_void_p(rows.data_ptr()), C.c_void_p(counts.data_ptr()), count_stride, cap, C.c_void_p(_stream_ptr())))
     torch.cuda.current_stream().synchronize()
     return counts, cand, rows
+
+
+def head_counts_gather(wide: torch.Tensor, count_stride: int, B: int) -> torch.Tensor:
+    """aq_head_counts_gather (tests): the B counters kept count_stride ints apart, as the compact int32 [B] array aq_nms reads."""
+    _require_gpu()
+    lib = load_library()
+    assert wide.dtype == torch.int32 and wide.is_contiguous() and wide.numel() >= (B - 1) * count_stride + 1
+    out = torch.full((B,), -1, dtype=torch.int32, device=wide.device)
+    _check(lib.aq_head_counts_gather(C.c_void_p(wide.data_ptr()), count_stride, C.c_void_p(out.data_ptr()), B, C.c_void_p(_stream_ptr())))
+    torch.cuda.current_stream().synchronize()
+    return out
 
 
 def stemdown_nhwc(tiles_u8: torch.Tensor, ws_oihw: torch.Tensor, bs: torch.Tensor, wa_oihw: torch.Tensor, ba: torch.Tensor,
@@ -1947,27 +1977,15 @@ def detect_decode_aug(heads, H: int, W: int, nc: int, anchors_px, strides, level
 
 
 def head_decode_level_aug(x: torch.Tensor, w_oi: torch.Tensor, bias: torch.Tensor, cand_off: int, stride: float, anchors_px, nc: int,
-                          conf_thres: float, cap: int, scale: float, flip_w: float):
+                          conf_thres: float, cap: int, scale: float, flip_w: float, count_stride: int = 1,
+                          counts: Optional[torch.Tensor] = None, cand: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None):
     """head_decode_level through aq_head_decode_aug (tests): the same outputs, the boxes de-scaled."""
     _require_gpu()
     lib = load_library()
-    assert x.dtype == torch.bfloat16 and x.stride(3) == 1
     B, ny, nx, cin = x.shape
-    ld = x.stride(2)
-    na = len(anchors_px)
-    cout = na * (nc + 5)
-    w = np.ascontiguousarray(w_oi.float().cpu().numpy().reshape(cout, cin))
-    bh = np.ascontiguousarray(bias.float().cpu().numpy())
-    n = C.c_size_t()
-    fp = C.POINTER(C.c_float)
-    _check(lib.aq_pack_head_weights(w.ctypes.data_as(fp), bh.ctypes.data_as(fp), cin, cout, None, C.byref(n), None))
-    wbuf = torch.empty(n.value, dtype=torch.uint8, device=x.device)
-    _check(lib.aq_pack_head_weights(w.ctypes.data_as(fp), bh.ctypes.data_as(fp), cin, cout, C.c_void_p(wbuf.data_ptr()), C.byref(n), C.c_void_p(_stream_ptr())))
-    counts = torch.zeros(B, dtype=torch.int32, device=x.device)
-    cand = torch.full((B, cap), -1, dtype=torch.int32, device=x.device)
-    rows = torch.zeros((B, cap, nc + 5), dtype=torch.float32, device=x.device)
-    anch = np.ascontiguousarray(np.asarray(anchors_px, np.float32).reshape(-1))
-    _check(lib.aq_head_decode_aug(x.data_ptr(), ld, 0, cin, wbuf.data_ptr(), B, ny, nx, cand_off, stride, anch.ctypes.data_as(fp), nc, na,
-                                  conf_thres, scale, flip_w, cand.data_ptr(), rows.data_ptr(), counts.data_ptr(), 1, cap, _stream_ptr()))
+    wbuf, anch, counts, cand, rows = _head_level_buffers(x, w_oi, bias, anchors_px, nc, cap, count_stride, counts, cand, rows)
+    _check(lib.aq_head_decode_aug(x.data_ptr(), x.stride(2), 0, cin, wbuf.data_ptr(), B, ny, nx, cand_off, stride,
+                                  anch.ctypes.data_as(C.POINTER(C.c_float)), nc, len(anchors_px), conf_thres, scale, flip_w, cand.data_ptr(),
+                                  rows.data_ptr(), counts.data_ptr(), count_stride, cap, _stream_ptr()))
     torch.cuda.current_stream().synchronize()
     return counts, cand, rows

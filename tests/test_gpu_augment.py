@@ -157,26 +157,42 @@ def test_detect_decode_aug_matches_descaled_oracle(lib, synth_ck):
         assert (pred[:, outside] == 0).all()
 
 
-def test_head_decode_aug_descales(lib):
-    """aq_head_decode_aug = aq_head_decode's candidates with xywh / scale and x mirrored."""
+def _head_decode_aug_descales(shape, scale, flip_w, nc=5):
     from aquaculture_amd import engine
     anchors = [(10.0, 13.0), (16.0, 30.0), (33.0, 23.0)]
+    B, ny, nx, cin = shape
     g = torch.Generator().manual_seed(3)
-    x = (torch.randn(2, 28, 28, 384, generator=g) * 0.7).bfloat16().cuda()
-    w = torch.randn(30, 384, generator=g) * (1.5 / 384 ** 0.5)
-    b = torch.randn(30, generator=g) * 0.5
-    cap = 3 * 28 * 28
-    c0, i0, r0 = (t.cpu() for t in engine.head_decode_level(x, w, b, 100, 16.0, anchors, 5, 0.25, cap))
-    c1, i1, r1 = (t.cpu() for t in engine.head_decode_level_aug(x, w, b, 100, 16.0, anchors, 5, 0.25, cap, 0.67, 640.0))
+    x = (torch.randn(B, ny, nx, cin, generator=g) * 0.7).bfloat16().cuda()
+    w = torch.randn(3 * (nc + 5), cin, generator=g) * (1.5 / cin ** 0.5)
+    b = torch.randn(3 * (nc + 5), generator=g) * 0.5
+    cap = 3 * ny * nx
+    c0, i0, r0 = (t.cpu() for t in engine.head_decode_level(x, w, b, 100, 16.0, anchors, nc, 0.25, cap))
+    c1, i1, r1 = (t.cpu() for t in engine.head_decode_level_aug(x, w, b, 100, 16.0, anchors, nc, 0.25, cap, scale, flip_w))
     assert torch.equal(c0, c1) and int(c0.sum()) > 0
-    for bi in range(2):
+    for bi in range(B):
         n = int(c0[bi])
         o0, o1 = torch.argsort(i0[bi, :n]), torch.argsort(i1[bi, :n])
         assert torch.equal(i0[bi, :n][o0], i1[bi, :n][o1])
         want = r0[bi, :n][o0].clone()
-        want[:, :4] /= 0.67                           # (on the CPU: an IEEE division, as _descale_pred's)
-        want[:, 0] = 640.0 - want[:, 0]
+        want[:, :4] /= scale                          # (on the CPU: an IEEE division, as _descale_pred's)
+        if flip_w != 0.0:
+            want[:, 0] = flip_w - want[:, 0]
         assert torch.equal(r1[bi, :n][o1], want)
+
+
+def test_head_decode_aug_descales(lib):
+    """aq_head_decode_aug = aq_head_decode's candidates with xywh / scale and x mirrored."""
+    _head_decode_aug_descales((2, 28, 28, 384), 0.67, 640.0)
+
+
+@pytest.mark.parametrize("cin,scale,flip_w,nc", [(c, 0.67, 640.0, 5) for c in (128, 192, 256, 320, 384, 512, 640, 768, 1024, 1280)] +
+                         [(192, 0.67, 0.0, 5), (768, 0.83, 0.0, 5), (384, 0.83, 640.0, 4), (1280, 0.67, 0.0, 4)])
+def test_head_decode_aug_descales_at_every_width(lib, cin, scale, flip_w, nc):
+    """The same for the AUG twin of every entry of the fused head's kernel table (cin / 32 = 4 .. 40 k-steps), 35 pixels per image: an
+    iteration of 64, 32 or 16 pixels covers one image or straddles two; with flip_w = 0 (pass 2 of an augmented call: scaled, not
+    mirrored) x is divided only; at four classes rows are 9 floats."""
+    assert lib.aq_head_decode_supported(cin, 3, nc) == 1
+    _head_decode_aug_descales((2, 5, 7, cin), scale, flip_w, nc)
 
 
 # ---- engine --------------------------------------------------------------------------------------------------------------------------
