@@ -143,7 +143,19 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "--facilities-conf / -eps / -min-cages); with --land-filter the ocean detections are scored; needs --geocode-bboxes")
     from .evaluate import add_options as _evaluate_options
     _evaluate_options(p)
+    p.add_argument("--tonnage", nargs="?", const="", default=None, metavar="DIR",
+                   help="after the sweep, its geocoding and the land filter, cluster the detections into facilities per image pass and estimate "
+                        "their live-weight production per pass by the reference's bootstrap (src/utils_tonnage.py, "
+                        "compute_facility_tonnage_estimates: K simulations of model error, area, depth, stocking density and harvest frequency), "
+                        "simulated on the GPU, and write tonnage_estimates.csv, tonnage_facilities.csv and tonnage.json (default <save_dir>); "
+                        "uses --facilities-conf / -eps / -min-cages; needs --geocode-bboxes and --tonnage-factors")
+    from .tonnage import add_options as _tonnage_options
+    _tonnage_options(p)
     opt = p.parse_args(argv)
+    if opt.tonnage is not None and not opt.geocode_bboxes:
+        p.error("--tonnage estimates from geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if opt.tonnage is not None and not opt.tonnage_factors:
+        p.error("--tonnage needs --tonnage-factors FILE (pass, s_mean, s_sd, h_mean, h_sd)")
     if opt.facilities is not None and not opt.geocode_bboxes:
         p.error("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if opt.land_filter is not None and not opt.geocode_bboxes:
@@ -186,7 +198,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         jpeg_decode="auto", augment=False, save_crop=False, line_thickness=3, hide_labels=False, hide_conf=False, blank_key=None, blank_geom=None,
         blank_geom_simplify=0.5, facilities=None, facilities_conf=0.5, facilities_eps=10.0, facilities_min_cages=5, facilities_by="year",
         land_filter=None, ocean_out=None, evaluate=None, evaluate_out=None, evaluate_conf=None, evaluate_eps=None, evaluate_min_cages=None,
-        evaluate_images=None, log=print, **unsupported):
+        evaluate_images=None, tonnage=None, tonnage_factors=None, tonnage_errors=None, tonnage_depths=None, tonnage_default_depth=4.84,
+        tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb, jpeg_slots_to_rgb, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     if blank_geom is not None and blank_key is None:     # the outlines are made for the images the key calls partly blank
@@ -197,6 +210,10 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         raise ValueError("--land-filter filters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if evaluate is not None and not geocode_bboxes:
         raise ValueError("--evaluate scores geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if tonnage is not None and not geocode_bboxes:
+        raise ValueError("--tonnage estimates from geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if tonnage is not None and not tonnage_factors:
+        raise ValueError("--tonnage needs --tonnage-factors FILE (pass, s_mean, s_sd, h_mean, h_sd)")
     for k in UNSUPPORTED:
         if unsupported.get(k):
             raise NotImplementedError(f"--{k.replace('_', '-')} is not part of the tile-sweep path (reference README.md:77)")
@@ -425,7 +442,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     with manifest_lock:
                         manifest.add(Path(p).stem for p in paths)
                 with lock:
-                    if facilities is not None:              # the circle areas' border test wants every image's own size
+                    if facilities is not None or tonnage is not None:       # the circle areas' border test wants every image's own size
                         image_hw.update((Path(p).stem, (int(sh[0]), int(sh[1]))) for p, sh in zip(paths, shapes0))
                     stats["seen"] += len(paths)
                     stats["labels"] += nlab
@@ -1007,6 +1024,17 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 ev = aqeval.evaluate_table(table, evaluate, ev_out, *grids, op=(facilities_conf, facilities_eps, facilities_min_cages), keep=ocean,
                                            images=aqeval.read_image_list(evaluate_images) if evaluate_images else None)
                 log(f"{aqeval.describe(ev)} in {ev_out} in {time.perf_counter() - t_e:.2f}s")
+            if tonnage is not None:
+                # the reference's measuring step (src/utils_tonnage.py): facilities per image pass whatever --facilities-by says (the
+                # facility file above stays as it is), the ocean rows when there are any
+                from . import tonnage as aqton
+                t_t = time.perf_counter()
+                hw = np.asarray([image_hw.get(str(s_), (geocode.IM_HEIGHT, geocode.IM_WIDTH)) for s_ in table["stems"]], np.int64).reshape(-1, 2)
+                ton_out = tonnage or str(save_dir)
+                est = aqton.tonnage_from_table(table, ton_out, tonnage_factors, tonnage_errors, tonnage_depths, tonnage_K, tonnage_seed, tonnage_mix,
+                                               tonnage_min_depth, tonnage_default_depth, facilities_conf, facilities_eps, facilities_min_cages,
+                                               hw[table["image"], 1], hw[table["image"], 0], keep=ocean)
+                log(f"tonnage: {aqton.describe(est)} in {ton_out} in {time.perf_counter() - t_t:.2f}s")
     manifest.close()
     eng.close()
     return save_dir

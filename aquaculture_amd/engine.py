@@ -79,6 +79,7 @@ EXPORTS = (
     "aq_facility_scratch_bytes", "aq_facility_dbscan_f64",
     "aq_land_scratch_bytes", "aq_land_filter_f64",
     "aq_eval_scratch_bytes", "aq_eval_member_conf_f64", "aq_box_match_f64",
+    "aq_tonnage_simulate_f64", "aq_tonnage_reduce_f64", "aq_tonnage_ndtri_f64", "aq_tonnage_uniform_f64",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -146,6 +147,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_eval_scratch_bytes.restype = sz
     lib.aq_eval_member_conf_f64.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, C.c_double, i32, vp, sz, vp, vp]
     lib.aq_box_match_f64.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, vp, i32, vp, i32, vp, vp, vp]
+    lib.aq_tonnage_simulate_f64.argtypes = [C.c_ulonglong, C.c_longlong, C.c_longlong, vp, vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, i32,
+                                            C.c_double, C.c_double, vp, vp, vp]
+    lib.aq_tonnage_reduce_f64.argtypes = [vp, C.c_longlong, C.c_longlong, vp, i32, vp, vp, vp]
+    lib.aq_tonnage_ndtri_f64.argtypes = [vp, C.c_longlong, vp, vp]
+    lib.aq_tonnage_uniform_f64.argtypes = [C.c_ulonglong, vp, C.c_longlong, vp, vp]
     lib.aq_engine_set_tuned_table.argtypes = [vp, i32, i32, i32, C.POINTER(i32), i32]
     lib.aq_engine_calibrate_amax.argtypes = [vp, vp, i32, i32, i32, vp, sz, C.POINTER(f32), i32, vp]
     lib.aq_engine_set_fp8_scales.argtypes = [vp, C.POINTER(f32), i32]
@@ -1402,6 +1408,62 @@ def box_match(qbox: torch.Tensor, qgroup: torch.Tensor, kbox: torch.Tensor, kgro
     for t_ in (qbox, qgroup, kb, start, hit) + ((pl, out) if pl is not None else ()):
         t_.record_stream(torch.cuda.current_stream())
     return hit, out
+
+
+# ---- --tonnage: aq_tonnage_simulate_f64 / aq_tonnage_reduce_f64 (the production bootstrap) and the two test hooks ----
+
+def tonnage_simulate(seed: int, k0: int, K: int, entry_start: torch.Tensor, area: torch.Tensor, err: torch.Tensor, flags: torch.Tensor,
+                     depth: torch.Tensor, pass_id: torch.Tensor, pass_params: torch.Tensor, mix: float, min_depth: float, probs,
+                     moments: torch.Tensor, entry_start_host: Optional[np.ndarray] = None,
+                     pass_params_host: Optional[np.ndarray] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Simulations k0 .. k0 + K - 1 on the current stream -> (ton float64 CUDA [K, F], T float64 CUDA [K, P]); moments (float64 CUDA [F, 2],
+    the caller's) grows by the chunk's sums and sums of squares.  entry_start int32 [F + 1], area float64 [E], err float64 [E, 2], flags
+    uint8 [E], depth float64 [F], pass_id int32 [F], pass_params float64 [P, 6], all CUDA and contiguous; probs = the four depth
+    probabilities.  entry_start_host, pass_params_host = the two tables' content in host memory (the ABI checks them there before it
+    launches); a caller that has them passes them, else they are copied back here, which synchronises.  include/aq_engine.h states the
+    arithmetic; tonnage.simulate_numpy gives the same bytes."""
+    _require_gpu()
+    lib = load_library()
+    F, E, P = int(depth.shape[0]), int(area.shape[0]), int(pass_params.shape[0])
+    for t_, dt, shape in ((entry_start, torch.int32, (F + 1,)), (area, torch.float64, (E,)), (err, torch.float64, (E, 2)), (flags, torch.uint8, (E,)),
+                          (depth, torch.float64, (F,)), (pass_id, torch.int32, (F,)), (pass_params, torch.float64, (P, 6)), (moments, torch.float64, (F, 2))):
+        if not t_.is_cuda or t_.dtype != dt or tuple(t_.shape) != shape or not t_.is_contiguous():
+            raise ValueError(f"tonnage: a contiguous CUDA {dt} tensor of shape {shape} is needed, not {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+    K = int(K)
+    ton = torch.empty((K, F), dtype=torch.float64, device=depth.device)
+    T = torch.empty((K, P), dtype=torch.float64, device=depth.device)
+    start_h = np.ascontiguousarray(entry_start.cpu().numpy() if entry_start_host is None else entry_start_host, dtype=np.int32)
+    pp_h = np.ascontiguousarray(pass_params.cpu().numpy() if pass_params_host is None else pass_params_host, dtype=np.float64)
+    if start_h.shape != (F + 1,) or pp_h.shape != (P, 6):
+        raise ValueError(f"tonnage: host copies of shape {start_h.shape} and {pp_h.shape} for tables of shape {(F + 1,)} and {(P, 6)}")
+    pr = np.ascontiguousarray(np.asarray(probs, np.float64).reshape(4))
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    _check(lib.aq_tonnage_simulate_f64(int(seed), int(k0), K, entry_start.data_ptr(), start_h.ctypes.data, F, ptr(area), ptr(err), ptr(flags), E,
+                                       ptr(depth), ptr(pass_id), ptr(pass_params), pp_h.ctypes.data, P, float(mix), float(min_depth),
+                                       pr.ctypes.data, ptr(ton), _stream_ptr()))
+    _check(lib.aq_tonnage_reduce_f64(ptr(ton), K, F, ptr(pass_id), P, ptr(T), ptr(moments), _stream_ptr()))
+    for t_ in (entry_start, area, err, flags, depth, pass_id, pass_params, moments):
+        t_.record_stream(torch.cuda.current_stream())
+    return ton, T
+
+
+def tonnage_ndtri(p: torch.Tensor) -> torch.Tensor:
+    """aq_tonnage_ndtri_f64: the kernels' inverse normal distribution function of p (float64 CUDA [n])."""
+    _require_gpu()
+    p = p.contiguous()
+    out = torch.empty_like(p)
+    _check(load_library().aq_tonnage_ndtri_f64(p.data_ptr() if p.numel() else None, p.numel(), out.data_ptr() if p.numel() else None, _stream_ptr()))
+    return out
+
+
+def tonnage_uniform(seed: int, counters: torch.Tensor) -> torch.Tensor:
+    """aq_tonnage_uniform_f64: the kernels' uniform draw of every counter (int32 CUDA [n, 4] holding the four unsigned words' bits)."""
+    _require_gpu()
+    counters = counters.contiguous()
+    n = int(counters.shape[0])
+    out = torch.empty(n, dtype=torch.float64, device=counters.device)
+    _check(load_library().aq_tonnage_uniform_f64(int(seed), counters.data_ptr() if n else None, n, out.data_ptr() if n else None, _stream_ptr()))
+    return out
 
 
 # ---- --land-filter: aq_land_filter_f64 (detection boxes against the segments of the land polygons) ----

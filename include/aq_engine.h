@@ -638,6 +638,54 @@ int aq_land_filter_f64(const double* seg_dev, long long E, const int32_t* entry_
                        int nbands, double Y0, double h, const double* boxes_dev, long long N, void* scratch_dev, size_t scratch_bytes,
                        uint8_t* flags_dev, void* stream);
 
+/* ---- --tonnage (tonnage.hip): the bootstrap of the facilities' live-weight production per image pass (reference src/utils_tonnage.py:28-127,
+ * compute_facility_tonnage_estimates, with :330-458, sample_model_errors).  Everything fp64; the only floating-point operations are + - x /
+ * sqrt, comparisons and selections (no fma, no libm), so aquaculture_amd.tonnage.simulate_numpy gives the same bytes.
+ * Random numbers.  Philox4x32-10 (multipliers D2511F53, CD9E8D57; key increments 9E3779B9, BB67AE85), key = (seed & 0xffffffff, seed >> 32),
+ * counter words (c0, c1, c2, c3) = (simulation k, entity, slot, attempt): a draw depends on nothing else.  Slots: 0 model error (entity = the
+ * entry's index; attempt = 0, 1 ..), 1 area, 2 Bernoulli, 3 depth A, 4 depth B, 5 stocking, 6 harvest (entity = the facility's index,
+ * attempt 0).  With output words w0 .. w3: x = ((w1 << 32) | w0) >> 11, u = ((double)x + 0.5) 2^-53, and 1 - 2^-53 where that rounds to 1.
+ * alog(x), x > 0: x = m 2^e, 0.5 <= m < 1; m < 0.7071067811865476: m = 2 m, e = e - 1; s = (m - 1) / (m + 1), s2 = s s; acc = 1/27, then
+ * acc = acc s2 + 1/j for j = 25, 23 .. 1; alog = e 0.6931471805599453 + (2 s) acc.
+ * ndtri(p): the Cephes Math Library's rational approximations with alog for log: NaN outside [0, 1], -inf at 0, +inf at 1; y = p, or 1 - p when
+ * p > 1 - e^-2; y > e^-2: y = y - 0.5, y2 = y y, (y + y ((y2 P0(y2)) / Q0(y2))) sqrt(2 pi); else x = sqrt(-2 alog(y)), x0 = x - alog(x) / x,
+ * z = 1 / x, x1 = (z P(z)) / Q(z) with (P1, Q1) for x < 8 and (P2, Q2) from 8 on; x0 - x1 when y was mirrored, else x1 - x0 as -(x0 - x1).
+ * Horner from the leading coefficient.
+ * Facility f owns the entries entry_start[f] .. entry_start[f + 1] - 1 (a cage of a facility each): area_orig (entry_area_dev [E]), the
+ * model error's (mean, sd) (entry_err_dev [E][2], 16-byte aligned) and flags (entry_flags_dev [E]): bits 0-1 the kind (0 full ellipse, 1
+ * border ellipse, 2 square; 3 as 0), bit 2 in the min selection, bit 3 in the max selection, bit 4 in the random selection (carried, not
+ * used: the reference's point estimate).  In simulation k, for the entries in ascending order:
+ *   area = area_orig + (mean + sd ndtri(u(k, e, 0, attempt))), attempt = 0, 1 .. while area <= 0; after 64 such draws area = area_orig (the
+ *   reference draws for ever); (min_c, max_c) = (area, area), ((4 area) / (2 + pi), ((2 pi) area) / (2 + pi)), ((2 area) / 3, (4 area) / 3)
+ *   by kind; lo = lo + min_c with bit 2, hi = hi + max_c with bit 3, both from +0.
+ * Then sim_area = lo + (hi - lo) u1; with d = depth_dev[f] and m = min_depth: depth = m unless d > m (the reference divides 0 by 0 at d = m),
+ * else u2 < mix: d + ((d - m) / 1.96) ndtri(pA0 + u3 (pA1 - pA0)), otherwise d + (d / 1.96) ndtri(pB0 + u4 (pB1 - pB0)), depth_probs (host
+ * memory) = pA0, pA1, pB0, pB1 = Phi(-1.96), Phi(0), Phi(0), Phi(1.96); with the six doubles of the facility's pass (pass_dev[f], kept inside
+ * [0, P) for this) s_mean, s_sd, pS0, pS1, h_mean, h_sd: stocking = s_mean + s_sd ndtri(pS0 + u5 (pS1 - pS0)), harvest = h_mean + h_sd
+ * ndtri(u6); ton_dev[(k - k0) F + f] = ((sim_area depth) stocking) (harvest (1 / 1000)).
+ * On `stream`, one launch, allocates nothing, no atomics: the same bytes on every call, whatever k0 and K_chunk split the simulations into.
+ * F = 0 or K_chunk = 0 does nothing.  Refused before anything is launched: K_chunk, F or E >= 2^31, K_chunk F >= 2^62, k0 < 0 or
+ * k0 + K_chunk > 2^32, a null pointer, an unaligned array, mix outside [0, 1], a min_depth, depth probability or pass parameter that is not
+ * finite, s_sd <= 0, P < 1, and offsets in entry_start_host (= entry_start_dev's content in host memory; pass_params_host likewise) that
+ * decrease or leave [0, E].  On the device entry ranges are kept inside [0, E], so tables the caller got wrong give wrong numbers but no
+ * access outside the arrays. */
+int aq_tonnage_simulate_f64(unsigned long long seed, long long k0, long long K_chunk, const int32_t* entry_start_dev,
+                            const int32_t* entry_start_host, long long F, const double* entry_area_dev, const double* entry_err_dev,
+                            const uint8_t* entry_flags_dev, long long E, const double* depth_dev, const int32_t* pass_dev,
+                            const double* pass_params_dev, const double* pass_params_host, int P, double mix, double min_depth,
+                            const double* depth_probs, double* ton_dev, void* stream);
+/* The sums over ton_dev [K_chunk][F], each a plain sequence of fp64 additions in the stated order:
+ *   T_dev[k][p] ([K_chunk][P]) = the sum of ton[k][f] over the facilities with pass_dev[f] == p in ascending f, from +0 (a pass without
+ *   facilities: +0; a pass id outside [0, P) enters no sum);
+ *   moments_dev[f] ([F][2], 16-byte aligned, caller-held) = (moments[f][0] + sum, moments[f][1] + sum of squares) of ton[.][f], t and t t
+ *   added one after the other in ascending k, so that the chunks of a run add up in one fixed order.
+ * On `stream`, two launches, no atomics.  K_chunk = 0 does nothing; counts >= 2^31, a null pointer and an unaligned array are refused. */
+int aq_tonnage_reduce_f64(const double* ton_dev, long long K_chunk, long long F, const int32_t* pass_dev, int P, double* T_dev,
+                          double* moments_dev, void* stream);
+/* Test hooks: out_dev[i] = ndtri(p_dev[i]); out_dev[i] = the uniform of counter counters_dev[i][0 .. 3] (uint32) under `seed`. */
+int aq_tonnage_ndtri_f64(const double* p_dev, long long n, double* out_dev, void* stream);
+int aq_tonnage_uniform_f64(unsigned long long seed, const uint32_t* counters_dev, long long n, double* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
