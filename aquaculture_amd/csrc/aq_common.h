@@ -88,6 +88,11 @@ struct ConvParams {
     unsigned magic_G, magic_k, magic_ntm;   // floor(2^32 / d) + 1
 };
 
+// Packed weight rows (and bias entries) beyond cout, all zero: a tile of BM rows whose first row is below cout reads BM whole rows, so
+// the last tile row ends at most BM - 1 rows past cout.  384 = the tallest tile of any conv kernel (conv_halo.hip; the launchers check
+// their tile tables against it).  With fewer, a taller tile reads past the packed buffer of a layer with few output channels.
+constexpr int kConvCoutSlack = 384;
+
 int aq_launch_conv(const ConvParams& p, int precision, int out_f32, int cfg, hipStream_t stream);
 int aq_conv_pick_config(int cout, int npix, int precision);
 int aq_launch_conv_halo(const ConvParams& p, int precision, int out_f32, int hcfg, bool one_tile_per_wg, hipStream_t stream);

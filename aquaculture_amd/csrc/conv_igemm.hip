@@ -619,6 +619,7 @@ int aq_launch_conv(const ConvParams& p_in, int precision, int out_f32, int cfg_i
     if (cfg < 0) { aq_set_error("conv: bad config %d", cfg); return AQ_ERR_INVALID; }
     const ConvConfig& k = kConfigs[cfg];
     ConvParams p = p_in;
+    if (k.bm > kConvCoutSlack) { aq_set_error("conv: config %d is taller than the packed weights' zero rows", cfg); return AQ_ERR_INVALID; }
     if (p.npix >= (1 << 24) || p.kgroups_pad >= (1 << 15) || p.G <= 0 || p.G >= (1 << 15) || p.k <= 0) {
         aq_set_error("conv: shape outside the fast-index range (npix=%d kgroups=%d)", p.npix, p.kgroups_pad);
         return AQ_ERR_INVALID;

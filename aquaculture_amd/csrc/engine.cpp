@@ -32,7 +32,7 @@ namespace {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 constexpr size_t kAlign = 256;
-constexpr int kCoutSlack = 256;   // packed weight rows beyond cout so any BM tile may over-read zeros
+constexpr int kCoutSlack = kConvCoutSlack;   // (aq_common.h)
 
 // Optional roctx ranges around every plan op (AQ_ROCTX=1; `rocprofv3 --kernel-trace --marker-trace` then shows which kernels belong to
 // which op).  The library is looked up at run time so that libaqengine.so does not depend on the profiler SDK.

@@ -666,13 +666,21 @@ def pack_conv_weights(w_oihw: torch.Tensor, precision: str, device) -> torch.Ten
 
 def conv2d_nhwc(x: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, stride=1, pad=None, act=True,
                 residual: Optional[torch.Tensor] = None, precision="bf16", out_f32=False,
-                cfg: Optional[int] = None) -> torch.Tensor:
-    """out = (residual +) SiLU(conv(x, w) + b) on NHWC tensors through aq_conv2d (tests)."""
+                cfg: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = (residual +) SiLU(conv(x, w) + b) on NHWC tensors through aq_conv2d (tests).  ``x``, ``residual`` and ``out`` may be channel
+    slices (starting on a multiple of 8 channels) of wider dense NHWC tensors."""
     _require_gpu()
     lib = load_library()
     prec = PRECISIONS[precision]
-    assert x.is_cuda and x.is_contiguous() and x.dtype == _act_dtype(prec)
+
+    def pixel_stride(t, h, w):
+        assert t.is_cuda and t.stride(3) == 1 and t.stride(1) == w * t.stride(2) and t.stride(0) == h * w * t.stride(2), \
+            "a channel slice of a dense NHWC tensor is needed"
+        return t.stride(2)
+
+    assert x.dtype == _act_dtype(prec)
     B, H, W, cin = x.shape
+    in_ld = pixel_stride(x, H, W)
     cout, _, k, _ = w_oihw.shape
     pad = k // 2 if pad is None else pad
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
@@ -690,13 +698,19 @@ def conv2d_nhwc(x: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, strid
         bbuf = torch.zeros(cout + 512, dtype=torch.float32, device=x.device)
         bbuf[:cout] = bias.float().to(x.device)
     odt = torch.float32 if (out_f32 or prec in (AQ_FP32, AQ_F16X3)) else torch.bfloat16
-    out = torch.empty((B, Ho, Wo, cout), dtype=odt, device=x.device)
-    res_ptr = residual.data_ptr() if residual is not None else None
+    if out is None:
+        out = torch.empty((B, Ho, Wo, cout), dtype=odt, device=x.device)
+    assert out.dtype == odt and tuple(out.shape) == (B, Ho, Wo, cout)
+    out_ld = pixel_stride(out, Ho, Wo)
+    res_ptr, res_ld = None, cout
+    if residual is not None:
+        assert residual.dtype == x.dtype and tuple(residual.shape) == (B, Ho, Wo, cout)
+        res_ptr, res_ld = residual.data_ptr(), pixel_stride(residual, Ho, Wo)
     old = os.environ.get("AQ_CONV_CFG")
     if cfg is not None:
         os.environ["AQ_CONV_CFG"] = str(cfg)
     try:
-        _check(lib.aq_conv2d(x.data_ptr(), cin, 0, cin, out.data_ptr(), cout, 0, cout, res_ptr, cout, 0,
+        _check(lib.aq_conv2d(x.data_ptr(), in_ld, 0, cin, out.data_ptr(), out_ld, 0, cout, res_ptr, res_ld, 0,
                              wbuf.data_ptr(), bbuf.data_ptr(), B, H, W, k, stride, pad, int(act), prec, int(out_f32),
                              _zero_page(x.device).data_ptr(), _stream_ptr()))
     finally:

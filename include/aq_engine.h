@@ -185,7 +185,9 @@ int aq_conv_config_tiles(int cfg, int* bm, int* bn);
 /* ---- individual kernels --------------------------------------------------------------- */
 /* Packs fp32 KRSC host weights into the device layout conv kernels read:
  * [cout_pad][k_pad] elements of `precision`, k = (ky, kx, cin) flattened, zero padded.  Returns the
- * byte count via *bytes when packed_dev == NULL. */
+ * byte count via *bytes when packed_dev == NULL.  cout_pad = cout + 384 rounded up to 32: a tile of
+ * any configuration (up to 384 rows) reads whole rows, so the rows behind cout are there and zero.
+ * aq_conv2d's bias_dev holds as many floats, zero behind cout, for the same reason. */
 int aq_pack_conv_weights(const float* w_krsc_host, int cout, int k, int cin, int precision,
                          void* packed_dev, size_t* bytes, void* stream);
 /* Implicit-GEMM convolution, NHWC, fused bias + SiLU + residual.  in/out/res element type = precision
