@@ -11,6 +11,17 @@
 // code: a DC symbol is "run 0, size s" at k = 0); lanes sit at different blocks and MCUs, but there is no per-block reconvergence point
 // to wait at.  A launch ends when its longest segment ends.  Tables: the six tables of one table set (all tiles of a sweep share one:
 // GDAL / Pillow write the standard tables) are staged in LDS; lanes whose set differs read theirs from global memory.
+//
+// What a lane may read (the bytes come straight from files, and a scan that ends in EOI may still encode fewer MCUs than its frame header
+// promises: a damaged file, a half-written tile closed properly, a restart interval cut short):
+//   - a segment OWNS [stream_off, stream_off + ((stream_len + 8 + 15) & ~15)): its data plus the zero bytes aq_jpeg_prepare writes behind it;
+//   - a lane's status and every coefficient it stores depend on owned bytes only;
+//   - a lane takes no stream word that ends past stream_len + 8 bytes (a valid segment never needs one: the refill happens at <= 32 unread
+//     bits, so the word it takes ends at most 8 bytes past the last bit decoded);
+//   - together with the two 64-byte windows loaded ahead it therefore loads no byte at or past stream_off + stream_len + 8 + 192, which is
+//     what makes the 256 spare bytes behind the last slot sufficient (aq_jpeg_prepare keeps stream_len + 40 inside the slot);
+//   - a lane that would need more bits ends with status 2: the host decoder's rule "consumed bits the file does not contain"
+//     (csrc/jpeg_coef.c, `fake`), applied when it happens and not at the segment's end.
 #include "aq_common.h"
 
 namespace {
@@ -37,7 +48,8 @@ __constant__ unsigned char kZig[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 3
                                        41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                        30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-// status per segment: 0 ok, 2 corrupt (bad code, coefficient index past 63, DC category > 11, or bits consumed past the segment's end)
+// status per segment: 0 ok, 2 corrupt (bad code, coefficient index past 63, DC category > 11, a stream word wanted that ends past
+// stream_len + 8 bytes, or bits consumed past the segment's end)
 //
 // The bit stream of a lane goes through a 2 x 64-byte window in LDS ([window][word][lane]: lanes on consecutive banks) that is refilled one
 // window at a time by four 16-byte loads, with the window after next already in flight in registers.  First build: one 4-byte global load
@@ -59,8 +71,9 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(const unsigned char* __re
     const bool lds_tabs = sg.tabset == set0;
     const JpegGpuTab* my = sets + (size_t)sg.tabset * 6;
 
-    // chunk c = bytes 64 c .. 64 c + 63 of the segment (16-byte aligned; behind the last segment the upload buffer has >= 256 spare bytes,
-    // so whole chunks are always readable -- what lies past stream_len is never counted as data: the overrun check works on bit counts)
+    // chunk c = bytes 64 c .. 64 c + 63 of the segment (16-byte aligned).  Chunk m + 2 is loaded when word 16 m has been taken, and no word
+    // past max_words is: the loads end before byte stream_len + 8 + 192 of the segment, inside the 256 spare bytes behind the last slot.
+    // What lies past stream_len is never counted as data: the overrun checks work on word and bit counts.
     const uint4* src = (const uint4*)(streams + sg.stream_off);
     auto put_window = [&](int wb, const uint4 (&q)[4]) {
 #pragma unroll
@@ -83,6 +96,7 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(const unsigned char* __re
 
     int wb = 0, widx = 0;
     unsigned words = 0;                                          // 32-bit words taken so far
+    const unsigned max_words = (sg.stream_len + 8u) >> 2;        // words that end within stream_len + 8 bytes: the data and owned zeros
     unsigned long long acc = 0;
     int nbits = 0;
     int pred0 = 0, pred1 = 0, pred2 = 0;
@@ -108,6 +122,7 @@ __global__ __launch_bounds__(64) void jpeg_huff_kernel(const unsigned char* __re
     while (__any(active)) {
         if (active) {
             if (nbits <= 32) {                                   // refill: 32 bits from the window
+                if (words >= max_words) { st = 2; active = false; continue; }     // the segment does not hold the bits this lane wants
                 acc = (acc << 32) | __builtin_bswap32(s_win[wb][widx][lane]);
                 nbits += 32;
                 ++words;

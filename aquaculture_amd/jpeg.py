@@ -135,7 +135,11 @@ class GpuDecodeBatch:
     def __init__(self, n_images: int, H: int, W: int, stream_buf: Optional[np.ndarray] = None, bytes_per_image: Optional[int] = None):
         self.n, self.H, self.W = n_images, H, W
         self.per = bytes_per_image or stream_capacity(H, W)
-        self.streams = stream_buf if stream_buf is not None else np.zeros(n_images * self.per + 256, np.uint8)      # (+ 256: the device reads whole 64-byte chunks, two ahead)
+        # + 256: a segment owns [stream_off, stream_off + ((stream_len + 8 + 15) & ~15)) -- its data and the zeros aq_jpeg_prepare writes behind
+        # it -- and a lane's status and coefficients depend on owned bytes only: it takes no stream word that ends past stream_len + 8 bytes
+        # (status 2 if it would need one) and, with the two 64-byte windows loaded ahead, loads no byte at or past stream_off + stream_len + 8
+        # + 192.  aq_jpeg_prepare keeps stream_len + 40 inside the slot, so the loads of the last slot end within 160 bytes behind it.
+        self.streams = stream_buf if stream_buf is not None else np.zeros(n_images * self.per + 256, np.uint8)
         assert self.streams.dtype == np.uint8 and self.streams.size >= n_images * self.per + 256
         self.qt = np.zeros((n_images, 3, 64), np.uint16)
         self.nco = coef_count(H, W)

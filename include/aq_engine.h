@@ -364,8 +364,12 @@ int aq_jpeg_idct_rgb(const int16_t* coef_dev, const long long* coef_off_dev, con
  * uploaded as they are; segs_dev: nseg descriptors of 32 bytes {u32 stream_off, u32 stream_len, u64 coef_off (int16 index of the image's
  * first coefficient in coef_dev), u32 mcu0, u32 n_mcu, u16 mcu_cols, u16 mcu_rows, u32 tabset}; tabsets_dev: table sets of six
  * aq_jpeg_gpu_tab each; coef_dev: ZEROED coefficient buffers in aq_jpeg_decode_coeffs's layout; status_dev: int32 per segment (0 ok, 2 corrupt).
- * The kernel reads the stream in 64-byte chunks from each segment's start and runs up to two chunks ahead: streams_dev needs 256 readable
- * bytes behind the last segment.  The caller validates every offset; the kernel trusts them. */
+ * A segment owns [stream_off, stream_off + ((stream_len + 8 + 15) & ~15)): its data plus the zero bytes aq_jpeg_prepare writes behind it.
+ * A lane's status and every coefficient it stores depend on owned bytes only: it takes no stream word that ends past stream_len + 8 bytes,
+ * and a lane that would need more bits ends with status 2 (the host decoder's rule, "consumed bits the file does not contain", applied
+ * when it happens).  The kernel loads the stream in 64-byte chunks from each segment's start, two chunks ahead, so it loads no byte at or
+ * past stream_off + stream_len + 8 + 192: streams_dev needs 256 readable bytes behind the last slot, whatever the files hold.  The caller
+ * validates every offset; the kernel trusts them. */
 int aq_jpeg_huffman_decode(const void* streams_dev, const void* segs_dev, int nseg, const void* tabsets_dev, void* coef_dev,
                            void* status_dev, void* stream);
 /* SPPF pools: y1 = mp5(x), y2 = mp5(y1), y3 = mp5(y2) written to channel slices c, 2c, 3c of the same buffer. */

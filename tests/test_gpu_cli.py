@@ -461,3 +461,36 @@ def test_gpu_jpeg_decode_gives_identical_labels(workdir, lib, tmp_path):
            "--nosave", "--save-txt", "--save-conf", "--project", str(tmp_path / "runs"), "--name", "gjpeg_trunc", "--batch-size", "4", "--half", "--jpeg-decode", "gpu"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
     assert r.returncode != 0 and victim in r.stderr, r.stderr[-1500:]
+
+
+def test_gpu_jpeg_decode_names_the_tile_whose_scan_ends_early(workdir, lib, tmp_path):
+    """--jpeg-decode gpu on a directory with one tile whose scan stops after a third of its bytes and then ends properly in EOI: the host
+    preparation takes the file, the device decoder gives its segment status 2, and the sweep stops with a non-zero exit code and a message
+    that names that tile and no other; the done-manifest does not list it.  Two tiles that sort before the victim have a restart marker per
+    MCU row (40 segments each), so the status index of the victim's segment is not its image index: the message depends on the mapping
+    through `first`.  This passes with and without the device decoder's bound on stream words (it covers the status -> ValueError
+    branch of the sweep, not the bound; tests/test_jpeg.py does that): AQ_JPEG_GPU_BPP = 12 makes a slot 622,592 bytes, the provable
+    worst-case read of an unbounded lane is 4 bytes per coefficient, 6 x 640^2 = 2.46 MB, under four slots, and six tiles follow the
+    victim in its super-batch (all ten tiles share the first one at batch size 4)."""
+    import shutil
+    from PIL import Image
+    src = tmp_path / "jpegs"
+    shutil.copytree(workdir / "jpegs", src)
+    names = sorted(os.listdir(src))
+    assert len(names) == 10
+    for n in (names[0], names[2]):
+        im = Image.open(src / n)
+        im.load()
+        im.save(src / n, format="JPEG", quality=75, restart_marker_rows=1)
+    victim = names[3]
+    data = (src / victim).read_bytes()
+    sos = data.index(b"\xff\xda")
+    start = sos + 2 + int.from_bytes(data[sos + 2:sos + 4], "big")
+    (src / victim).write_bytes(data[:start + (len(data) - start) // 3] + b"\xff\xd9")
+    cmd = [sys.executable, os.path.join(ROOT, "yolov5", "detect.py"), "--weights", str(workdir / "multilabel_farms_synth.pt"), "--source", str(src),
+           "--nosave", "--save-txt", "--save-conf", "--project", str(tmp_path / "runs"), "--name", "gjpeg_short", "--batch-size", "4", "--half", "--jpeg-decode", "gpu"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=420, env=dict(os.environ, AQ_JPEG_GPU_BPP="12"))
+    assert r.returncode != 0 and victim in r.stderr and "GPU entropy decode status 2" in r.stderr, r.stdout[-1500:] + r.stderr[-1500:]
+    assert not [n for n in names if n != victim and n in r.stderr], r.stderr[-1500:]
+    done = tmp_path / "runs" / "gjpeg_short" / "done.rank0.txt"
+    assert not done.exists() or victim[:-5] not in open(done).read().split()

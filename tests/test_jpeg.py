@@ -290,6 +290,93 @@ def test_gpu_decode_preparation_refuses_what_the_host_decoder_refuses(jpeg_lib):
         b.add(0, _jpeg(rng.integers(0, 255, (48, 48, 3), dtype=np.uint8)))  # another size than the batch's
 
 
+def _bulk_files(tmp_path):
+    """21 files of 64 x 64 (16 MCUs): 62 restart segments, 3 table sets (the standard tables and two optimised sets)."""
+    rng = np.random.default_rng(21)
+    kws = [dict(quality=75)] * 8 + [dict(quality=90, optimize=True)] * 2 + [dict(quality=75, restart_marker_blocks=3)] * 4 + \
+          [dict(quality=80, restart_marker_blocks=5)] * 4 + [dict(quality=85, restart_marker_rows=1)] * 3
+    order = rng.permutation(len(kws))
+    paths, datas = [], []
+    for j, k in enumerate(order):
+        datas.append(_jpeg(rng.integers(0, 255, (64, 64, 3), dtype=np.uint8), **kws[k]))
+        paths.append(str(tmp_path / f"{j:02d}.jpeg"))
+        open(paths[-1], "wb").write(datas[-1])
+    return paths, datas
+
+
+@pytest.mark.parametrize("nthreads", [1, 3, 8])
+def test_bulk_preparation_equals_add_and_finish(jpeg_lib, tmp_path, nthreads):
+    """GpuDecodeBatch.prepare_files -- the C-thread path the sweep uses -- against add + finish on files with and without restart markers
+    and with three table sets: the same descriptors field by field, the same table bytes behind every segment's `tabset` (the two paths
+    number the sets differently), the same `first`, the same quantisation tables and the same stream bytes over every segment's data
+    plus the 8 zero bytes -- in upload buffers that held different stale bytes."""
+    paths, datas = _bulk_files(tmp_path)
+    H = W = 64
+    per = jpeg_lib.stream_capacity(H, W, 12)
+    a = jpeg_lib.GpuDecodeBatch(len(paths), H, W, stream_buf=np.full(len(paths) * per + 256, 0xAA, np.uint8), bytes_per_image=per)
+    b = jpeg_lib.GpuDecodeBatch(len(paths), H, W, stream_buf=np.full(len(paths) * per + 256, 0x33, np.uint8), bytes_per_image=per)
+    for i, d in enumerate(datas):
+        assert a.add(i, d) == 0
+    segs_a, sets_a, first_a = a.finish()
+    segs_b, sets_b, first_b = b.prepare_files(paths, nthreads)
+    assert segs_a.shape == segs_b.shape == (62,) and sets_a.shape == sets_b.shape == (3, jpeg_lib.TABSET_BYTES)
+    assert (np.diff(first_a) > 1).any() and (np.diff(first_a) == 1).any()
+    for f in jpeg_lib.SEG_DTYPE.names:
+        if f != "tabset":
+            assert np.array_equal(segs_a[f], segs_b[f]), f
+    assert np.array_equal(sets_a[segs_a["tabset"]], sets_b[segs_b["tabset"]])
+    assert len({bytes(t) for t in sets_b}) == 3
+    assert first_a.dtype == first_b.dtype and np.array_equal(first_a, first_b)
+    assert np.array_equal(a.qt, b.qt)
+    for sg in segs_a:
+        o, e = int(sg["stream_off"]), int(sg["stream_off"]) + int(sg["stream_len"]) + 8
+        assert np.array_equal(a.streams[o:e], b.streams[o:e]) and not a.streams[e - 8:e].any()
+
+
+def test_bulk_preparation_names_the_first_offending_file_with_the_reason(jpeg_lib, tmp_path):
+    """prepare_files raises ValueError for the FIRST file the GPU decoder does not take, with that file's reason: another size than the
+    batch's, no EOI, more restart segments than the bulk path holds per image (73 > SEG_CAP; `add` takes that file), a scan larger than
+    bytes_per_image.  A second bad file behind the first is not the one named."""
+    rng = np.random.default_rng(22)
+    noise = lambda h, w: rng.integers(0, 255, (h, w, 3), dtype=np.uint8)
+
+    def write(name, data):
+        (tmp_path / name).write_bytes(data)
+        return str(tmp_path / name)
+
+    good = [write(f"good{i}.jpeg", _jpeg(noise(64, 64), quality=75)) for i in range(4)]
+    other_size = write("other_size.jpeg", _jpeg(noise(48, 64), quality=75))
+    data = _jpeg(noise(64, 64), quality=75)
+    no_eoi = write("no_eoi.jpeg", data[:-2])
+    per = jpeg_lib.stream_capacity(64, 64, 12)
+    for bad, later, why in ((other_size, no_eoi, "not a baseline 8-bit 4:2:0 JPEG of the batch's size"), (no_eoi, other_size, "corrupt or truncated")):
+        paths = good[:2] + [bad] + good[2:3] + [later] + good[3:]
+        for nthreads in (1, 3):
+            with pytest.raises(ValueError) as e:
+                jpeg_lib.GpuDecodeBatch(len(paths), 64, 64, bytes_per_image=per).prepare_files(paths, nthreads)
+            assert str(e.value).startswith(bad + ":") and why in str(e.value) and later not in str(e.value), str(e.value)
+    # 272 x 272 = 17 x 17 MCUs, a restart marker every 4: 73 segments
+    many = _jpeg(noise(272, 272), quality=50, restart_marker_blocks=4)
+    big = [write(f"big{i}.jpeg", _jpeg(noise(272, 272), quality=50)) for i in range(2)]
+    per = jpeg_lib.stream_capacity(272, 272, 12)
+    b = jpeg_lib.GpuDecodeBatch(3, 272, 272, bytes_per_image=per)
+    assert b.add(1, many) == 0 and b._segs[1].shape[0] == 73 > b.SEG_CAP
+    paths = [big[0], write("many_segments.jpeg", many), big[1]]
+    with pytest.raises(ValueError) as e:
+        b.prepare_files(paths, 2)
+    assert str(e.value).startswith(paths[1] + ":") and f"more than {b.SEG_CAP} restart segments" in str(e.value), str(e.value)
+    # a scan that does not fit the slot: 0.5 bits per pixel reserved, q = 100 noise takes more than 8
+    small = jpeg_lib.stream_capacity(272, 272, 0.5)
+    fat = _jpeg(noise(272, 272), quality=100)
+    ramp = np.add.outer(np.arange(272), np.arange(272))[..., None].repeat(3, 2) // 3
+    lean = [write(f"lean{i}.jpeg", _jpeg((ramp + 20 * i).astype(np.uint8), quality=50)) for i in range(2)]
+    assert len(_scan_bytes(fat)) > small
+    paths = [lean[0], lean[1], write("fat.jpeg", fat)]
+    with pytest.raises(ValueError) as e:
+        jpeg_lib.GpuDecodeBatch(3, 272, 272, bytes_per_image=small).prepare_files(paths, 2)
+    assert str(e.value).startswith(paths[2] + ":") and "bits per pixel" in str(e.value) and "AQ_JPEG_GPU_BPP" in str(e.value), str(e.value)
+
+
 @pytest.mark.gpu
 def test_gpu_entropy_decode_equals_the_host_decoder(jpeg_lib, lib):
     """aq_jpeg_huffman_decode (one lane per restart segment) on batches of same-size files: the coefficient buffers equal
@@ -333,43 +420,200 @@ def test_gpu_entropy_decode_equals_the_host_decoder(jpeg_lib, lib):
             assert np.array_equal(rgb[i], _pil(files[i]))
 
 
+def _scan_start(data):
+    sos = data.index(b"\xff\xda")
+    return sos + 2 + int.from_bytes(data[sos + 2:sos + 4], "big")
+
+
+def _gpu_decode(streams, segs, sets, n_coef):
+    """aq_jpeg_huffman_decode on host arrays: (status [nseg], coefficients [n_coef], canary intact) -- 4096 int16 canaries sit behind the
+    coefficient buffer."""
+    import torch
+    from aquaculture_amd import engine
+    coef = torch.zeros(n_coef + 4096, dtype=torch.int16, device="cuda")
+    coef[n_coef:] = 12345
+    st = engine.jpeg_huffman_decode(torch.from_numpy(streams).cuda(), torch.from_numpy(segs.view(np.uint8).reshape(-1, 32)).cuda(),
+                                    torch.from_numpy(sets).cuda(), coef).cpu().numpy()
+    out = coef.cpu().numpy()
+    return st, out[:n_coef], bool((out[n_coef:] == 12345).all())
+
+
 @pytest.mark.gpu
 def test_gpu_entropy_decode_flags_damaged_scans(jpeg_lib, lib):
     """Bits flipped inside the entropy-coded data (markers intact, so the host preparation accepts the file): every segment either decodes to
     SOME coefficients or reports status 2 -- the kernel terminates, stays inside its buffers (a canary behind them is intact), and a scan cut
-    short inside its data (the EOI kept) is reported as consumed-past-the-end."""
-    import torch
-    from aquaculture_amd import engine
-    rng = np.random.default_rng(5)
+    short inside its data (the EOI kept) is reported as consumed-past-the-end.  The same files are refused as by the host decoder, and
+    what the host decodes the GPU decodes to the same coefficients -- on standard tables, optimised tables and a file with restart markers
+    (there a file counts as decoded only if all its segments are); of the 40 mutated files of every base at least 10 go either way."""
     H, W = 96, 128
-    good = _jpeg(rng.integers(0, 255, (H, W, 3), dtype=np.uint8), quality=80)
-    sos = good.index(b"\xff\xda")
-    start = sos + 2 + int.from_bytes(good[sos + 2:sos + 4], "big")
-    files = [good]
-    for k in range(40):
-        d = bytearray(good)
-        for _ in range(1 + k % 5):
-            pos = int(rng.integers(start, len(good) - 2))
-            d[pos] = (d[pos] ^ (1 << int(rng.integers(0, 8)))) & 0xFE or 0x01          # never create 0xFF (a marker) by accident
-        files.append(bytes(d))
-    files.append(good[:start + (len(good) - start) // 3] + b"\xff\xd9")                # a third of the scan, then EOI
-    b = jpeg_lib.GpuDecodeBatch(len(files), H, W, bytes_per_image=jpeg_lib.stream_capacity(H, W, 12))
-    keep = [i for i, d in enumerate(files) if b.add(i, d) == 0]
-    assert 0 in keep and len(files) - 1 in keep and len(keep) > 30
-    # compact the accepted files into slots 0.. (finish() wants a prefix)
-    b2 = jpeg_lib.GpuDecodeBatch(len(keep), H, W, bytes_per_image=jpeg_lib.stream_capacity(H, W, 12))
-    for j, i in enumerate(keep):
-        assert b2.add(j, files[i]) == 0
-    segs, sets, first = b2.finish()
     n = jpeg_lib.coef_count(H, W)
-    coef = torch.zeros(len(keep) * n + 4096, dtype=torch.int16, device="cuda")
-    coef[len(keep) * n:] = 12345
-    st = engine.jpeg_huffman_decode(torch.from_numpy(b2.streams).cuda(), torch.from_numpy(segs.view(np.uint8).reshape(-1, 32)).cuda(),
-                                    torch.from_numpy(sets).cuda(), coef).cpu().numpy()
-    assert set(st.tolist()) <= {0, 2} and st[0] == 0 and st[-1] == 2
-    assert bool((coef[len(keep) * n:] == 12345).all())
-    host_ok = []
-    tmp, qt = np.zeros(n, np.int16), np.zeros((3, 64), np.uint16)
-    for j, i in enumerate(keep):
-        host_ok.append(jpeg_lib.decode_coeffs(files[i], tmp, qt)[0] == 0)
-    assert [s == 0 for s in st.tolist()] == host_ok                                     # the same files are refused as by the host decoder
+    # (seeds picked on the CPU, with the host decoder alone, so that both outcomes are well populated: 21 / 19, 17 / 23 and 20 / 20 of 40)
+    for name, seed, kw in (("q80", 5, dict(quality=80)), ("q95 optimised", 13, dict(quality=95, optimize=True)),
+                           ("q60 restart rows", 9, dict(quality=60, restart_marker_rows=1))):
+        rng = np.random.default_rng(seed)
+        good = _jpeg(rng.integers(0, 255, (H, W, 3), dtype=np.uint8), **kw)
+        start = _scan_start(good)
+        files = [good]
+        for k in range(40):
+            d = bytearray(good)
+            for _ in range(1 + k % 5):
+                pos = int(rng.integers(start, len(good) - 2))
+                d[pos] = (d[pos] ^ (1 << int(rng.integers(0, 8)))) & 0xFE or 0x01          # never create 0xFF (a marker) by accident
+            files.append(bytes(d))
+        last = good.rindex(b"\xff\xd4") + 2 if "restart_marker_rows" in kw else start      # (six segments: RST0 .. RST4 between them)
+        files.append(good[:last + (len(good) - last) // 3] + b"\xff\xd9")                  # a third of the (last segment's) scan, then EOI
+        b = jpeg_lib.GpuDecodeBatch(len(files), H, W, bytes_per_image=jpeg_lib.stream_capacity(H, W, 12))
+        keep = [i for i, d in enumerate(files) if b.add(i, d) == 0]
+        assert 0 in keep and len(files) - 1 in keep and len(keep) > 30, name
+        # compact the accepted files into slots 0.. (finish() wants a prefix)
+        b2 = jpeg_lib.GpuDecodeBatch(len(keep), H, W, bytes_per_image=jpeg_lib.stream_capacity(H, W, 12))
+        for j, i in enumerate(keep):
+            assert b2.add(j, files[i]) == 0
+        segs, sets, first = b2.finish()
+        st, coef, canary = _gpu_decode(b2.streams, segs, sets, len(keep) * n)
+        assert set(st.tolist()) <= {0, 2} and st[0] == 0 and st[-1] == 2, name
+        assert canary, name
+        host_ok = []
+        want, qt = np.zeros((len(keep), n), np.int16), np.zeros((3, 64), np.uint16)
+        for j, i in enumerate(keep):
+            host_ok.append(jpeg_lib.decode_coeffs(files[i], want[j], qt)[0] == 0)
+        gpu_ok = [not st[first[j]:first[j + 1]].any() for j in range(len(keep))]
+        assert gpu_ok == host_ok, name                                                  # the same files are refused as by the host decoder
+        mutated_ok = sum(host_ok[j] for j, i in enumerate(keep) if 0 < i < len(files) - 1)
+        mutated_bad = sum(not host_ok[j] for j, i in enumerate(keep) if 0 < i < len(files) - 1)
+        print(f"{name}: {len(keep) - 2} of 40 mutated files prepared, {mutated_ok} decoded by the host, {mutated_bad} refused")
+        assert mutated_ok >= 10 and mutated_bad >= 10, (name, mutated_ok, mutated_bad)
+        got = coef.reshape(len(keep), n)
+        bad = [keep[j] for j in range(len(keep)) if host_ok[j] and not np.array_equal(got[j], want[j])]
+        assert not bad, f"{name}: files {bad} decode on both sides, to different coefficients"
+
+
+# ---- scans that end early: what a lane reads, and how much it does, must not depend on bytes its segment does not own -----------------------
+#
+# A segment owns [stream_off, stream_off + ((stream_len + 8 + 15) & ~15)) (csrc/jpeg_huff.hip).  The victims below end in EOI but encode fewer
+# MCUs than their frame header promises; aq_jpeg_prepare accepts them.  Every stream tensor carries a guard tail of 4 * coef_count + 512
+# bytes behind the production-sized n * per + 256: a symbol takes at most 31 bits (16 code + 15 value) and a block at most 64 symbols, so
+# even a bit reader without any bound stays inside the allocation, and a kernel that breaks the contract fails by assertion.
+
+_SHORT_SCAN_CASES = ["cut 5 %", "cut 1/3", "cut 99 %", "empty scan 16x16", "restart segment cut", "66 files: tables from global memory",
+                     "65 files: tables in LDS"]
+_short_scan_cache = {}
+
+
+def _owned_end(seg):
+    return int(seg["stream_off"]) + ((int(seg["stream_len"]) + 8 + 15) & ~15)
+
+
+def _short_scan_case(jpeg_lib, name):
+    """Builds the case's batch (the victim in the LAST slot), decodes it three times -- every non-owned byte behind the victim's owned range
+    (the rest of its slot, the spare, the guard; for the restart victim also whatever lies between its segments) filled with zeros, 0x55
+    and another image's prepared scan, repeated -- and returns everything the tests look at.  One decode set per case for the module."""
+    if name in _short_scan_cache:
+        return _short_scan_cache[name]
+    rng = np.random.default_rng(5)
+    H, W = (16, 16) if "16x16" in name else (96, 128)
+    img, img2 = (rng.integers(0, 255, (H, W, 3), dtype=np.uint8) for _ in range(2))
+    kw = dict(quality=60, restart_marker_rows=1) if "restart" in name else dict(quality=80)
+    good, good2 = _jpeg(img, **kw), _jpeg(img2, quality=80)
+    start = _scan_start(good)
+    victim_seg = 0                                                     # the cut segment of the victim file
+    if name.startswith("cut"):
+        frac = {"cut 5 %": 0.05, "cut 1/3": 1 / 3, "cut 99 %": 0.99}[name]
+        others, victim = [good, good2], good[:start + int((len(good) - 2 - start) * frac)] + b"\xff\xd9"
+    elif "empty" in name:
+        others, victim = [good, good2], good[:start] + b"\xff\xd9"     # EOI right behind the SOS header
+    elif "restart" in name:
+        a, e = good.index(b"\xff\xd0", start) + 2, good.index(b"\xff\xd1", start)
+        others, victim, victim_seg = [good2, good], good[:a + (e - a) // 3] + good[e:], 1
+    elif "66" in name:
+        others = [good, good2] * 32 + [_jpeg(img2, quality=80, optimize=True)]          # lane 0 of the second wave: other tables
+        victim = good[:start + (len(good) - start) // 3] + b"\xff\xd9"
+    else:
+        others, victim = [good, good2] * 32, good[:start + (len(good) - start) // 3] + b"\xff\xd9"
+    files = others + [victim]
+    nf, n = len(files), jpeg_lib.coef_count(H, W)
+    per = jpeg_lib.stream_capacity(H, W, 12)
+    b = jpeg_lib.GpuDecodeBatch(nf, H, W, bytes_per_image=per)
+    for i, d in enumerate(files):
+        assert b.add(i, d) == 0, (name, i)
+    segs, sets, first = b.finish()
+    assert b.streams.size == nf * per + 256
+    vseg = int(first[nf - 1]) + victim_seg
+    owned = np.zeros(nf * per + 256 + 4 * n + 512, bool)               # production size + the guard tail
+    for sg in segs:
+        owned[int(sg["stream_off"]):_owned_end(sg)] = True
+    assert owned[:nf * per].any() and not owned[nf * per:].any()
+    foreign = ~owned
+    foreign[:_owned_end(segs[vseg])] = False                            # non-owned bytes BEHIND the victim's owned range
+    donor = b.streams[int(segs[0]["stream_off"]):int(segs[0]["stream_off"]) + int(segs[0]["stream_len"])]
+    runs = []
+    for fill in ("zeros", "0x55", "scan"):
+        streams = np.zeros(owned.size, np.uint8)
+        streams[:b.streams.size] = b.streams
+        k = int(foreign.sum())
+        streams[foreign] = 0 if fill == "zeros" else 0x55 if fill == "0x55" else np.resize(donor, k)
+        runs.append(_gpu_decode(streams, segs, sets, nf * n))
+    want = np.zeros((nf, n), np.int16)
+    host_rc = [jpeg_lib.decode_coeffs(d, want[i], np.zeros((3, 64), np.uint16))[0] for i, d in enumerate(files)]
+    intact = np.zeros(n, np.int16)                                      # the victim's file before it was cut
+    assert jpeg_lib.decode_coeffs(good, intact, np.zeros((3, 64), np.uint16))[0] == 0
+    case = dict(H=H, W=W, n=n, nf=nf, segs=segs, first=first, vseg=vseg, runs=runs, want=want, host_rc=host_rc, intact=intact)
+    _short_scan_cache[name] = case
+    return case
+
+
+def _mcu_rows(coef, H, W):
+    """[mcu_rows][values]: the coefficients of a 4:2:0 image grouped by MCU row (two Y block rows, one Cb, one Cr)."""
+    rows, cols = (H + 15) // 16, (W + 15) // 16
+    ny, nc = 4 * rows * cols * 64, rows * cols * 64
+    return np.concatenate([coef[:ny].reshape(rows, -1), coef[ny:ny + nc].reshape(rows, -1), coef[ny + nc:].reshape(rows, -1)], axis=1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", _SHORT_SCAN_CASES)
+def test_gpu_entropy_decode_of_a_short_scan_ignores_foreign_bytes(jpeg_lib, lib, name):
+    """A lane whose segment ends before its MCUs do -- a damaged file, a half-written tile closed properly, a restart interval cut short --
+    must not decode what follows its segment.  Whatever the bytes behind the victim's owned range hold, the status vector and the
+    coefficient tensor are the same; the victim gets status 2 (the host refuses it too), every other file status 0 and the host decoder's
+    coefficients (for the restart victim: every other SEGMENT, the third one's genuine data right behind the cut one), and the canary
+    behind the coefficient buffer is intact.  The victim sits in the last slot, so an unbounded reader runs into the spare and the guard.
+    Cases: scans cut after 5 %, 1/3 and 99 % of their bytes; an empty scan (stream_len 0); the second of six restart segments cut to a
+    third; the victim as lane 1 of a second wave whose lane 0 has other Huffman tables (it reads its own from global memory) and as lane 0
+    (tables staged in LDS)."""
+    c = _short_scan_case(jpeg_lib, name)
+    (st0, coef0, canary0), nf, n, first, vseg = c["runs"][0], c["nf"], c["n"], c["first"], c["vseg"]
+    for fill, (st, coef, canary) in zip(("zeros", "0x55", "scan"), c["runs"]):
+        assert canary, fill
+        assert st.tolist() == st0.tolist(), f"status with {fill} behind the victim's segment differs from the run with zeros"
+        diff = int((coef != coef0).sum())
+        assert diff == 0, f"{diff} coefficients with {fill} behind the victim's segment differ from the run with zeros"
+    assert st0[vseg] == 2 and c["host_rc"][-1] != 0
+    assert not np.delete(st0, vseg).any(), st0.tolist()
+    assert c["host_rc"][:-1] == [0] * (nf - 1)
+    got = coef0.reshape(nf, n)
+    bad = [i for i in range(nf - 1) if not np.array_equal(got[i], c["want"][i])]
+    assert not bad, f"files {bad} differ from the host decoder's coefficients"
+    if vseg != first[nf - 1]:                                           # restart rows: segment s = MCU row s; all but the cut one as in the intact file
+        H, W = c["H"], c["W"]
+        rows_got, rows_want = _mcu_rows(got[nf - 1], H, W), _mcu_rows(c["intact"], H, W)
+        keep = [r for r in range(rows_got.shape[0]) if r != vseg - first[nf - 1]]
+        assert len(keep) == 5 and np.array_equal(rows_got[keep], rows_want[keep])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", _SHORT_SCAN_CASES)
+def test_gpu_entropy_decode_of_a_short_scan_does_bounded_work(jpeg_lib, lib, name):
+    """With zeros behind the segment, at most 3 blocks of the victim's buffer are "stray" -- non-zero and different from the intact file's
+    block: one block straddles the end of the data; behind the end a lane may use at most 16 more bytes plus the 64 bits already in its
+    accumulator, 192 bits in all, and with the standard tables the zero padding costs at least 3 bits per stored coefficient: at most 64
+    coefficients, two further blocks.  (A reader without the bound fills every block behind the cut with -1s.  The kernel stops earlier than
+    the derivation allows -- no word that ends past stream_len + 8 bytes -- and these cases give 1 or 2 stray blocks; the derivation is not
+    tight the other way for every cut, though: zero bits end a chroma block after 4 bits with its DC stored, so a cut inside an MCU's
+    fourth Y block can leave that block, Cb, Cr and the next Y block stray.)"""
+    c = _short_scan_case(jpeg_lib, name)
+    n, nf = c["n"], c["nf"]
+    got = c["runs"][0][1].reshape(nf, n)[nf - 1].reshape(-1, 64)
+    intact = c["intact"].reshape(-1, 64)
+    stray = got.any(axis=1) & (got != intact).any(axis=1)
+    print(f"{name}: {int(stray.sum())} stray blocks of {stray.size}")
+    assert int(stray.sum()) <= 3, np.nonzero(stray)[0].tolist()
