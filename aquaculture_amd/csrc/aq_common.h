@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdlib.h>
 #include "../../include/aq_engine.h"
+#include "size_guards.h"   // the launchers' size limits (host arithmetic)
 
 typedef unsigned short bf16_t;  // raw bf16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;

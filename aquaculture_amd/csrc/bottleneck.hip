@@ -534,8 +534,8 @@ int launch_btl(BtlParams p, hipStream_t stream) {
     using G = BtlGeom<MBW, MSPLIT, NW, TW, KT, W1REG, RESG>;
     auto fn = bottleneck_kernel<MBW, MSPLIT, NW, TW, KT, W1REG, RESG>;
     constexpr size_t lds = G::LDS;
+    static_assert(TW == sg::btl_tile_w(G::C) && G::TH == sg::btl_tile_h(G::C), "size_guards.h counts these tiles (aq_bottleneck has checked them)");
     p.tiles_x = (p.W + TW - 1) / TW; p.tiles_y = (p.H + G::TH - 1) / G::TH;
-    AQ_REQUIRE((long long)p.B * p.tiles_x * p.tiles_y < (1LL << 30), "bottleneck: batch too large");
     p.n_tiles = p.B * p.tiles_x * p.tiles_y;
     int cus = 0;
     AQ_CHECK_HIP(aq_cus(&cus));
@@ -579,13 +579,11 @@ bool btl_asm_enabled() {
     return on;
 }
 
-// Does the assembly kernel take this launch?  (16 x 16 tiles; 32-bit buffer offsets; magic-number tile decode needs >= 2 tiles per row and image.)
+// Does an assembly kernel (C = 48: 16 x 16 tiles, C = 96: 8 x 16) take this launch?  The switches here, the sizes in sg::btl_asm_tiles_fit.
 bool btl_asm_fits(int C, int B, int H, int W, int in_ld, int out_ld) {
-    if (C != 48 || !btl_asm_enabled() || btl_wide()) return false;
-    const long long tx = (W + 15) / 16, ty = (H + 15) / 16, tpi = tx * ty, nt = tpi * B;
-    if (tx < 2 || tpi < 2 || nt >= (1LL << 24) || nt * tpi >= (1LL << 32)) return false;
-    if ((long long)B * H * W * in_ld * 2 >= (1LL << 30) || (long long)B * H * W * out_ld * 2 >= (1LL << 31)) return false;
-    return true;
+    static const bool off96 = [] { const char* e = getenv("AQ_BTL96_ASM"); return e && *e == '0'; }();
+    if ((C != 48 && C != 96) || (C == 96 && off96) || !btl_asm_enabled() || btl_wide()) return false;
+    return sg::btl_asm_tiles_fit(C, B, H, W, in_ld, out_ld);
 }
 
 int launch_btl_asm(const BtlParams& p, hipStream_t stream) {
@@ -646,16 +644,6 @@ const unsigned char kBtl96AsmCode[] = {
 #include "bottleneck96_asm_hsaco.inc"
 };
 constexpr size_t kBtl96AsmWBytes = (size_t)2 * (9 + 81) * 1024;     // per channel half: nine A fragments of the 1x1, 81 of the 3x3
-
-// Does the C = 96 assembly kernel take this launch?  (8 x 16 tiles; 32-bit buffer offsets; magic-number tile decode needs >= 2 tiles per row and image.)
-bool btl96_asm_fits(int C, int B, int H, int W, int in_ld, int out_ld) {
-    static const bool off = [] { const char* e = getenv("AQ_BTL96_ASM"); return e && *e == '0'; }();
-    if (C != 96 || off || !btl_asm_enabled() || btl_wide()) return false;
-    const long long tx = (W + 15) / 16, ty = (H + 7) / 8, tpi = tx * ty, nt = tpi * B;
-    if (tx < 2 || tpi < 2 || nt >= (1LL << 24) || nt * tpi >= (1LL << 32)) return false;
-    if ((long long)B * H * W * in_ld * 2 >= (1LL << 30) || (long long)B * H * W * out_ld * 2 >= (1LL << 31)) return false;
-    return true;
-}
 
 int launch_btl96_asm(const BtlParams& p, hipStream_t stream) {
     int cus = 0;
@@ -735,13 +723,13 @@ void btl_tail_pack_w3(const float* w3, bf16_t* dst) {
 
 // 1 when aq_bottleneck takes this launch on a generated-assembly build (C = 48 or 96), 0 when it runs the HIP-source kernel.
 extern "C" int aq_bottleneck_asm_form(int C, int B, int H, int W, int in_ld, int out_ld) {
-    return btl_asm_fits(C, B, H, W, in_ld, out_ld) || btl96_asm_fits(C, B, H, W, in_ld, out_ld);
+    return btl_asm_fits(C, B, H, W, in_ld, out_ld);
 }
 
 // AQ_C3TAIL=0 (the engine's A/B switch) is read by the engine; this query follows btl_asm_fits, plus the concat's 32-bit row offsets.
 extern "C" int aq_bottleneck_c3tail_supported(int B, int H, int W, int in_ld, int cat_ld, int out_ld) {
     if (!btl_asm_fits(48, B, H, W, in_ld, out_ld)) return 0;
-    return (long long)B * H * W * cat_ld * 2 < (1LL << 31) && in_ld % 8 == 0 && cat_ld % 8 == 0 && out_ld % 8 == 0;
+    return sg::c3tail_cat_fits(B, H, W, cat_ld) && in_ld % 8 == 0 && cat_ld % 8 == 0 && out_ld % 8 == 0;
 }
 
 // w1 (48,1,1,48), w2 (48,3,3,48), w3 (96,1,1,96) fp32 KRSC -> the tail kernel's weight image (bias: b1 | b2 | b3 as 192 floats, the caller's).
@@ -856,7 +844,7 @@ extern "C" int aq_bottleneck(const void* in_dev, int in_ld, int in_choff, void* 
     AQ_REQUIRE(B > 0 && H > 0 && W > 0, "bottleneck: empty input");
     AQ_REQUIRE(in_ld % 8 == 0 && out_ld % 8 == 0 && in_choff % 8 == 0 && out_choff % 8 == 0 && in_choff + C <= in_ld && out_choff + C <= out_ld,
                "bottleneck: channel slices must be 8-aligned and inside their rows");
-    AQ_REQUIRE((long long)B * H * W < (1LL << 31), "bottleneck: batch too large");
+    AQ_REQUIRE(sg::bottleneck_fits(C, B, H, W), "bottleneck: batch too large");
     BtlParams p{};
     p.in = (const char*)in_dev + (size_t)in_choff * 2; p.in_ld_b = in_ld * 2;
     p.out = (char*)out_dev + (size_t)out_choff * 2; p.out_ld_b = out_ld * 2;
@@ -873,15 +861,9 @@ extern "C" int aq_bottleneck(const void* in_dev, int in_ld, int in_choff, void* 
     AQ_REQUIRE(p.zero, "bottleneck: zero page allocation failed");
     const hipStream_t st = (hipStream_t)stream;
     if (btl_asm_fits(C, B, H, W, in_ld, out_ld)) {
-        BtlShape sh48;
-        btl_shape(48, &sh48);
-        p.w += (size_t)sh48.msplit * ((48 / 8 + 3) / 4 + (9 * 48 / 8 + 3) / 4) * sh48.mbw * 64 * 16;      // skip the HIP kernel's image
-        return launch_btl_asm(p, st);
-    }
-    if (btl96_asm_fits(C, B, H, W, in_ld, out_ld)) {
-        const int cb = 96 / 8, ks1 = (cb + 3) / 4, ks2 = (9 * cb + 3) / 4;
+        const int cb = C / 8, ks1 = (cb + 3) / 4, ks2 = (9 * cb + 3) / 4;
         p.w += (size_t)sh.msplit * (ks1 + ks2) * sh.mbw * 64 * 16;                                       // skip the HIP kernel's image
-        return launch_btl96_asm(p, st);
+        return C == 48 ? launch_btl_asm(p, st) : launch_btl96_asm(p, st);
     }
     switch (C) {
         case 16: return launch_btl<1, 1, 4, 32, 0, false, false>(p, st);

@@ -82,7 +82,7 @@ extern "C" int aq_conv1x1_asm(const void* in_dev, int in_ld, int in_choff, void*
     AQ_REQUIRE(in_ld % 8 == 0 && out_ld % 4 == 0 && in_choff % 8 == 0 && out_choff % 4 == 0 && in_choff + cin <= in_ld && out_choff + cout <= out_ld,
                "conv1x1_asm: channel slices must be aligned and inside their rows");
     // 32-bit buffer offsets; "no tile left" fetches from in_bytes + 0x100 + lane parts, which must not wrap
-    AQ_REQUIRE(npix > 0 && npix * (long long)in_ld * 2 < (1LL << 31) - (1LL << 22) && npix * (long long)out_ld * 2 < (1LL << 32) - (1LL << 22),
+    AQ_REQUIRE(npix > 0 && sg::conv1x1_asm_fits(npix, in_ld, out_ld),
                "conv1x1_asm: tensor too large for 32-bit offsets");
     int cus = 0;
     AQ_CHECK_HIP(aq_cus(&cus));

@@ -198,7 +198,7 @@ extern "C" int aq_conv1x1_direct(const void* in_dev, int in_ld, int in_choff, vo
                                  const void* packed_w_dev, const float* bias_dev, long long npix, int act, void* stream) {
     AQ_REQUIRE(in_dev && out_dev && packed_w_dev && bias_dev, "conv1x1_direct: null pointer");
     AQ_REQUIRE(aq_conv1x1_direct_supported(cin, cout), "conv1x1_direct: unsupported %d -> %d", cin, cout);
-    AQ_REQUIRE(npix > 0 && npix < (1LL << 31), "conv1x1_direct: bad pixel count");
+    AQ_REQUIRE(npix > 0 && sg::conv1x1_direct_fits(npix), "conv1x1_direct: bad pixel count");
     AQ_REQUIRE(in_ld % 8 == 0 && out_ld % 8 == 0 && in_choff % 8 == 0 && out_choff % 8 == 0 && in_choff + cin <= in_ld && out_choff + cout <= out_ld,
                "conv1x1_direct: channel slices must be 8-aligned and inside their rows");
     C1Params p{};
@@ -223,7 +223,7 @@ extern "C" int aq_conv1x1_direct_f8out(const void* in_dev, int in_ld, int in_cho
                                        void* stream) {
     AQ_REQUIRE(in_dev && out_dev && packed_w_dev && bias_dev, "conv1x1_direct_f8out: null pointer");
     AQ_REQUIRE((cin == 192 && cout == 192) || (cin == 384 && cout == 384), "conv1x1_direct_f8out: unsupported %d -> %d", cin, cout);
-    AQ_REQUIRE(npix > 0 && npix < (1LL << 31) && out_scale > 0.0f, "conv1x1_direct_f8out: bad pixel count or scale");
+    AQ_REQUIRE(npix > 0 && sg::conv1x1_direct_fits(npix) && out_scale > 0.0f, "conv1x1_direct_f8out: bad pixel count or scale");
     AQ_REQUIRE(in_ld % 8 == 0 && in_choff % 8 == 0 && in_choff + cin <= in_ld && out_pitch_bytes % 8 == 0 && out_byte_off % 8 == 0 &&
                    out_byte_off + cout <= out_pitch_bytes, "conv1x1_direct_f8out: slices must be 8-byte aligned and inside their rows");
     C1Params p{};

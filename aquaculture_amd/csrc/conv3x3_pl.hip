@@ -522,12 +522,11 @@ static int pl_conv(const void* in_dev, long long in_sp, long long in_ss, int cin
                    int B, int H, int W, int act, void* stream, bool w8, int pick_B) {
     AQ_REQUIRE(in_dev && out_dev && packed_w_dev && bias_dev, "conv3x3_pl: null pointer");
     AQ_REQUIRE(aq_conv3x3_pl_supported(cin, cout), "conv3x3_pl: unsupported %d -> %d", cin, cout);
-    AQ_REQUIRE(B > 0 && H > 0 && W > 0 && (long long)B * (H + 1) * (W + 1) + W + 2 < (1LL << 23), "conv3x3_pl: shape outside the fast-index range");
+    AQ_REQUIRE(B > 0 && H > 0 && W > 0 && sg::pl3x3_index_fits(B, H, W), "conv3x3_pl: shape outside the fast-index range");
     AQ_REQUIRE(in_sp % 16 == 0 && in_ss % 16 == 0 && out_ld % 4 == 0 && out_choff % 4 == 0 && out_choff + cout <= out_ld,
                "conv3x3_pl: slices must be 8-byte aligned and inside their rows");
     AQ_REQUIRE(!res_dev || (res_ld % 4 == 0 && res_choff % 4 == 0 && res_choff + cout <= res_ld), "conv3x3_pl: bad residual slice");
-    AQ_REQUIRE((long long)B * H * W * out_ld * 2 < (1LL << 31) && (long long)B * H * W * res_ld * 2 < (1LL << 31),
-               "conv3x3_pl: output / residual tensors beyond the 32-bit offset range");
+    AQ_REQUIRE(sg::pl3x3_offsets_fit(B, H, W, out_ld, res_ld), "conv3x3_pl: output / residual tensors beyond the 32-bit offset range");
     int cus = 0;
     AQ_CHECK_HIP(aq_cus(&cus));
     PlParams p{};
@@ -571,7 +570,7 @@ static int pl_conv(const void* in_dev, long long in_sp, long long in_ss, int cin
     AQ_REQUIRE(k >= 0 || fam >= 0, "conv3x3_pl: no tile of this kernel fits a %d-wide image in its region rows", W);
     const int bn = nb * 16;
     const long long ntiles = ((long long)p.npix + bn - 1) / bn * p.n_mt;
-    AQ_REQUIRE(ntiles > 0 && ntiles < (1LL << 30), "conv3x3_pl: bad tile count");
+    AQ_REQUIRE(ntiles > 0 && ntiles < (1LL << 30), "conv3x3_pl: bad tile count");       // (a cross-check: sg::pl3x3_index_fits implies it)
     p.ntiles = (int)ntiles;
     if (fam >= 0) {
         long long grid = (long long)cus * kPlAsm[fam].occ;
@@ -740,7 +739,7 @@ extern "C" int aq_conv3x3_pl_s2_supported(int cin, int cout, int B, int H, int W
     if (cin < 64 || cin % 32 || cout % PL_BM || cout > 960 || B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return 0;
     const int n_mt = cout / PL_BM;
     if (n_mt & (n_mt - 1)) return 0;
-    if ((long long)B * (H / 2 + 1) * (W / 2 + 1) + W / 2 + 2 >= (1LL << 23)) return 0;
+    if (!sg::pl3x3_index_fits(B, H / 2, W / 2)) return 0;
     return pl_region_rows(B, H / 2, W / 2, -PL_S2_NB * 16) <= PL_S2_ROWS;
 }
 
@@ -782,8 +781,7 @@ extern "C" int aq_conv3x3_pl_s2(const void* in_dev, int in_ld, int in_choff, int
                "conv3x3_pl_s2: slices must be 16-byte (input) / 8-byte (output) aligned and inside their rows");
     const int Ho = H / 2, Wo = W / 2;
     // (the input goes through a buffer descriptor with num_records = 2^31: valid offsets must stay below it, the padding rows' 2^31 is beyond)
-    AQ_REQUIRE((long long)B * Ho * Wo * out_ld * 2 < (1LL << 31) && (long long)B * H * W * in_ld * 2 < (1LL << 31) && in_ld * 2 < (1 << 24),
-               "conv3x3_pl_s2: tensors beyond the 31-bit offset range");
+    AQ_REQUIRE(sg::pl3x3s2_fits(B, H, W, in_ld, out_ld), "conv3x3_pl_s2: tensors beyond the 31-bit offset range");
     int cus = 0;
     AQ_CHECK_HIP(aq_cus(&cus));
     PlAsmArgs a{};
@@ -799,7 +797,7 @@ extern "C" int aq_conv3x3_pl_s2(const void* in_dev, int in_ld, int in_choff, int
     while ((1 << a.mt_log2) < n_mt) ++a.mt_log2;
     const int bn = PL_S2_NB * 16;
     const long long ntiles = ((long long)a.npix + bn - 1) / bn * n_mt;
-    AQ_REQUIRE(ntiles > 0 && ntiles < (1LL << 30), "conv3x3_pl_s2: bad tile count");
+    AQ_REQUIRE(ntiles > 0 && ntiles < (1LL << 30), "conv3x3_pl_s2: bad tile count");    // (a cross-check: sg::pl3x3_index_fits implies it)
     a.ntiles = (int)ntiles;
     long long grid = cus;
     if (grid > ntiles) grid = ntiles;
@@ -849,7 +847,7 @@ extern "C" int aq_conv3x3_pl_f8_supported(int cin, int cout, int B, int H, int W
     if (cin < 64 || cin % 64 || cout % PL_BM || cout > 960 || B <= 0 || H <= 0 || W <= 0) return 0;
     const int n_mt = cout / PL_BM;
     if (n_mt & (n_mt - 1)) return 0;
-    if ((long long)B * (H + 1) * (W + 1) + W + 2 >= (1LL << 23)) return 0;
+    if (!sg::pl3x3_index_fits(B, H, W)) return 0;
     return pl_region_rows(B, H, W, 13 * 16) <= PL_ROWS;
 }
 
@@ -908,8 +906,7 @@ extern "C" int aq_conv3x3_pl_f8(const void* in_dev, int in_ld, int in_choff, int
     AQ_REQUIRE(in_choff % 16 == 0 && in_ld % 16 == 0 && in_choff + cin <= in_ld && out_ld % 4 == 0 && out_choff % 4 == 0 && out_choff + cout <= out_ld,
                "conv3x3_pl_f8: slices must be 16-byte (input) / 8-byte (output) aligned and inside their rows");
     AQ_REQUIRE(!res_dev || (res_ld % 4 == 0 && res_choff % 4 == 0 && res_choff + cout <= res_ld), "conv3x3_pl_f8: bad residual slice");
-    AQ_REQUIRE((long long)B * H * W * out_ld * 2 < (1LL << 31) && (long long)B * H * W * res_ld * 2 < (1LL << 31) && (long long)B * H * W * in_ld < (1LL << 31) &&
-                   in_ld < (1 << 24), "conv3x3_pl_f8: tensors beyond the 31-bit offset range");
+    AQ_REQUIRE(sg::pl3x3_f8_offsets_fit(B, H, W, in_ld, out_ld, res_ld), "conv3x3_pl_f8: tensors beyond the 31-bit offset range");
     int cus = 0;
     AQ_CHECK_HIP(aq_cus(&cus));
     PlAsmArgs a{};
@@ -924,7 +921,7 @@ extern "C" int aq_conv3x3_pl_f8(const void* in_dev, int in_ld, int in_choff, int
     const int n_mt = cout / PL_BM;
     while ((1 << a.mt_log2) < n_mt) ++a.mt_log2;
     const long long ntiles = ((long long)a.npix + 207) / 208 * n_mt;
-    AQ_REQUIRE(ntiles > 0 && ntiles < (1LL << 30), "conv3x3_pl_f8: bad tile count");
+    AQ_REQUIRE(ntiles > 0 && ntiles < (1LL << 30), "conv3x3_pl_f8: bad tile count");    // (a cross-check: sg::pl3x3_index_fits implies it)
     a.ntiles = (int)ntiles;
     long long grid = cus;
     if (grid > ntiles) grid = ntiles;

@@ -334,7 +334,8 @@ int aq_launch_conv_halo(const ConvParams& p_in, int precision, int out_f32, int 
         aq_set_error("halo conv: only 3x3 / stride 1 / pad 1 layers with same-precision output");
         return AQ_ERR_INVALID;
     }
-    if (p.npix >= (1 << 24) || p.G <= 0 || p.kgroups_pad >= (1 << 15)) { aq_set_error("halo conv: shape outside the fast-index range"); return AQ_ERR_INVALID; }
+    // (the predicate's G < 2^15 follows from kgroups_pad >= 9 G here)
+    if (!sg::igemm_index_fits(p.npix, p.kgroups_pad, p.G)) { aq_set_error("halo conv: shape outside the fast-index range"); return AQ_ERR_INVALID; }
     const int nw = k.threads / 64;
     p.halo = p.W + 1;
     p.xrows = (k.bn + 2 * p.halo + 7) / 8 * 8;
@@ -348,7 +349,7 @@ int aq_launch_conv_halo(const ConvParams& p_in, int precision, int out_f32, int 
     p.magic_ntm = (unsigned)(0x100000000ull / (unsigned)p.n_tiles_m) + 1u;
     p.bias_n = p.n_tiles_m * k.bm;
     const long long ntiles = (long long)p.n_tiles_m * p.n_tiles_n;
-    if (ntiles <= 0 || ntiles * p.n_tiles_m >= (1LL << 31)) { aq_set_error("halo conv: bad tile count"); return AQ_ERR_INVALID; }
+    if (ntiles <= 0 || !sg::igemm_tiles_fit(p.npix, p.cout, k.bm, k.bn)) { aq_set_error("halo conv: bad tile count"); return AQ_ERR_INVALID; }
     const size_t wbuf = (size_t)k.bm * 128, xb = (size_t)p.xrows * 128;
     const size_t lds = 2 * wbuf + 2 * xb + 128 + (size_t)p.bias_n * 4;
     const size_t stg = (size_t)nw * aqdev::kStgBytes;

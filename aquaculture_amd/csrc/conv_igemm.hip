@@ -620,7 +620,7 @@ int aq_launch_conv(const ConvParams& p_in, int precision, int out_f32, int cfg_i
     const ConvConfig& k = kConfigs[cfg];
     ConvParams p = p_in;
     if (k.bm > kConvCoutSlack) { aq_set_error("conv: config %d is taller than the packed weights' zero rows", cfg); return AQ_ERR_INVALID; }
-    if (p.npix >= (1 << 24) || p.kgroups_pad >= (1 << 15) || p.G <= 0 || p.G >= (1 << 15) || p.k <= 0) {
+    if (!sg::igemm_index_fits(p.npix, p.kgroups_pad, p.G) || p.k <= 0) {
         aq_set_error("conv: shape outside the fast-index range (npix=%d kgroups=%d)", p.npix, p.kgroups_pad);
         return AQ_ERR_INVALID;
     }
@@ -640,9 +640,9 @@ int aq_launch_conv(const ConvParams& p_in, int precision, int out_f32, int cfg_i
     const size_t lds = conv_lds_bytes(k, variant == 3 ? 2 * p.bias_n : p.bias_n);
     if (lds > 160 * 1024) { aq_set_error("conv: config %d needs %zu B of LDS", cfg, lds); return AQ_ERR_INVALID; }
     const long long ntiles = (long long)p.n_tiles_m * p.n_tiles_n;
-    if (ntiles <= 0 || ntiles > 0x7fffffffLL) { aq_set_error("conv: bad tile count %lld", ntiles); return AQ_ERR_INVALID; }
+    if (ntiles <= 0 || ntiles > 0x7fffffffLL) { aq_set_error("conv: bad tile count %lld", ntiles); return AQ_ERR_INVALID; }   // (a cross-check: sg::igemm_tiles_fit below implies the upper bound)
     p.magic_ntm = (unsigned)(0x100000000ull / (unsigned)p.n_tiles_m) + 1u;
-    if (ntiles * p.n_tiles_m >= (1LL << 31)) { aq_set_error("conv: too many tiles"); return AQ_ERR_INVALID; }
+    if (!sg::igemm_tiles_fit(p.npix, p.cout, k.bm, k.bn)) { aq_set_error("conv: too many tiles"); return AQ_ERR_INVALID; }
     // persistent grid: as many workgroups as stay resident, capped by the tile count
     int cus = 0, blocks = 0;
     AQ_CHECK_HIP(aq_cus(&cus));

@@ -423,13 +423,12 @@ int down_common(DownParams& p, const void* in_dev, int in_ld, int in_choff, int 
     AQ_REQUIRE(B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "downblock: H and W must be even (got %dx%d)", H, W);
     AQ_REQUIRE(in_ld % 8 == 0 && out_ld % 8 == 0 && in_choff % 8 == 0 && out_choff % 8 == 0 && in_choff + cin <= in_ld && out_choff + cout <= out_ld,
                "downblock: channel slices must be 8-aligned and inside their rows");
-    AQ_REQUIRE((long long)B * H * W < (1LL << 31), "downblock: batch too large");
+    AQ_REQUIRE(sg::down_fits(B, H, W, th), "downblock: batch too large");
     p.in = (const char*)in_dev + (size_t)in_choff * 2; p.in_ld_b = in_ld * 2;
     p.out = (char*)out_dev + (size_t)out_choff * 2; p.out_ld_b = out_ld * 2;
     p.w = (const char*)packed_w_dev; p.bias = bias_dev;
     p.B = B; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2;
     p.tiles_x = (p.Wo + kTW - 1) / kTW; p.tiles_y = (p.Ho + th - 1) / th;
-    AQ_REQUIRE((long long)B * p.tiles_x * p.tiles_y < (1LL << 30), "downblock: batch too large");
     p.n_tiles = B * p.tiles_x * p.tiles_y;
     p.zero = aq_zero_page();
     AQ_REQUIRE(p.zero, "downblock: zero page allocation failed");
@@ -482,6 +481,9 @@ int pack_down(const float* wa_host, const float* wb_host, int cin, int cmid, voi
     return AQ_OK;
 }
 
+static_assert(kTW == sg::kDownTW && DownGeom<48, 96, true, 0>::TH == sg::kDownblockTH && DownGeom<48, 96, true, 0, true>::TH == sg::kDownblockTH &&
+                  DownGeom<96, 192, false, 3>::TH == sg::kConv3x3s2TH, "size_guards.h counts these tiles");
+
 }  // namespace
 
 // Fused form: wa KRSC (96,3,3,48), wb KRSC (96,1,1,96).
@@ -509,7 +511,7 @@ extern "C" int aq_stemdown(const uint8_t* tiles_dev, void* out_dev, int out_ld, 
                            const void* packed_w_dev, const float* bias_dev, int B, int Hi, int Wi, void* stream) {
     AQ_REQUIRE(tiles_dev && stem_w_dev && stem_bias_dev, "stemdown: null pointer");
     AQ_REQUIRE(aq_stemdown_supported(Hi, Wi) && ((uintptr_t)tiles_dev & 3) == 0, "stemdown: tile size %dx%d must be a multiple of 4, tiles 4-byte aligned", Hi, Wi);
-    AQ_REQUIRE((long long)B * Hi * Wi * 3 < (1LL << 40), "stemdown: batch too large");
+    AQ_REQUIRE(sg::tile_bytes_fit(B, Hi, Wi), "stemdown: batch too large");
     DownParams p{};
     // `in` is unused by the stem-fused form; down_common only offsets it
     const int rc = down_common(p, tiles_dev, 48, 0, 48, out_dev, out_ld, out_choff, 96, packed_w_dev, bias_dev, B, Hi / 2, Wi / 2, DownGeom<48, 96, true, 0, true>::TH);

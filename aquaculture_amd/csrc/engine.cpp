@@ -439,14 +439,26 @@ bool heads_fused(const aq_engine* e) {
     return n_heads == 3;
 }
 
-// The size guards of the launchers, restated per op for a batch of B tiles of H x W: the first op that no kernel it can launch accepts
-// (-1: all fit), with the guard that refuses it in `why`.  A conv whose direct form (tuned table, aq_engine_set_conv_config) refuses the
-// batch falls back to the implicit-GEMM / halo kernel unless the form was forced (run_conv); the fp8 pairs fall back to that bf16 form.
-// Each term is the launcher's own AQ_REQUIRE / *_fits predicate; every one grows with B.
+// Does the implicit-GEMM / halo launcher take npix output pixels of conv op oi?  On the tile shape run_conv passes first: cfg where it is
+// one (conv_cfg / the tuned table), else the heuristic's.  (A table's shape that refuses a batch other than the table's is retried by
+// run_conv on the heuristic shape; the tile-count term is not checked again for that retry, so the answer can only be the stricter one.)
+bool igemm_takes(const aq_engine* e, int oi, int cfg, long long npix) {
+    const PackedW& pw = e->packed[oi];
+    if (!sg::igemm_index_fits(npix, pw.kgroups_pad, pw.G)) return false;
+    const int shape = cfg & ~AQ_CONV_CFG_ONE_TILE_PER_WG, cout = e->ops[oi].dst.channels;
+    int bm = 0, bn = 0;
+    if (cfg < 0 || shape >= AQ_CONV_CFG_DIRECT1X1) cfg = aq_conv_pick_config(cout, (int)npix, e->desc.precision);
+    return aq_conv_config_tiles(cfg, &bm, &bn) == AQ_OK && sg::igemm_tiles_fit(npix, cout, bm, bn);
+}
+
+// The first plan op that no kernel it can launch accepts for a batch of B tiles of H x W (-1: all fit), with the guard that refuses it in
+// `why`.  Every limit is the launcher's own predicate (size_guards.h); only the decode / NMS grid cap is stated here.  A conv whose direct
+// form (tuned table, aq_engine_set_conv_config) refuses the batch falls back to the implicit-GEMM / halo kernel unless the form was forced
+// (run_conv); the fp8 pairs fall back to that bf16 form.  Every predicate only gets harder to meet as B grows.
 int plan_unfit_op(const aq_engine* e, long long B, int H, int W, char* why, size_t why_len) {
     char dummy[8];
     if (!why) { why = dummy; why_len = sizeof dummy; }
-    const int eb = aq_elem_bytes(e->desc.precision);
+    const int prec = e->desc.precision, eb = aq_elem_bytes(prec);
     const aq_engine::Tuned* tt = nullptr;
     for (const aq_engine::Tuned& t : e->tuned)
         if (t.H == H && t.W == W) tt = &t;
@@ -461,50 +473,46 @@ int plan_unfit_op(const aq_engine* e, long long B, int H, int W, char* why, size
         if (op.dst.tensor >= 0) dims(op.dst.tensor, &hd, &wd);
         const long long ld_s = op.src.tensor >= 0 ? e->tensors[op.src.tensor].channels : 0;
         const long long ld_d = op.dst.tensor >= 0 ? e->tensors[op.dst.tensor].channels : 0;
+        const long long groups = op.src.channels * eb / 16;
         switch (op.kind) {
         case AQ_OP_PREPROCESS:
-            if (B * (H / 2) * (W / 2) >= (1LL << 31)) return fail(oi, "preprocess: %lld output pixels >= 2^31", B * (H / 2) * (W / 2));
+            if (!sg::preprocess_fits(B, H, W)) return fail(oi, "preprocess: %lld output pixels >= 2^31", B * (H / 2) * (W / 2));
             break;
         case AQ_OP_STEM:
-            if (B * H * W * 3 >= (1LL << 32) || B * hd * wd >= (1LL << 31)) return fail(oi, "stem: %lld input bytes >= 2^32 or output pixels >= 2^31", B * H * W * 3);
+            if (!sg::stem_fits(B, H, W)) return fail(oi, "stem: %lld input bytes >= 2^32 or output pixels >= 2^31", B * H * W * 3);
             break;
         case AQ_OP_DOWNBLOCK:
-            if (B * hs * ws >= (1LL << 31)) return fail(oi, "down-block: %lld input pixels >= 2^31", B * hs * ws);
+            if (!sg::downblock_fits(B, hs, ws)) return fail(oi, "down-block: %lld input pixels >= 2^31 or output tiles >= 2^30", B * hs * ws);
             break;
         case AQ_OP_BOTTLENECK:
-            if (B * hs * ws >= (1LL << 31)) return fail(oi, "Bottleneck: %lld pixels >= 2^31", B * hs * ws);
+            if (!sg::bottleneck_fits(op.src.channels, B, hs, ws)) return fail(oi, "Bottleneck: %lld pixels >= 2^31 or tiles >= 2^30", B * hs * ws);
             break;
         case AQ_OP_SPPF_POOL:
-            if (B * hs * ws * (op.src.channels * eb / 16) >= (1LL << 31))
-                return fail(oi, "SPPF pool: %lld 16-byte groups >= 2^31", B * hs * ws * (op.src.channels * eb / 16));
+            if (!sg::sppf_pool_fits(B, hs, ws, groups)) return fail(oi, "SPPF pool: %lld 16-byte groups >= 2^31", B * hs * ws * groups);
             break;
         case AQ_OP_UPSAMPLE2X:
-            if (B * hs >= 65536) return fail(oi, "upsample2x: %lld input rows >= 65536", B * hs);
-            if (B * 4 * hs * ws * (op.src.channels * eb / 16) >= (1LL << 31))
-                return fail(oi, "upsample2x: %lld 16-byte groups >= 2^31", B * 4 * hs * ws * (op.src.channels * eb / 16));
+            if (!sg::upsample2x_rows_fit(B, hs)) return fail(oi, "upsample2x: %lld input rows >= 65536", B * hs);
+            if (!sg::upsample2x_fits(B, hs, ws, groups)) return fail(oi, "upsample2x: %lld 16-byte groups >= 2^31", B * 4 * hs * ws * groups);
             break;
         case AQ_OP_CONV: {
             const long long npix = B * hd * wd;
-            if (op.level >= 0 && fused && npix >= (1LL << 30)) return fail(oi, "fused head + decode: %lld pixels >= 2^30", npix);
-            const bool igemm = npix < (1LL << 24);        // aq_launch_conv / aq_launch_conv_halo: the fast-index range
+            if (op.level >= 0 && fused && !sg::head_decode_fits(B, hd, wd)) return fail(oi, "fused head + decode: %lld pixels >= 2^30", npix);
             const int cfg = e->conv_cfg[oi] >= 0 ? e->conv_cfg[oi] : (tt ? tt->cfg[oi] : -1);
             const long long ld_r = op.res.tensor >= 0 ? e->tensors[op.res.tensor].channels : 0;
             bool form = false;
             switch (cfg & ~AQ_CONV_CFG_ONE_TILE_PER_WG) {
-            case AQ_CONV_CFG_DIRECT1X1: form = npix < (1LL << 31); break;
-            case AQ_CONV_CFG_ASM1X1: form = npix * ld_s * 2 < (1LL << 31) - (1LL << 22) && npix * ld_d * 2 < (1LL << 32) - (1LL << 22); break;
-            case AQ_CONV_CFG_DIRECT3X3S2: form = B * hs * ws < (1LL << 31); break;
-            case AQ_CONV_CFG_PL3X3:
-                form = B * (hs + 1) * (ws + 1) + ws + 2 < (1LL << 23) && npix * ld_d * 2 < (1LL << 31) && npix * ld_r * 2 < (1LL << 31);
-                break;
-            case AQ_CONV_CFG_PL3X3S2:                      // (the query checks the index range; aq_conv3x3_pl_s2 the 31-bit byte offsets)
-                form = B <= INT32_MAX && aq_conv3x3_pl_s2_supported(op.src.channels, op.dst.channels, (int)B, (int)hs, (int)ws) &&
-                       npix * ld_d * 2 < (1LL << 31) && B * hs * ws * ld_s * 2 < (1LL << 31);
+            case AQ_CONV_CFG_DIRECT1X1: form = sg::conv1x1_direct_fits(npix); break;
+            case AQ_CONV_CFG_ASM1X1: form = sg::conv1x1_asm_fits(npix, ld_s, ld_d); break;
+            case AQ_CONV_CFG_DIRECT3X3S2: form = sg::conv3x3s2_direct_fits(B, hs, ws); break;
+            case AQ_CONV_CFG_PL3X3: form = sg::pl3x3_index_fits(B, hs, ws) && sg::pl3x3_offsets_fit(B, hs, ws, ld_d, ld_r); break;
+            case AQ_CONV_CFG_PL3X3S2:                      // (the query adds what the image width asks of the tile's region)
+                form = aq_conv3x3_pl_s2_supported(op.src.channels, op.dst.channels, (int)B, (int)hs, (int)ws) && sg::pl3x3s2_fits(B, hs, ws, ld_s, ld_d);
                 break;
             default: form = false;
             }
             const bool forced = e->conv_cfg[oi] >= 0 && e->conv_cfg[oi] >= AQ_CONV_CFG_DIRECT1X1 && e->conv_cfg[oi] < AQ_CONV_CFG_ONE_TILE_PER_WG;
-            if (!(form || (!forced && igemm))) return fail(oi, "conv: implicit-GEMM pixel count %lld >= 2^24 and no other form takes it", npix);
+            const bool igemm = !form && !forced && igemm_takes(e, oi, cfg, npix);
+            if (!(form || igemm)) return fail(oi, "conv: %lld output pixels are past the implicit-GEMM guard (pixels < 2^24, K groups < 2^15, tile count < 2^31) and no other form takes it", npix);
             break;
         }
         default:
@@ -876,6 +884,33 @@ extern "C" int aq_conv2d(const void* in_dev, int in_ld, int in_choff, int cin, v
     const char* forced = getenv("AQ_CONV_CFG");
     if (forced && *forced) cfg = atoi(forced);
     return aq_launch_conv(p, precision, out_f32, cfg, (hipStream_t)stream);
+}
+
+extern "C" int aq_size_guard(int which, const long long* v, int n) {
+    static const int kArgs[] = {3, 4, 4, 2, 3, 3, 3, 4, 6, 4, 1, 3, 3, 5, 5, 6, 6, 3, 3};   // per aq_size_guard_id
+    if (which < 0 || which >= (int)(sizeof kArgs / sizeof kArgs[0]) || !v || n != kArgs[which]) return -1;
+    switch (which) {
+    case AQ_SG_PREPROCESS: return sg::preprocess_fits(v[0], v[1], v[2]);
+    case AQ_SG_SPPF_POOL: return sg::sppf_pool_fits(v[0], v[1], v[2], v[3]);
+    case AQ_SG_UPSAMPLE2X: return sg::upsample2x_fits(v[0], v[1], v[2], v[3]);
+    case AQ_SG_UPSAMPLE2X_ROWS: return sg::upsample2x_rows_fit(v[0], v[1]);
+    case AQ_SG_STEM: return sg::stem_fits(v[0], v[1], v[2]);
+    case AQ_SG_DOWNBLOCK: return sg::downblock_fits(v[0], v[1], v[2]);
+    case AQ_SG_CONV3X3S2_DIRECT: return sg::conv3x3s2_direct_fits(v[0], v[1], v[2]);
+    case AQ_SG_BOTTLENECK: return sg::bottleneck_fits(v[0], v[1], v[2], v[3]);
+    case AQ_SG_BTL_ASM_TILES: return sg::btl_asm_tiles_fit(v[0], v[1], v[2], v[3], v[4], v[5]);
+    case AQ_SG_C3TAIL_CAT: return sg::c3tail_cat_fits(v[0], v[1], v[2], v[3]);
+    case AQ_SG_CONV1X1_DIRECT: return sg::conv1x1_direct_fits(v[0]);
+    case AQ_SG_CONV1X1_ASM: return sg::conv1x1_asm_fits(v[0], v[1], v[2]);
+    case AQ_SG_PL3X3_INDEX: return sg::pl3x3_index_fits(v[0], v[1], v[2]);
+    case AQ_SG_PL3X3_OFFSETS: return sg::pl3x3_offsets_fit(v[0], v[1], v[2], v[3], v[4]);
+    case AQ_SG_PL3X3S2: return sg::pl3x3s2_fits(v[0], v[1], v[2], v[3], v[4]);
+    case AQ_SG_PL3X3_F8_OFFSETS: return sg::pl3x3_f8_offsets_fit(v[0], v[1], v[2], v[3], v[4], v[5]);
+    case AQ_SG_IGEMM: return sg::igemm_fits(v[0], v[1], v[2], v[3], v[4], v[5]);
+    case AQ_SG_HEAD_DECODE: return sg::head_decode_fits(v[0], v[1], v[2]);
+    case AQ_SG_TILE_BYTES: return sg::tile_bytes_fit(v[0], v[1], v[2]);
+    }
+    return -1;
 }
 
 extern "C" int aq_engine_create(const aq_model_desc* d, int device, aq_engine** out) {

@@ -212,7 +212,7 @@ int head_decode_launch(const void* in_dev, int in_ld, int in_choff, int cin, con
     AQ_REQUIRE(count_stride >= 1, "head_decode: counter stride");
     AQ_REQUIRE(in_dev && packed_dev && cand_dev && cand_rows_dev && cand_count_dev && anchors_px, "head_decode: null pointer");
     AQ_REQUIRE(aq_head_decode_supported(cin, na, nc), "head_decode: unsupported cin=%d na=%d nc=%d", cin, na, nc);
-    AQ_REQUIRE(B > 0 && ny > 0 && nx > 0 && (long long)B * ny * nx < (1LL << 30) && in_ld % 8 == 0 && in_choff % 8 == 0 && in_choff + cin <= in_ld && cand_cap > 0,
+    AQ_REQUIRE(B > 0 && ny > 0 && nx > 0 && sg::head_decode_fits(B, ny, nx) && in_ld % 8 == 0 && in_choff % 8 == 0 && in_choff + cin <= in_ld && cand_cap > 0,
                "head_decode: bad geometry");
     int cus = 0;
     AQ_CHECK_HIP(aq_cus(&cus));

@@ -224,7 +224,7 @@ extern "C" int aq_preprocess_s2d(const uint8_t* tiles_dev, void* out_dev, int B,
     AQ_REQUIRE(tiles_dev && out_dev, "preprocess: null pointer");
     AQ_REQUIRE(B > 0 && H > 0 && W > 0 && (H % 2 == 0) && (W % 2 == 0), "preprocess: bad shape B=%d H=%d W=%d", B, H, W);
     const long long n = (long long)B * (H / 2) * (W / 2);
-    AQ_REQUIRE(n < (1LL << 31), "preprocess: batch too large");
+    AQ_REQUIRE(sg::preprocess_fits(B, H, W), "preprocess: batch too large");
     if (precision == AQ_FP32)
         hipLaunchKernelGGL(preprocess_s2d_kernel<true>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, tiles_dev, (char*)out_dev, B, H, W);
     else
@@ -240,7 +240,7 @@ extern "C" int aq_sppf_pool(void* buf_dev, int ld, int ch_off, int c, int B, int
     AQ_REQUIRE(ch_off + 4 * c <= ld, "sppf_pool: slices [x|y1|y2|y3] exceed the buffer width");
     const int groups = c * eb / 16;
     const long long n = (long long)B * H * W * groups;
-    AQ_REQUIRE(n < (1LL << 31), "sppf_pool: batch too large");
+    AQ_REQUIRE(sg::sppf_pool_fits(B, H, W, groups), "sppf_pool: batch too large");
     char* base = (char*)buf_dev + (long long)ch_off * eb;
     constexpr int GPB = 4;
     const size_t plane_lds = (size_t)2 * H * W * 16 * GPB;
@@ -272,9 +272,8 @@ extern "C" int aq_upsample2x(const void* in_dev, int in_ld, int in_choff, void* 
     AQ_REQUIRE((c * eb) % 16 == 0 && (in_choff * eb) % 16 == 0 && (out_choff * eb) % 16 == 0 &&
                (in_ld * eb) % 16 == 0 && (out_ld * eb) % 16 == 0, "upsample2x: channels must be 16-byte groups");
     const int groups = c * eb / 16;
-    const long long n = (long long)B * 4 * H * W * groups;
-    AQ_REQUIRE(n < (1LL << 31), "upsample2x: batch too large");
-    AQ_REQUIRE((long long)B * H < 65536, "upsample2x: more than 65535 input rows");
+    AQ_REQUIRE(sg::upsample2x_fits(B, H, W, groups), "upsample2x: batch too large");
+    AQ_REQUIRE(sg::upsample2x_rows_fit(B, H), "upsample2x: more than 65535 input rows");
     hipLaunchKernelGGL(upsample2x_kernel, dim3((unsigned)((W * groups + 255) / 256), (unsigned)(B * H)), dim3(256), 0, (hipStream_t)stream,
                        (const char*)in_dev + (long long)in_choff * eb, in_ld * eb,
                        (char*)out_dev + (long long)out_choff * eb, out_ld * eb, groups, H, W);

@@ -26,6 +26,7 @@ namespace {
 constexpr int kK = 108;                        // 6 * 6 * 3
 constexpr int kKyPad = 24;                     // K positions per ky row (18 real + 6 zero-weight)
 constexpr int kTH = 8, kTW = 64;               // output tile per workgroup: 8 rows x 64 columns, wave w owns rows 2w, 2w+1
+static_assert(kTH == sg::kStemTH && kTW == sg::kStemTW, "size_guards.h counts the stem's tiles");
 constexpr int kPH = 2 * kTH + 4;               // 20 patch rows
 constexpr int kPRowDw = 104;                   // input dwords (= 416 bytes = 416 patch elements) loaded per patch row:
                                                // bytes [6*x0 - 8, 6*x0 + 408) of the image row; pixel tx's 18+6 values start
@@ -505,9 +506,8 @@ extern "C" int aq_stem_conv(const uint8_t* tiles_dev, void* out_dev, int out_ld,
     p.w = (const char*)packed_w_dev; p.bias = bias_dev;
     p.B = B; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2;
     p.cout = cout; p.act = act; p.npix = B * p.Ho * p.Wo;
-    AQ_REQUIRE((long long)B * H * W * 3 < (1LL << 31) * 2 && (long long)B * p.Ho * p.Wo < (1LL << 31), "stem_conv: batch too large");
+    AQ_REQUIRE(sg::stem_fits(B, H, W), "stem_conv: batch too large");
     const int tiles_x = (p.Wo + kTW - 1) / kTW, tiles_y = (p.Ho + kTH - 1) / kTH;
-    AQ_REQUIRE((long long)B * tiles_x * tiles_y < (1LL << 31), "stem_conv: batch too large");
     p.n_tiles_n = B * tiles_y * tiles_x;
     p.n_tiles_m = 1;
     const hipStream_t st = (hipStream_t)stream;
@@ -548,9 +548,8 @@ extern "C" int aq_stem_conv_scaled(const uint8_t* tiles_dev, int H0, int W0, con
     p.w = (const char*)packed_w_dev; p.bias = bias_dev;
     p.B = B; p.H = hp; p.W = wp; p.Ho = hp / 2; p.Wo = wp / 2;
     p.cout = cout; p.act = act; p.npix = B * p.Ho * p.Wo;
-    AQ_REQUIRE((long long)B * H0 * W0 * 3 < (1LL << 40) && (long long)B * p.Ho * p.Wo < (1LL << 31), "stem_conv_scaled: batch too large");
+    AQ_REQUIRE(sg::tile_bytes_fit(B, H0, W0) && sg::stem_out_fits(B, p.Ho, p.Wo), "stem_conv_scaled: batch too large");
     const int tiles_x = (p.Wo + kTW - 1) / kTW, tiles_y = (p.Ho + kTH - 1) / kTH;
-    AQ_REQUIRE((long long)B * tiles_x * tiles_y < (1LL << 31), "stem_conv_scaled: batch too large");
     p.n_tiles_n = B * tiles_y * tiles_x;
     p.n_tiles_m = 1;
     const StemAugSrc src{ytab_dev, xtab_dev, H0, W0, h, w};

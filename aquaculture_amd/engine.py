@@ -64,7 +64,7 @@ class aq_det(C.Structure):
 
 # every symbol include/aq_engine.h declares (tests check the library exports all of them)
 EXPORTS = (
-    "aq_last_error", "aq_version", "aq_engine_create", "aq_engine_destroy", "aq_engine_workspace_bytes",
+    "aq_last_error", "aq_version", "aq_engine_create", "aq_engine_destroy", "aq_engine_workspace_bytes", "aq_size_guard",
     "aq_engine_infer", "aq_engine_run_ops", "aq_engine_candidates", "aq_engine_forward_raw", "aq_engine_tensor_ptr", "aq_engine_profile",
     "aq_engine_op_times", "aq_engine_num_ops", "aq_engine_set_conv_config", "aq_engine_autotune", "aq_engine_set_tuned_table",
     "aq_engine_get_conv_config", "aq_conv_num_configs", "aq_debug_conv_stamp", "aq_debug_mfma_peak",
@@ -104,6 +104,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_engine_destroy.argtypes = [vp]
     lib.aq_engine_destroy.restype = None
     lib.aq_engine_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
+    lib.aq_size_guard.argtypes = [i32, C.POINTER(C.c_longlong), i32]
     lib.aq_engine_infer.argtypes = [vp, vp, i32, i32, i32, vp, sz, vp, vp, f32, f32, i32, vp]
     lib.aq_engine_run_ops.argtypes = [vp, vp, i32, i32, i32, vp, sz, i32, i32, f32, f32, i32, vp, vp, vp]
     lib.aq_engine_candidates.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]

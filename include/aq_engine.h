@@ -107,6 +107,30 @@ void aq_engine_destroy(aq_engine* e);
  * that some plan op cannot run -- a kernel's size guard with no fallback form, checked with the launchers' own predicates -- with a
  * message naming the op ("plan op N") and the largest batch that fits. */
 int aq_engine_workspace_bytes(aq_engine* e, int max_batch, int H, int W, size_t* bytes);
+/* Test hook: one size-guard predicate of csrc/size_guards.h (the launchers' and the sizing call's limits) on the n values v, in the
+ * order of the function's arguments.  1: fits, 0: refused, -1: unknown `which` or wrong n.  Host arithmetic; needs no GPU. */
+enum aq_size_guard_id {
+    AQ_SG_PREPROCESS = 0,          /* B, H, W */
+    AQ_SG_SPPF_POOL = 1,           /* B, H, W, groups */
+    AQ_SG_UPSAMPLE2X = 2,          /* B, H, W, groups */
+    AQ_SG_UPSAMPLE2X_ROWS = 3,     /* B, H */
+    AQ_SG_STEM = 4,                /* B, H, W */
+    AQ_SG_DOWNBLOCK = 5,           /* B, H, W */
+    AQ_SG_CONV3X3S2_DIRECT = 6,    /* B, H, W */
+    AQ_SG_BOTTLENECK = 7,          /* C, B, H, W */
+    AQ_SG_BTL_ASM_TILES = 8,       /* C, B, H, W, in_ld, out_ld */
+    AQ_SG_C3TAIL_CAT = 9,          /* B, H, W, cat_ld */
+    AQ_SG_CONV1X1_DIRECT = 10,     /* npix */
+    AQ_SG_CONV1X1_ASM = 11,        /* npix, in_ld, out_ld */
+    AQ_SG_PL3X3_INDEX = 12,        /* B, H, W */
+    AQ_SG_PL3X3_OFFSETS = 13,      /* B, H, W, out_ld, res_ld */
+    AQ_SG_PL3X3S2 = 14,            /* B, H, W, in_ld, out_ld */
+    AQ_SG_PL3X3_F8_OFFSETS = 15,   /* B, H, W, in_ld_bytes, out_ld, res_ld */
+    AQ_SG_IGEMM = 16,              /* npix, kgroups_pad, G, cout, bm, bn */
+    AQ_SG_HEAD_DECODE = 17,        /* B, ny, nx */
+    AQ_SG_TILE_BYTES = 18          /* B, H, W */
+};
+int aq_size_guard(int which, const long long* v, int n);
 /* tiles_dev: uint8 [B][H][W][3] RGB.  dets_dev: [B][max_det].  counts_dev: [B].
  * Replaces `pred = model(im); pred = non_max_suppression(pred, conf, iou, None, False, max_det)`. */
 int aq_engine_infer(aq_engine* e, const uint8_t* tiles_dev, int B, int H, int W,

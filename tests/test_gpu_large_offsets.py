@@ -559,7 +559,7 @@ def test_upsample2x_past_2_31_and_row_limit(lib):
         assert torch.equal(out[i, ..., :384], x[i].repeat_interleave(2, 0).repeat_interleave(2, 1)), i
     del x, out, flat
     torch.cuda.empty_cache()
-    rows = 65535 // 40
+    rows = guards.largest(lambda B: guards.upsample2x_rows_fit(B, 40))
     x = _randn((rows + 1, 40, 8, 8), torch.bfloat16, 91)
     out, flat = _guarded((rows + 1, 80, 16, 8), torch.bfloat16)
     assert lib.aq_upsample2x(x.data_ptr(), 8, 0, out.data_ptr(), 8, 0, 8, rows, 40, 8, 0, s) == 0
@@ -613,7 +613,8 @@ def test_engine_refuses_fp32_batch_past_model1_pixel_limit(synth_ck):
     from aquaculture_amd.engine import Engine
     eng = Engine(synth_ck, "fp32", 0)
     try:
-        limit = ((1 << 24) - 1) // (160 * 160)
+        limit, op = guards.plan_batch_limit(eng.plan, 640, 640, 4)
+        assert (limit, op) == (655, "model.1")
         assert eng.workspace_bytes(limit, 640, 640) > 0
         with pytest.raises(RuntimeError, match=rf"model\.1\).*largest batch that fits is {limit}\b"):
             eng.workspace_bytes(limit + 1, 640, 640)
@@ -637,10 +638,29 @@ def test_engine_refuses_bf16_batch_past_upsample_rows(synth_ck):
         with open(os.path.join(os.path.dirname(aquaculture_amd.__file__), "data", "tuned_tables.json")) as f:
             ship = json.load(f)
         eng.set_tuned_table(64, 640, 640, ship[eng.tune_key(64, 640, 640)])
-        limit = 65535 // 40
+        limit = guards.largest(lambda B: guards.upsample2x_rows_fit(B, 40))
+        assert limit == 1638
         assert eng.workspace_bytes(limit, 640, 640) > 0
         up = [o.name for o in eng.plan.ops if o.kind == spec.OP_UPSAMPLE2X]
         with pytest.raises(RuntimeError, match=rf"\((?:{'|'.join(n.replace('.', '[.]') for n in up)})\).*largest batch that fits is {limit}\b"):
             eng.workspace_bytes(limit + 1, 640, 640)
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("precision,eb", [("bf16", 2), ("fp32", 4)])
+def test_engine_sizing_limit_at_32_px_tiles(synth_ck, precision, eb):
+    """Sizing only, nothing launched: at 32 x 32 tiles the sizing call takes the largest batch the restated predicates give for the engine's
+    plan -- 32767, set by the row guard of the second upsample (model.15: B x 2 input rows < 65536), below the 65535 grid cap -- and
+    refuses one more, naming that op and that batch."""
+    from aquaculture_amd.engine import Engine
+    eng = Engine(synth_ck, precision, 0)
+    try:
+        limit, op = guards.plan_batch_limit(eng.plan, 32, 32, eb)
+        assert 0 < limit < guards.BATCH_CAP and op is not None, (limit, op)
+        assert eng.workspace_bytes(limit, 32, 32) > 0
+        with pytest.raises(RuntimeError, match=rf"\({op.replace('.', '[.]')}\).*largest batch that fits is {limit}\b"):
+            eng.workspace_bytes(limit + 1, 32, 32)
+        assert eng._ws is None and not eng._slots, "sizing allocated a workspace"
     finally:
         eng.close()
