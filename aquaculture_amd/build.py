@@ -43,6 +43,7 @@ SOURCES = [
     ("land_filter.hip", ["-ffp-contract=off"]),  # --land-filter: boxes against the land polygons' segments; the fp64 orientation determinant exactly as written (no fma)
     ("evaluate.hip", ["-ffp-contract=off"]),     # --evaluate: member confidences over the facilities' neighbour search (the same fp64 distance test) and the box joins
     ("tonnage.hip", ["-ffp-contract=off"]),      # --tonnage: the production bootstrap; fp64 in + - x / sqrt only, every product and sum rounded as written (no fma)
+    ("depth.hip", ["-ffp-contract=off"]),        # --bathymetry: depth-raster cells under the facilities' cages; fp64 cell ranges and one written order of the sum (no fma)
     ("engine.cpp", ["-x", "hip"]),
 ]
 # -packed-fp32-ops: no v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 in compiled kernels.  The SiLU epilogues run beside other waves' MFMAs (two

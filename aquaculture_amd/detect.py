@@ -151,7 +151,15 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "uses --facilities-conf / -eps / -min-cages; needs --geocode-bboxes and --tonnage-factors")
     from .tonnage import add_options as _tonnage_options
     _tonnage_options(p)
+    from .bathymetry import add_options as _bathymetry_options
+    _bathymetry_options(p)
     opt = p.parse_args(argv)
+    if opt.bathymetry and not opt.geocode_bboxes:
+        p.error("--bathymetry takes the depth under geocoded facilities: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if opt.bathymetry and opt.tonnage is None and opt.facilities is None:
+        p.error("--bathymetry gives the facilities of --tonnage or --facilities their depth: it needs at least one of the two")
+    if opt.bathymetry and opt.tonnage_depths:
+        p.error("cage depths come from --bathymetry or from --tonnage-depths, not from both")
     if opt.tonnage is not None and not opt.geocode_bboxes:
         p.error("--tonnage estimates from geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if opt.tonnage is not None and not opt.tonnage_factors:
@@ -199,7 +207,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         blank_geom_simplify=0.5, facilities=None, facilities_conf=0.5, facilities_eps=10.0, facilities_min_cages=5, facilities_by="year",
         land_filter=None, ocean_out=None, evaluate=None, evaluate_out=None, evaluate_conf=None, evaluate_eps=None, evaluate_min_cages=None,
         evaluate_images=None, tonnage=None, tonnage_factors=None, tonnage_errors=None, tonnage_depths=None, tonnage_default_depth=4.84,
-        tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, log=print, **unsupported):
+        tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, bathymetry=None, bathymetry_statistic="bathy_min", log=print,
+        **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb, jpeg_slots_to_rgb, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     if blank_geom is not None and blank_key is None:     # the outlines are made for the images the key calls partly blank
@@ -214,6 +223,12 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         raise ValueError("--tonnage estimates from geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if tonnage is not None and not tonnage_factors:
         raise ValueError("--tonnage needs --tonnage-factors FILE (pass, s_mean, s_sd, h_mean, h_sd)")
+    if bathymetry and not geocode_bboxes:
+        raise ValueError("--bathymetry takes the depth under geocoded facilities: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if bathymetry and tonnage is None and facilities is None:
+        raise ValueError("--bathymetry gives the facilities of --tonnage or --facilities their depth: it needs at least one of the two")
+    if bathymetry and tonnage_depths:
+        raise ValueError("cage depths come from --bathymetry or from --tonnage-depths, not from both")
     for k in UNSUPPORTED:
         if unsupported.get(k):
             raise NotImplementedError(f"--{k.replace('_', '-')} is not part of the tile-sweep path (reference README.md:77)")
@@ -1004,6 +1019,15 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 ocean_path = ocean_out or str(save_dir / "ocean_detections.geojson")
                 n_ocean = aqland.write_ocean_geojson(ocean_path, table["stems"], table, ocean)
                 log(f"{n_ocean} of {ocean.shape[0]} detections at sea ({segs.shape[0]} land edges) in {ocean_path} in {time.perf_counter() - t_l:.2f}s")
+            bathy = None
+            if bathymetry:
+                # the depth raster under the cages (reference src/utils_tonnage.py:591-665), read once for both steps below
+                from . import bathymetry as aqbathy
+                t_b = time.perf_counter()
+                bathy = aqbathy.settings([bathymetry] if isinstance(bathymetry, str) else list(bathymetry), table, ocean, bathymetry_statistic,
+                                         tonnage_default_depth, tonnage_min_depth)
+                log(f"bathymetry: a window of {bathy['grid']['data'].shape[0]} x {bathy['grid']['data'].shape[1]} cells of "
+                    f"{', '.join(os.path.basename(f_) for f_ in bathy['grid']['files'])} in {time.perf_counter() - t_b:.2f}s")
             if facilities is not None:
                 # the steps after it (reference src/process_yolo/calc_net_areas.py, src/cluster_facilities.py).  An image this rank's sweep
                 # did not see (another rank's, or one a resumed run had finished) counts as the 1024-px tile the geocoding assumes anyway.
@@ -1012,7 +1036,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 hw = np.asarray([image_hw.get(str(s_), (geocode.IM_HEIGHT, geocode.IM_WIDTH)) for s_ in table["stems"]], np.int64).reshape(-1, 2)
                 fac_out = facilities or str(save_dir / "facilities.geojson")
                 fac = aqfac.facilities_from_table(table, fac_out, facilities_by, facilities_conf, facilities_eps, facilities_min_cages,
-                                                  hw[table["image"], 1], hw[table["image"], 0], keep=ocean)
+                                                  hw[table["image"], 1], hw[table["image"], 0], keep=ocean, bathymetry=bathy)
                 log(f"{len(fac['facility_index'])} facilities of {int((fac['_members'] >= 0).sum())} cages in {fac_out} "
                     f"in {time.perf_counter() - t_f:.2f}s")
             if evaluate is not None:
@@ -1033,7 +1057,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 ton_out = tonnage or str(save_dir)
                 est = aqton.tonnage_from_table(table, ton_out, tonnage_factors, tonnage_errors, tonnage_depths, tonnage_K, tonnage_seed, tonnage_mix,
                                                tonnage_min_depth, tonnage_default_depth, facilities_conf, facilities_eps, facilities_min_cages,
-                                               hw[table["image"], 1], hw[table["image"], 0], keep=ocean)
+                                               hw[table["image"], 1], hw[table["image"], 0], keep=ocean, bathymetry=bathy)
                 log(f"tonnage: {aqton.describe(est)} in {ton_out} in {time.perf_counter() - t_t:.2f}s")
     manifest.close()
     eng.close()

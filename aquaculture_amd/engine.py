@@ -80,6 +80,7 @@ EXPORTS = (
     "aq_land_scratch_bytes", "aq_land_filter_f64",
     "aq_eval_scratch_bytes", "aq_eval_member_conf_f64", "aq_box_match_f64",
     "aq_tonnage_simulate_f64", "aq_tonnage_reduce_f64", "aq_tonnage_ndtri_f64", "aq_tonnage_uniform_f64",
+    "aq_depth_ranges_f64", "aq_depth_stats_f64",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -153,6 +154,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_tonnage_reduce_f64.argtypes = [vp, C.c_longlong, C.c_longlong, vp, i32, vp, vp, vp]
     lib.aq_tonnage_ndtri_f64.argtypes = [vp, C.c_longlong, vp, vp]
     lib.aq_tonnage_uniform_f64.argtypes = [C.c_ulonglong, vp, C.c_longlong, vp, vp]
+    lib.aq_depth_ranges_f64.argtypes = [vp, C.c_longlong, vp, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp]
+    lib.aq_depth_stats_f64.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp, vp, vp, vp, vp, i32, i32, C.c_double, vp, C.c_longlong, vp, vp, vp]
     lib.aq_engine_set_tuned_table.argtypes = [vp, i32, i32, i32, C.POINTER(i32), i32]
     lib.aq_engine_calibrate_amax.argtypes = [vp, vp, i32, i32, i32, vp, sz, C.POINTER(f32), i32, vp]
     lib.aq_engine_set_fp8_scales.argtypes = [vp, C.POINTER(f32), i32]
@@ -1479,6 +1482,66 @@ def tonnage_uniform(seed: int, counters: torch.Tensor) -> torch.Tensor:
     out = torch.empty(n, dtype=torch.float64, device=counters.device)
     _check(load_library().aq_tonnage_uniform_f64(int(seed), counters.data_ptr() if n else None, n, out.data_ptr() if n else None, _stream_ptr()))
     return out
+
+
+# ---- --bathymetry: aq_depth_ranges_f64 / aq_depth_stats_f64 (the depth raster's cells under every facility's cages) ----
+
+def depth_word_starts(windows: np.ndarray) -> np.ndarray:
+    """int64 [F + 1]: the first bitmap word of every facility, (cells + 31) // 32 words each, from windows int32 [F, 4] (c0, c1, r0, r1)."""
+    w = np.asarray(windows, np.int64).reshape(-1, 4)
+    cells = np.maximum(w[:, 1] - w[:, 0] + 1, 0) * np.maximum(w[:, 3] - w[:, 2] + 1, 0)
+    return np.ascontiguousarray(np.concatenate([[0], np.cumsum((cells + 31) // 32)]), dtype=np.int64)
+
+
+def depth_stats(entry_start: torch.Tensor, cages: torch.Tensor, raster: torch.Tensor, x0: float, y0: float, dx: float, dy: float,
+                nodata: Optional[float] = None, times: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor, np.ndarray]:
+    """Both launches on the current stream: entry_start int32 CUDA [F + 1], cages float64 CUDA [E, 4] (lon_min, lon_max, lat_min, lat_max),
+    raster float32 CUDA [nrows, ncols] with its north-west corner (x0, y0) and cell size (dx, dy); nodata None: no value is nodata ->
+    (stats float64 CUDA [F, 3]: min, max, sum; count int64 CUDA [F]; windows int32 [F, 4] in host memory).  Between the launches the
+    windows come back to the host, which lays out the bitmap (depth_word_starts) -- the one synchronisation.  include/aq_engine.h states
+    the arithmetic; bathymetry.stats_numpy gives the same bytes.  times = a dict that receives "ranges_ms" and "stats_ms" (HIP events)
+    and "bitmap_words"."""
+    _require_gpu()
+    lib = load_library()
+    F, E = int(entry_start.shape[0]) - 1, int(cages.shape[0])
+    for t_, dt, nd in ((entry_start, torch.int32, 1), (cages, torch.float64, 2), (raster, torch.float32, 2)):
+        if not t_.is_cuda or t_.dtype != dt or t_.ndim != nd or not t_.is_contiguous():
+            raise ValueError(f"depth: a contiguous CUDA {dt} tensor of {nd} dimensions is needed, not {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+    if F < 0 or tuple(cages.shape) != (E, 4):
+        raise ValueError(f"depth: entry_start of shape {tuple(entry_start.shape)} and cages of shape {tuple(cages.shape)}")
+    nrows, ncols = int(raster.shape[0]), int(raster.shape[1])
+    dev = entry_start.device
+    ranges = torch.empty((E, 4), dtype=torch.int32, device=dev)
+    windows = torch.empty((F, 4), dtype=torch.int32, device=dev)
+    stats = torch.empty((F, 3), dtype=torch.float64, device=dev)
+    count = torch.empty((F,), dtype=torch.int64, device=dev)
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if times is not None else None
+    if ev:
+        ev[0].record()
+    _check(lib.aq_depth_ranges_f64(entry_start.data_ptr(), F, ptr(cages), E, float(x0), float(y0), float(dx), float(dy), nrows, ncols, ptr(ranges),
+                                   ptr(windows), _stream_ptr()))
+    if ev:
+        ev[1].record()
+    win_h = np.ascontiguousarray(windows.cpu().numpy())
+    start_h = depth_word_starts(win_h)
+    words = int(start_h[-1])
+    if words >= 1 << 31:
+        raise ValueError(f"depth: a bitmap of {words} words for {F} facilities (fewer than 2^31 in one call): pass fewer facilities at a time")
+    bitmap = torch.zeros(words, dtype=torch.int32, device=dev)
+    start_d = torch.from_numpy(start_h).to(dev)
+    if ev:
+        ev[2].record()
+    _check(lib.aq_depth_stats_f64(entry_start.data_ptr(), F, ptr(ranges), E, ptr(windows), win_h.ctypes.data, start_d.data_ptr(), start_h.ctypes.data,
+                                  ptr(raster), nrows, ncols, float("nan") if nodata is None else float(nodata), ptr(bitmap), words, ptr(stats),
+                                  ptr(count), _stream_ptr()))
+    if ev:
+        ev[3].record()
+        ev[3].synchronize()
+        times.update(ranges_ms=ev[0].elapsed_time(ev[1]), stats_ms=ev[2].elapsed_time(ev[3]), bitmap_words=words)
+    for t_ in (entry_start, cages, raster, ranges, windows, start_d, bitmap, stats, count):
+        t_.record_stream(torch.cuda.current_stream())
+    return stats, count, win_h
 
 
 # ---- --land-filter: aq_land_filter_f64 (detection boxes against the segments of the land polygons) ----

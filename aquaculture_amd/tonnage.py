@@ -461,12 +461,24 @@ def write_files(out_dir: str, est: dict, params: dict) -> None:
 def tonnage_from_table(table, out_dir: str, factors_path: str, errors_path: Optional[str] = None, depths_path: Optional[str] = None,
                        K: int = 10000, seed: int = 0, mix: float = 0.5, min_depth: float = DEFAULT_MIN_DEPTH, default_depth: float = DEFAULT_DEPTH,
                        conf_thresh: float = 0.5, eps: float = 10.0, min_cages: int = 5, widths=geocode.IM_WIDTH, heights=geocode.IM_HEIGHT,
-                       cpu: bool = False, keep=None) -> dict:
-    """Facilities per image pass (facilities.cluster), their estimates and the three files in `out_dir`."""
+                       cpu: bool = False, keep=None, bathymetry: Optional[dict] = None) -> dict:
+    """Facilities per image pass (facilities.cluster), their estimates and the three files in `out_dir`.  bathymetry (bathymetry.settings'
+    result, instead of a depths file): the facilities' cage depths come from the depth raster and are written to facility_depths.csv
+    beside the three files, in the form `depths_path` takes."""
+    if bathymetry is not None and depths_path:
+        raise ValueError("tonnage: cage depths come from --bathymetry or from --tonnage-depths, not from both")
     factors = read_factors(factors_path)
     errors = read_errors(errors_path) if errors_path else None
     depths = read_depths(depths_path) if depths_path else None
     fac = aqfac.cluster(table, "pass", conf_thresh, eps, min_cages, widths, heights, labels_fn=aqfac.dbscan_numpy if cpu else None, keep=keep)
+    extra = {}
+    if bathymetry is not None:
+        from . import bathymetry as aqbathy
+        cols = aqbathy.depths_of(fac, table, dict(bathymetry, default_depth=float(default_depth), min_depth=float(min_depth)), cpu=cpu)
+        depths = {int(fi): float(d) for fi, d in zip(fac["facility_index"], cols["cage_depth"])}
+        os.makedirs(out_dir, exist_ok=True)
+        missing = aqbathy.write_depths_csv(os.path.join(out_dir, aqbathy.DEPTHS_FILE), fac, cols, "pass")
+        extra = {"bathymetry": {**aqbathy.describe_settings(bathymetry), "default_depth_facilities": missing}}
     est = estimate(fac, None, table, factors, errors, depths, K, seed, mix, min_depth, cpu, default_depth)
     device = "cpu"
     if not cpu:
@@ -475,7 +487,7 @@ def tonnage_from_table(table, out_dir: str, factors_path: str, errors_path: Opti
     write_files(out_dir, est, {"device": device, "cpu": bool(cpu), "mix": float(mix), "min_depth": float(min_depth), "default_depth": float(default_depth),
                                "factors": {p: list(v) for p, v in sorted(factors.items())},
                                "errors": [[*k, *v] for k, v in sorted((errors or {}).items())], "depths_file": bool(depths_path),
-                               "facilities_conf": float(conf_thresh), "facilities_eps": float(eps), "facilities_min_cages": int(min_cages)})
+                               "facilities_conf": float(conf_thresh), "facilities_eps": float(eps), "facilities_min_cages": int(min_cages), **extra})
     return est
 
 
@@ -508,9 +520,13 @@ def main(argv: Optional[List[str]] = None) -> int:
     p.add_argument("--cpu", action="store_true", help="the numpy restatement instead of the GPU (the same bytes)")
     aqfac.add_options(p)
     add_options(p)
+    from . import bathymetry as aqbathy
+    aqbathy.add_options(p)
     opt = p.parse_args(argv)
     if not opt.tonnage_factors:
         p.error("--tonnage-factors FILE is needed")
+    if opt.bathymetry and opt.tonnage_depths:
+        p.error("cage depths come from --bathymetry or from --tonnage-depths, not from both")
     out = opt.out or os.path.dirname(os.path.abspath(opt.labels.rstrip("/")))
     table = geocode.geocode_label_dir(opt.labels, opt.geocode_bboxes)
     keep = None
@@ -518,9 +534,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         from . import land as aqland
         segs = aqland.load_land_geojson(opt.land)
         keep = aqland.ocean_rows(table, segs, cpu=opt.cpu)
+    bathy = aqbathy.settings(opt.bathymetry, table, keep, opt.bathymetry_statistic) if opt.bathymetry else None
     est = tonnage_from_table(table, out, opt.tonnage_factors, opt.tonnage_errors, opt.tonnage_depths, opt.tonnage_K, opt.tonnage_seed, opt.tonnage_mix,
                              opt.tonnage_min_depth, opt.tonnage_default_depth, opt.facilities_conf, opt.facilities_eps, opt.facilities_min_cages,
-                             opt.image_size[0], opt.image_size[1], cpu=opt.cpu, keep=keep)
+                             opt.image_size[0], opt.image_size[1], cpu=opt.cpu, keep=keep, bathymetry=bathy)
     print(f"{describe(est)} in {out}")
     return 0
 

@@ -716,6 +716,38 @@ int aq_tonnage_reduce_f64(const double* ton_dev, long long K_chunk, long long F,
 int aq_tonnage_ndtri_f64(const double* p_dev, long long n, double* out_dev, void* stream);
 int aq_tonnage_uniform_f64(unsigned long long seed, const uint32_t* counters_dev, long long n, double* out_dev, void* stream);
 
+/* ---- --bathymetry (depth.hip): min, max, sum and count of the depth raster's cells under every facility (reference
+ * src/utils_tonnage.py:591-665, add_facility_depth: rasterstats.zonal_stats(all_touched=True) over the union of a facility's circle and square
+ * cages).  raster_dev: float32 [nrows][ncols], row 0 the northernmost; cell (r, c) is the half-open square [x0 + c dx, x0 + (c + 1) dx) x
+ * (y0 - (r + 1) dy, y0 - r dy].  Facility f owns the cages entry_start[f] .. entry_start[f + 1] - 1 of cages_dev [E][4] (lon_min, lon_max,
+ * lat_min, lat_max; 32-byte aligned).  Only fp64 - / floor, comparisons and selections decide a cell, only fp64 + in one written order makes
+ * the sum, so aquaculture_amd.bathymetry.stats_numpy gives the same bytes.
+ * aq_depth_ranges_f64: c0 = floor((lon_min - x0) / dx), c1 = floor((lon_max - x0) / dx), r0 = floor((y0 - lat_max) / dy), r1 = floor((y0 -
+ * lat_min) / dy), each kept inside [-1, ncols] / [-1, nrows] in fp64 before the conversion (what is not >= -1, NaN included, gives -1); the cage
+ * touches columns c0 .. c1 and rows r0 .. r1 intersected with the raster's: cage_range_dev [E][4] int32 (c0, c1, r0, r1; 16-byte aligned),
+ * (0, -1, 0, -1) for a cage without a cell or with a NaN coordinate.  window_dev [F][4] (16-byte aligned) = the bounding rectangle of the facility's cage ranges,
+ * (0, -1, 0, -1) without any.  On `stream`, one launch, one wavefront per facility, no atomics.  F = 0 does nothing.  F or E >= 2^31, a negative
+ * nrows or ncols, dx or dy not positive and finite, an origin that is not finite, a null pointer and an unaligned array are refused before
+ * anything is launched; entry ranges are kept inside [0, E] on the device. */
+int aq_depth_ranges_f64(const int32_t* entry_start_dev, long long F, const double* cages_dev, long long E, double x0, double y0, double dx,
+                        double dy, int nrows, int ncols, int32_t* cage_range_dev, int32_t* window_dev, void* stream);
+/* aq_depth_stats_f64: the facility's touched cells are the union of its cages' ranges, kept as bits of its own words of bitmap_dev
+ * [bitmap_words] uint32, which the caller zeroed: with W the window's width, bit i (word i / 32, bit i % 32, from the facility's first word
+ * word_start[f]) is cell (i / W, i % W) of the window, so facility f needs (cells + 31) / 32 words.  The bits are set with integer atomicOr.
+ * Valid cells: touched, not NaN, not equal to nodata (a NaN nodata excludes nothing).  stats_dev [F][3] = min, max (the float32 values
+ * widened; a zero is +0.0) and sum; count_dev [F] int64.  The sum: partial l = 0 .. 63 starts at +0.0 and adds the valid cells with
+ * i % 64 == l in ascending i; the partials are added in order of l from +0.0.  No valid cell: +inf, -inf, +0.0, 0.
+ * window_host and word_start_host = the content of window_dev and word_start_dev in host memory, checked there.  Refused before anything is
+ * launched: F or E >= 2^31, bitmap_words >= 2^31, a window of 2^31 cells or more or one that leaves the raster, a facility with fewer words
+ * than its window needs, word starts that decrease or leave [0, bitmap_words], a null pointer, an unaligned array.  On the device the
+ * windows are kept inside the raster, the cage ranges inside the window, the entries inside [0, E], and a window that does not fit its
+ * words counts as empty: tables the caller got wrong give wrong numbers but no access outside the arrays.  On `stream`, one launch, one
+ * wavefront per facility, no floating-point atomics: the same bytes on every call.  F = 0 does nothing. */
+int aq_depth_stats_f64(const int32_t* entry_start_dev, long long F, const int32_t* cage_range_dev, long long E, const int32_t* window_dev,
+                       const int32_t* window_host, const long long* word_start_dev, const long long* word_start_host, const float* raster_dev,
+                       int nrows, int ncols, double nodata, uint32_t* bitmap_dev, long long bitmap_words, double* stats_dev,
+                       long long* count_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
