@@ -11,7 +11,8 @@ per image).  EOF on stdin ends the worker.
 
 Mode `coef` (round 3, the split decode): the worker undoes only the Huffman coding (libaqjpeg.so through aquaculture_amd/jpeg.py) and
 writes the image's quantised DCT coefficient blocks and quantisation tables into its slot of a byte ring [n_slots][jpeg.slot_bytes(H, W)];
-the GPU does the rest (aq_jpeg_idct_rgb), byte-identical to this process's PIL decode.  The parent only selects this mode for file sets
+the GPU does the rest (aq_jpeg_idct_rgb_checked), byte-identical to this process's PIL decode for images inside its acceptance rule (the
+parent refuses the others).  The parent only selects this mode for file sets
 whose headers say baseline 4:2:0 throughout; a file that still fails here is an error, as a PIL failure is.
 """
 import sys

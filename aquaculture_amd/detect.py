@@ -98,7 +98,10 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "(cached in $AQ_TUNE_CACHE or ~/.cache/aquaculture_amd/); auto = only for sweeps of >= 8 batches per GPU")
     p.add_argument("--jpeg-decode", choices=("auto", "host", "split", "gpu"), default="auto",
                    help="split: the decode workers undo only the Huffman coding, the GPU does the inverse DCT, chroma upsampling and colour "
-                        "conversion (byte-identical to libjpeg-turbo; baseline 4:2:0 JPEGs, which is what the reference's tiler writes); "
+                        "conversion (byte-identical to libjpeg-turbo for every image inside the decoder's acceptance rule -- each block's IDCT "
+                        "workspace within +-16383, three times what an encoder produces from 8-bit pixels; a file outside it, e.g. one with a "
+                        "damaged quantisation table, ends the run with an error that names it; baseline 4:2:0 JPEGs, which is what the "
+                        "reference's tiler writes); "
                         "host: full software decode in the workers; "
                         "gpu: the Huffman stage on the GPU as well (one lane per image, super-batches of AQ_JPEG_GPU_SUPERBATCH = 2048 tiles in "
                         "flight): the host only reads the files and strips byte stuffing, H2D carries the files' entropy-coded bytes; "
@@ -209,7 +212,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         evaluate_images=None, tonnage=None, tonnage_factors=None, tonnage_errors=None, tonnage_depths=None, tonnage_default_depth=4.84,
         tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, bathymetry=None, bathymetry_statistic="bathy_min", log=print,
         **unsupported):
-    from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb, jpeg_slots_to_rgb, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
+    from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb_checked, jpeg_slots_to_rgb, JPEG_WS_MAX, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     if blank_geom is not None and blank_key is None:     # the outlines are made for the images the key calls partly blank
         blank_key = ""
@@ -367,9 +370,14 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 item = q.get()
                 if item is None:
                     return
-                ev, counts_h, dets_h, paths, shapes0, hw, gidx, t_inf, slot_id, crop_src, blank_h = item
+                ev, counts_h, dets_h, paths, shapes0, hw, gidx, t_inf, slot_id, crop_src, blank_h, jflags_h = item
                 item = None
                 ev.synchronize()
+                if jflags_h is not None and jflags_h.numpy().any():     # before anything of this batch is written or recorded
+                    bad = [p for p, f in zip(paths, jflags_h.numpy().tolist()) if f]
+                    raise ValueError(f"{bad[0]}: outside the acceptance rule of the GPU JPEG decode: a block's pass-1 IDCT workspace exceeds +-{JPEG_WS_MAX} "
+                                     f"(dequantised coefficients no encoder produces from 8-bit pixels: a damaged quantisation table?), where libjpeg's own "
+                                     f"pixels depend on its build{f'; {len(bad) - 1} more in the same batch' if len(bad) > 1 else ''}.  Use --jpeg-decode host.")
                 t0 = time.perf_counter()
                 nlab = ndet = 0
                 released = False
@@ -825,6 +833,12 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
     t_steady, n_steady, n_fed = [None], [0], [0]
     all_split = [False]
     jpeg_scratch = [None] * depth
+    jpeg_flags = [None] * depth                            # per slot: the pixel half's acceptance flags, on the device and pinned
+
+    def jpeg_flag_slot(slot):
+        if jpeg_flags[slot] is None:
+            jpeg_flags[slot] = (torch.empty(batch_size, dtype=torch.int32, device=dev), torch.empty(batch_size, dtype=torch.int32).pin_memory())
+        return jpeg_flags[slot]
     source_iter = scene_source() if tile_scenes else image_source()
     scene_dev, scene_path, scene_ev = None, None, None
     # Autotune on the first full batch (rank 0 times, every rank installs the same table: identical kernels on all GPUs of a run).
@@ -848,7 +862,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             if diag is not None:
                 diag["slot_wait"] += time.perf_counter() - t0
             st = streams[slot]
-            crop_src = None
+            crop_src = jflags = jflags_h = None
             with torch.cuda.stream(st):
                 if isinstance(host, tuple) and host[0] == "scene":      # scene mode: one upload per scene, tiles cut by the letterbox kernel
                     _, spath, sarr, origins, thw = host
@@ -870,7 +884,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     if jpeg_scratch[slot] is None:
                         jpeg_scratch[slot] = torch.empty(eng.lib.aq_jpeg_scratch_bytes(batch_size, h0_, w0_), dtype=torch.uint8, device=dev)
                     off_ = torch.arange(qt_v.shape[0], dtype=torch.int64, device=dev) * nco_
-                    tiles = jpeg_idct_rgb(coef_v, off_, qt_v, h0_, w0_, scratch=jpeg_scratch[slot])
+                    tiles, jflags = jpeg_idct_rgb_checked(coef_v, off_, qt_v, h0_, w0_, scratch=jpeg_scratch[slot], flags=jpeg_flag_slot(slot)[0])
                     used_ev = torch.cuda.Event()
                     used_ev.record(st)
                     hook(used_ev)                          # the super-batch's buffer is free for its next decode once this batch has read it
@@ -886,7 +900,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                         h0_, w0_ = shapes0[0]
                         if jpeg_scratch[slot] is None:
                             jpeg_scratch[slot] = torch.empty(eng.lib.aq_jpeg_scratch_bytes(batch_size, h0_, w0_), dtype=torch.uint8, device=tiles.device)
-                        tiles = jpeg_slots_to_rgb(tiles, h0_, w0_, scratch=jpeg_scratch[slot])
+                        tiles, jflags = jpeg_slots_to_rgb(tiles, h0_, w0_, scratch=jpeg_scratch[slot], flags=jpeg_flag_slot(slot)[0])
                     crop_src = original_images(tiles)
                     tiles = letterbox_device(tiles, tuple(imgsz), int(max(ck.stride)), True)
                 blank_h = blank_batch(crop_src, shapes0, slot) if blank_key is not None else None
@@ -918,12 +932,15 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 counts_h, dets_h = pinned[slot][0][:B], pinned[slot][1][:B]
                 counts_h.copy_(counts, non_blocking=True)
                 dets_h.copy_(dets, non_blocking=True)
+                if jflags is not None:                     # the acceptance flags of the JPEG pixel half travel with the results the writer waits for
+                    jflags_h = jpeg_flag_slot(slot)[1][:B]
+                    jflags_h.copy_(jflags, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(st)
             H, W = int(tiles.shape[1]), int(tiles.shape[2])
             shape_str = f"(1, 3, {H}, {W})"
             t2 = time.perf_counter()
-            q.put((ev, counts_h, dets_h, paths, shapes0, (H, W), list(gidx), t2 - t1, slot, crop_src, blank_h))
+            q.put((ev, counts_h, dets_h, paths, shapes0, (H, W), list(gidx), t2 - t1, slot, crop_src, blank_h, jflags_h))
             crop_src = None
             if diag is not None:
                 diag["put"] += time.perf_counter() - t2

@@ -70,7 +70,7 @@ EXPORTS = (
     "aq_engine_get_conv_config", "aq_conv_num_configs", "aq_debug_conv_stamp", "aq_debug_mfma_peak",
     "aq_conv_config_tiles", "aq_pack_conv_weights", "aq_pack_conv_weights_x3", "aq_conv2d", "aq_pack_stem_weights", "aq_stem_conv", "aq_pack_bottleneck_weights", "aq_bottleneck", "aq_bottleneck_asm_form", "aq_bottleneck_c3tail_supported", "aq_pack_bottleneck_c3tail_weights", "aq_bottleneck_c3tail", "aq_pack_downblock_weights", "aq_downblock", "aq_stemdown_supported", "aq_stemdown", "aq_conv1x1_direct_supported", "aq_pack_conv1x1_direct", "aq_conv1x1_direct", "aq_conv1x1_asm_supported", "aq_pack_conv1x1_asm", "aq_conv1x1_asm", "aq_nms_opts", "aq_engine_set_nms_options",
     "aq_conv3x3s2_direct_supported", "aq_pack_conv3x3s2_direct", "aq_conv3x3s2_direct",
-    "aq_conv3x3_pl_supported", "aq_conv3x3_pl_asm_family", "aq_pack_conv3x3_pl", "aq_conv3x3_pl", "aq_conv3x3_pl_s2_supported", "aq_pack_conv3x3_pl_s2", "aq_conv3x3_pl_s2", "aq_jpeg_scratch_bytes", "aq_jpeg_idct_rgb", "aq_f32_to_e4m3", "aq_conv1x1_direct_f8out", "aq_absmax_bf16", "aq_engine_calibrate_amax", "aq_engine_set_fp8_scales", "aq_engine_last_launch", "aq_conv3x3_pl_f8_supported", "aq_pack_conv3x3_pl_f8", "aq_conv3x3_pl_f8", "aq_conv3x3_pl_w8_supported", "aq_pack_conv3x3_pl_w8", "aq_conv3x3_pl_w8", "aq_head_decode_supported", "aq_pack_head_weights", "aq_head_decode", "aq_head_counts_gather", "aq_preprocess_s2d", "aq_sppf_pool",
+    "aq_conv3x3_pl_supported", "aq_conv3x3_pl_asm_family", "aq_pack_conv3x3_pl", "aq_conv3x3_pl", "aq_conv3x3_pl_s2_supported", "aq_pack_conv3x3_pl_s2", "aq_conv3x3_pl_s2", "aq_jpeg_scratch_bytes", "aq_jpeg_idct_rgb", "aq_jpeg_idct_rgb_checked", "aq_f32_to_e4m3", "aq_conv1x1_direct_f8out", "aq_absmax_bf16", "aq_engine_calibrate_amax", "aq_engine_set_fp8_scales", "aq_engine_last_launch", "aq_conv3x3_pl_f8_supported", "aq_pack_conv3x3_pl_f8", "aq_conv3x3_pl_f8", "aq_conv3x3_pl_w8_supported", "aq_pack_conv3x3_pl_w8", "aq_conv3x3_pl_w8", "aq_head_decode_supported", "aq_pack_head_weights", "aq_head_decode", "aq_head_counts_gather", "aq_preprocess_s2d", "aq_sppf_pool",
     "aq_upsample2x", "aq_letterbox_u8", "aq_letterbox_tiles_u8", "aq_format_label_rows", "aq_detect_decode", "aq_nms_scratch_bytes", "aq_nms", "aq_jpeg_huffman_decode", "aq_write_label_files",
     "aq_crop_jpeg_coefs", "aq_crop_jpeg_bytes", "aq_write_crop_files",
     "aq_annotate_u8", "aq_image_jpeg_coefs", "aq_image_jpeg_bytes", "aq_write_image_files",
@@ -199,6 +199,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_jpeg_scratch_bytes.argtypes = [i32, i32, i32]
     lib.aq_jpeg_scratch_bytes.restype = sz
     lib.aq_jpeg_idct_rgb.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.aq_jpeg_idct_rgb_checked.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     lib.aq_f32_to_e4m3.argtypes = [f32]
     lib.aq_f32_to_e4m3.restype = C.c_ubyte
     lib.aq_conv3x3_pl_f8_supported.argtypes = [i32] * 5
@@ -1917,10 +1918,15 @@ def conv3x3_pl_f8_nhwc(xq: torch.Tensor, act_scale: float, w_oihw: torch.Tensor,
     return out
 
 
-def jpeg_idct_rgb(coef: torch.Tensor, coef_off: torch.Tensor, qt: torch.Tensor, H: int, W: int, out: Optional[torch.Tensor] = None,
-                  scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The device half of the split JPEG decode (aq_jpeg_idct_rgb): coef int16 CUDA (the images' coefficient blocks), coef_off int64 [B]
-    (first value of each image, multiples of 64), qt uint16 [B,3,64]  ->  uint8 RGB [B,H,W,3], the pixels libjpeg(-turbo) produces."""
+JPEG_WS_MAX = 16383     # AQ_JPEG_WS_MAX (include/aq_engine.h): the acceptance rule of the device half of the JPEG decode
+
+
+def jpeg_idct_rgb_checked(coef: torch.Tensor, coef_off: torch.Tensor, qt: torch.Tensor, H: int, W: int, out: Optional[torch.Tensor] = None,
+                          scratch: Optional[torch.Tensor] = None, flags: Optional[torch.Tensor] = None):
+    """The device half of the split JPEG decode (aq_jpeg_idct_rgb_checked): coef int16 CUDA (the images' coefficient blocks), coef_off int64
+    [B] (first value of each image, multiples of 64), qt uint16 [B,3,64]  ->  (uint8 RGB [B,H,W,3], flags int32 CUDA [B]).  Image b's pixels
+    are the ones libjpeg(-turbo) produces iff flags[b] == 0: a flag of 1 says that one of its blocks is outside the acceptance rule
+    (a pass-1 IDCT workspace value beyond +-JPEG_WS_MAX), where the library's own pixels are not defined; the caller refuses the file."""
     _require_gpu()
     lib = load_library()
     B = int(coef_off.shape[0])
@@ -1930,8 +1936,19 @@ def jpeg_idct_rgb(coef: torch.Tensor, coef_off: torch.Tensor, qt: torch.Tensor, 
     n = lib.aq_jpeg_scratch_bytes(B, H, W)
     if scratch is None or scratch.numel() < n:
         scratch = torch.empty(n, dtype=torch.uint8, device=coef.device)
-    _check(lib.aq_jpeg_idct_rgb(coef.data_ptr(), coef_off.data_ptr(), qt.data_ptr(), B, H, W, scratch.data_ptr(), out.data_ptr(), _stream_ptr()))
-    return out
+    if flags is None:
+        flags = torch.empty(B, dtype=torch.int32, device=coef.device)
+    assert flags.is_cuda and flags.dtype == torch.int32 and flags.is_contiguous() and flags.numel() >= B
+    _check(lib.aq_jpeg_idct_rgb_checked(coef.data_ptr(), coef_off.data_ptr(), qt.data_ptr(), B, H, W, scratch.data_ptr(), out.data_ptr(),
+                                        flags.data_ptr(), _stream_ptr()))
+    return out, flags[:B]
+
+
+def jpeg_idct_rgb(coef: torch.Tensor, coef_off: torch.Tensor, qt: torch.Tensor, H: int, W: int, out: Optional[torch.Tensor] = None,
+                  scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """jpeg_idct_rgb_checked without its flags: the pixels libjpeg(-turbo) produces for images inside the acceptance rule, and no word
+    about the others.  For callers that know their files (tests, tools); detect.py uses the checked call."""
+    return jpeg_idct_rgb_checked(coef, coef_off, qt, H, W, out=out, scratch=scratch)[0]
 
 
 def jpeg_huffman_decode(streams: torch.Tensor, segs: torch.Tensor, tabsets: torch.Tensor, coef: torch.Tensor, status: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1949,16 +1966,17 @@ def jpeg_huffman_decode(streams: torch.Tensor, segs: torch.Tensor, tabsets: torc
     return status
 
 
-def jpeg_slots_to_rgb(slots: torch.Tensor, H: int, W: int, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+def jpeg_slots_to_rgb(slots: torch.Tensor, H: int, W: int, scratch: Optional[torch.Tensor] = None, flags: Optional[torch.Tensor] = None):
     """A batch as the decode workers' coefficient mode delivers it -- uint8 CUDA [b, jpeg.slot_bytes(H, W)]: per image the int16 coefficient
-    blocks, then three uint16 quantisation tables -- to RGB tiles uint8 [b, H, W, 3] on the device."""
+    blocks, then three uint16 quantisation tables -- to (RGB tiles uint8 [b, H, W, 3], flags int32 [b]) on the device, as
+    jpeg_idct_rgb_checked returns them."""
     from . import jpeg
     assert slots.is_cuda and slots.dtype == torch.uint8 and slots.dim() == 2 and slots.is_contiguous() and slots.shape[1] == jpeg.slot_bytes(H, W)
     b = slots.shape[0]
     nco = jpeg.coef_count(H, W)
     qt = slots[:, 2 * nco:2 * nco + 384].contiguous().view(torch.int16)
     off = torch.arange(b, dtype=torch.int64, device=slots.device) * (slots.shape[1] // 2)
-    return jpeg_idct_rgb(slots.view(torch.int16).reshape(-1), off, qt, H, W, scratch=scratch)
+    return jpeg_idct_rgb_checked(slots.view(torch.int16).reshape(-1), off, qt, H, W, scratch=scratch, flags=flags)
 
 
 def _head_level_buffers(x: torch.Tensor, w_oi: torch.Tensor, bias: torch.Tensor, anchors_px, nc: int, cap: int, count_stride: int,

@@ -378,8 +378,20 @@ int aq_letterbox_tiles_u8(const uint8_t* scene_dev, long long scene_bytes, long 
  * libjpeg(-turbo) -- dequantisation, the islow IDCT, h2v2 fancy chroma upsampling, YCbCr -> RGB -- bit for bit, on the device.  Input: the
  * quantised coefficient blocks of B baseline 4:2:0 JPEGs of one size as written by aq_jpeg_decode_coeffs (libaqjpeg.so, include/aq_jpeg.h:
  * the entropy decoder, which stays on the host), image b from coef_off_dev[b] (int16 units, a multiple of 64), qt_dev uint16 [B][3][64].
- * Output: uint8 RGB [B][H][W][3].  scratch_dev: aq_jpeg_scratch_bytes(B, H, W) bytes. */
+ * Output: uint8 RGB [B][H][W][3].  scratch_dev: aq_jpeg_scratch_bytes(B, H, W) bytes.
+ * THE ACCEPTANCE RULE: "bit for bit" holds for images all of whose blocks keep every value of the IDCT's pass-1 workspace (the column pass,
+ * DESCALEd by 11 bits) within +-AQ_JPEG_WS_MAX -- the rule of oracle/jpeg_oracle.py (WS_MAX; tests/test_jpeg_synth.py ties the two
+ * constants and pins the rule to libjpeg-turbo).  Beyond it the library's pixels depend on its build.  aq_jpeg_idct_rgb_checked zeroes
+ * flags_dev (int32 [B]) on the stream and sets image b's flag to 1 when one of its blocks is outside the rule; the image's pixels are
+ * written all the same and are nobody's.  aq_jpeg_idct_rgb is the checked entry without flags: its pixels are libjpeg's only for
+ * accepted blocks, and it cannot say when they are not. */
+#define AQ_JPEG_WS_MAX 16383
+/* Inside the rule every dequantised coefficient satisfies |coef q| < 4096 (the column pass is invertible with known gains).  The kernel
+ * refuses a block beyond this bound BEFORE it looks at its 32-bit workspace, which a larger value can wrap back into range. */
+#define AQ_JPEG_DEQ_MAX 4096
 size_t aq_jpeg_scratch_bytes(int B, int H, int W);
+int aq_jpeg_idct_rgb_checked(const int16_t* coef_dev, const long long* coef_off_dev, const uint16_t* qt_dev, int B, int H, int W,
+                             void* scratch_dev, uint8_t* out_dev, int32_t* flags_dev, void* stream);
 int aq_jpeg_idct_rgb(const int16_t* coef_dev, const long long* coef_off_dev, const uint16_t* qt_dev, int B, int H, int W,
                      void* scratch_dev, uint8_t* out_dev, void* stream);
 /* GPU entropy decode (round 4): the Huffman stage of the same decode on the device, one lane per restart segment (= per image for files
