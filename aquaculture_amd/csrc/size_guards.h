@@ -104,4 +104,12 @@ inline bool igemm_fits(ll npix, ll kgroups_pad, ll G, ll cout, ll bm, ll bn) {
 // ---- head_decode.hip ----  (ny x nx: the level's grid)
 inline bool head_decode_fits(ll B, ll ny, ll nx) { return B * ny * nx < (1LL << 30); }
 
+// ---- dedup.hip ----  (every count of a call -- ring vertices, rings, bitmap words, groups, cages -- is a 31-bit index; these three have no
+// line in oracle/guards.py: tests/test_gpu_dedup.py walks their edges through the launchers' refusals)
+constexpr ll kDedupMaxSlots = 5, kDedupMaxPerms = 120;      // images of one (pass, tile key) group: the longest image pass; 5! orders
+constexpr ll kDedupMaxSide = 1LL << 15;                     // frame width and height
+inline bool dedup_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }
+inline bool dedup_frame_fits(ll w, ll h) { return w >= 1 && h >= 1 && w <= kDedupMaxSide && h <= kDedupMaxSide; }
+constexpr ll dedup_pitch(ll w) { return cdiv(w + 1, 32); }  // words of a bitmap row: w pixels and the column x = w of the toggles
+
 }  // namespace sg

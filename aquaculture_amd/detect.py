@@ -156,7 +156,21 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
     _tonnage_options(p)
     from .bathymetry import add_options as _bathymetry_options
     _bathymetry_options(p)
+    p.add_argument("--dedup-years", nargs="?", const="", default=None, metavar="DIR",
+                   help="after the sweep, its geocoding and the land filter, keep one year's cages per tile and image pass (the reference's "
+                        "dedup_cages_in_overlap_years_with_white_space, src/utils_tonnage.py:668-911: the years of a pass that cover the same tile "
+                        "share its area in some order, each keeping its non-blank polygon minus the years before it), the pixel masks, the cages' "
+                        "windows and the n! orders on the GPU; writes dedup_cages.csv, dedup_tiles.csv and dedup.json (default <save_dir>), and "
+                        "--facilities (by pass), --bathymetry and --tonnage see the survivors only; needs --geocode-bboxes, implies --blank-geom")
+    from .dedup import add_options as _dedup_options
+    _dedup_options(p)
     opt = p.parse_args(argv)
+    if opt.dedup_years is not None and not opt.geocode_bboxes:
+        p.error(DEDUP_NEEDS_GEOCODE)
+    if opt.dedup_years is not None and opt.facilities is not None and opt.facilities_by != "pass":
+        p.error(DEDUP_BY_PASS)
+    if opt.dedup_years is not None and opt.blank_geom is None:
+        opt.blank_geom = ""
     if opt.bathymetry and not opt.geocode_bboxes:
         p.error("--bathymetry takes the depth under geocoded facilities: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if opt.bathymetry and opt.tonnage is None and opt.facilities is None:
@@ -185,6 +199,10 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
     return opt
 
 
+DEDUP_NEEDS_GEOCODE = "--dedup-years works on geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)"
+DEDUP_BY_PASS = "--dedup-years keeps one year per tile and image pass: with it --facilities needs --facilities-by pass, not year"
+
+
 def run_params(weights_id, conf_thres, iou_thres, max_det, imgsz, precision, save_conf, classes=None, agnostic_nms=False, augment=False,
                save_crop=False, save_img=None, blank_key=False, blank_geom=False) -> dict:
     """What the label bytes depend on (run_params.json; --resume refuses a directory written with anything else).  The optional settings are
@@ -210,10 +228,18 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         blank_geom_simplify=0.5, facilities=None, facilities_conf=0.5, facilities_eps=10.0, facilities_min_cages=5, facilities_by="year",
         land_filter=None, ocean_out=None, evaluate=None, evaluate_out=None, evaluate_conf=None, evaluate_eps=None, evaluate_min_cages=None,
         evaluate_images=None, tonnage=None, tonnage_factors=None, tonnage_errors=None, tonnage_depths=None, tonnage_default_depth=4.84,
-        tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, bathymetry=None, bathymetry_statistic="bathy_min", log=print,
-        **unsupported):
+        tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, bathymetry=None, bathymetry_statistic="bathy_min", dedup_years=None,
+        dedup_selection="random", dedup_seed=0, log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb_checked, jpeg_slots_to_rgb, JPEG_WS_MAX, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
+    if dedup_years is not None and not geocode_bboxes:
+        raise ValueError(DEDUP_NEEDS_GEOCODE)
+    if dedup_years is not None and facilities is not None and facilities_by != "pass":
+        raise ValueError(DEDUP_BY_PASS)
+    if dedup_years is not None and dedup_selection not in ("random", "min", "max"):
+        raise ValueError(f"--dedup-selection {dedup_selection!r}: random, min or max")
+    if dedup_years is not None and blank_geom is None:   # the masks of the partly blank images are their outlines
+        blank_geom = ""
     if blank_geom is not None and blank_key is None:     # the outlines are made for the images the key calls partly blank
         blank_key = ""
     if facilities is not None and not geocode_bboxes:
@@ -465,7 +491,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     with manifest_lock:
                         manifest.add(Path(p).stem for p in paths)
                 with lock:
-                    if facilities is not None or tonnage is not None:       # the circle areas' border test wants every image's own size
+                    if facilities is not None or tonnage is not None or dedup_years is not None:       # the circle areas' border test wants every image's own size
                         image_hw.update((Path(p).stem, (int(sh[0]), int(sh[1]))) for p, sh in zip(paths, shapes0))
                     stats["seen"] += len(paths)
                     stats["labels"] += nlab
@@ -1036,6 +1062,21 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 ocean_path = ocean_out or str(save_dir / "ocean_detections.geojson")
                 n_ocean = aqland.write_ocean_geojson(ocean_path, table["stems"], table, ocean)
                 log(f"{n_ocean} of {ocean.shape[0]} detections at sea ({segs.shape[0]} land edges) in {ocean_path} in {time.perf_counter() - t_l:.2f}s")
+            dd = None
+            hw = None
+            if facilities is not None or tonnage is not None or dedup_years is not None:
+                # An image this rank's sweep did not see (another rank's, or one a resumed run had finished) counts as the 1024-px tile the
+                # geocoding assumes anyway.
+                hw = np.asarray([image_hw.get(str(s_), (geocode.IM_HEIGHT, geocode.IM_WIDTH)) for s_ in table["stems"]], np.int64).reshape(-1, 2)
+            if dedup_years is not None:
+                # the step before every clustering by pass (reference src/utils_tonnage.py:668-911, :979-995), on the key and the outlines
+                # this sweep has just written; detections.geojson stays as it is and cage_ids stay its row numbers
+                from . import dedup as aqdedup
+                t_d = time.perf_counter()
+                dd_out = dedup_years or str(save_dir)
+                dd = aqdedup.dedup_from_table(table, key_out, geom_out, dd_out, dedup_selection, dedup_seed, facilities_conf, ocean,
+                                              hw[table["image"], 1], hw[table["image"], 0])
+                log(f"dedup years: {aqdedup.describe(dd)} in {dd_out} in {time.perf_counter() - t_d:.2f}s")
             bathy = None
             if bathymetry:
                 # the depth raster under the cages (reference src/utils_tonnage.py:591-665), read once for both steps below
@@ -1046,14 +1087,12 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 log(f"bathymetry: a window of {bathy['grid']['data'].shape[0]} x {bathy['grid']['data'].shape[1]} cells of "
                     f"{', '.join(os.path.basename(f_) for f_ in bathy['grid']['files'])} in {time.perf_counter() - t_b:.2f}s")
             if facilities is not None:
-                # the steps after it (reference src/process_yolo/calc_net_areas.py, src/cluster_facilities.py).  An image this rank's sweep
-                # did not see (another rank's, or one a resumed run had finished) counts as the 1024-px tile the geocoding assumes anyway.
+                # the steps after it (reference src/process_yolo/calc_net_areas.py, src/cluster_facilities.py)
                 from . import facilities as aqfac
                 t_f = time.perf_counter()
-                hw = np.asarray([image_hw.get(str(s_), (geocode.IM_HEIGHT, geocode.IM_WIDTH)) for s_ in table["stems"]], np.int64).reshape(-1, 2)
                 fac_out = facilities or str(save_dir / "facilities.geojson")
                 fac = aqfac.facilities_from_table(table, fac_out, facilities_by, facilities_conf, facilities_eps, facilities_min_cages,
-                                                  hw[table["image"], 1], hw[table["image"], 0], keep=ocean, bathymetry=bathy)
+                                                  hw[table["image"], 1], hw[table["image"], 0], keep=ocean, bathymetry=bathy, dedup=dd)
                 log(f"{len(fac['facility_index'])} facilities of {int((fac['_members'] >= 0).sum())} cages in {fac_out} "
                     f"in {time.perf_counter() - t_f:.2f}s")
             if evaluate is not None:
@@ -1070,11 +1109,10 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 # facility file above stays as it is), the ocean rows when there are any
                 from . import tonnage as aqton
                 t_t = time.perf_counter()
-                hw = np.asarray([image_hw.get(str(s_), (geocode.IM_HEIGHT, geocode.IM_WIDTH)) for s_ in table["stems"]], np.int64).reshape(-1, 2)
                 ton_out = tonnage or str(save_dir)
                 est = aqton.tonnage_from_table(table, ton_out, tonnage_factors, tonnage_errors, tonnage_depths, tonnage_K, tonnage_seed, tonnage_mix,
                                                tonnage_min_depth, tonnage_default_depth, facilities_conf, facilities_eps, facilities_min_cages,
-                                               hw[table["image"], 1], hw[table["image"], 0], keep=ocean, bathymetry=bathy)
+                                               hw[table["image"], 1], hw[table["image"], 0], keep=ocean, bathymetry=bathy, dedup=dd)
                 log(f"tonnage: {aqton.describe(est)} in {ton_out} in {time.perf_counter() - t_t:.2f}s")
     manifest.close()
     eng.close()

@@ -81,6 +81,7 @@ EXPORTS = (
     "aq_eval_scratch_bytes", "aq_eval_member_conf_f64", "aq_box_match_f64",
     "aq_tonnage_simulate_f64", "aq_tonnage_reduce_f64", "aq_tonnage_ndtri_f64", "aq_tonnage_uniform_f64",
     "aq_depth_ranges_f64", "aq_depth_stats_f64",
+    "aq_dedup_fill_u32", "aq_dedup_sets_u32", "aq_dedup_select_f64",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -220,6 +221,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_nms_scratch_bytes.argtypes = [i32, i32]
     lib.aq_nms_scratch_bytes.restype = sz
     lib.aq_nms.argtypes = [vp, i32, i32, i32, i32, f32, f32, i32, vp, vp, i32, vp, vp, vp, vp]
+    lib.aq_dedup_fill_u32.argtypes = [vp, C.c_longlong, vp, vp, vp, vp, C.c_longlong, vp, C.c_longlong, vp]
+    lib.aq_dedup_sets_u32.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, vp]
+    lib.aq_dedup_select_f64.argtypes = [vp, vp, vp, vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp]
     lib.aq_augment_geometry.argtypes = [i32, i32, i32, vp, C.POINTER(i32)]
     lib.aq_augment_taps.argtypes = [i32, i32, i32, vp]
     lib.aq_stem_conv_scaled.argtypes = [vp, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]
@@ -1543,6 +1547,81 @@ def depth_stats(entry_start: torch.Tensor, cages: torch.Tensor, raster: torch.Te
     for t_ in (entry_start, cages, raster, ranges, windows, start_d, bitmap, stats, count):
         t_.record_stream(torch.cuda.current_stream())
     return stats, count, win_h
+
+
+# ---- --dedup-years: aq_dedup_fill_u32 / aq_dedup_sets_u32 / aq_dedup_select_f64 (one year's cages per tile and image pass) ----
+
+DEDUP_MAX_SLOTS, DEDUP_MAX_PERMS = 5, 120
+DEDUP_ABSENT, DEDUP_FULL, DEDUP_BITMAP = 0, 1, 2
+
+
+def _dedup_tensor(name: str, t_: torch.Tensor, dt, shape) -> None:
+    if not t_.is_cuda or t_.dtype != dt or not t_.is_contiguous() or any(b is not None and a != b for a, b in zip(t_.shape, shape)) or t_.ndim != len(shape):
+        raise ValueError(f"dedup: {name} has to be a contiguous CUDA {dt} tensor of shape {shape}, not {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+
+
+def dedup_fill(ring_xy: torch.Tensor, ring_start: torch.Tensor, ring_frame: torch.Tensor, bitmap: torch.Tensor,
+               ring_start_host: np.ndarray, ring_frame_host: np.ndarray) -> torch.Tensor:
+    """aq_dedup_fill_u32 on the current stream: ring_xy int32 CUDA [V, 2], ring_start int32 CUDA [R + 1], ring_frame int32 CUDA [R, 4]
+    (first word, w, h, 0), bitmap int32 CUDA [words], zeroed by the caller and filled in place; the *_host arrays hold the same tables in
+    host memory (int32, contiguous).  include/aq_engine.h states the contract; dedup.fill_numpy gives the same bytes."""
+    _require_gpu()
+    V, R = int(ring_xy.shape[0]), int(ring_start.shape[0]) - 1
+    for name, t_, dt, shape in (("ring_xy", ring_xy, torch.int32, (V, 2)), ("ring_start", ring_start, torch.int32, (R + 1,)),
+                                ("ring_frame", ring_frame, torch.int32, (R, 4)), ("bitmap", bitmap, torch.int32, (None,))):
+        _dedup_tensor(name, t_, dt, shape)
+    rs, rf = np.ascontiguousarray(ring_start_host, dtype=np.int32), np.ascontiguousarray(ring_frame_host, dtype=np.int32)
+    if rs.shape != (R + 1,) or rf.shape != (R, 4):
+        raise ValueError("dedup: the host copies do not have the device tables' shapes")
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    _check(load_library().aq_dedup_fill_u32(ptr(ring_xy), V, ptr(ring_start), rs.ctypes.data, ptr(ring_frame), rf.ctypes.data, R, ptr(bitmap),
+                                            int(bitmap.shape[0]), _stream_ptr()))
+    for t_ in (ring_xy, ring_start, ring_frame, bitmap):
+        t_.record_stream(torch.cuda.current_stream())
+    return bitmap
+
+
+def dedup_sets(group: torch.Tensor, cage: torch.Tensor, bitmap: torch.Tensor, group_host: np.ndarray) -> torch.Tensor:
+    """aq_dedup_sets_u32: group int32 CUDA [G, 16], cage int32 CUDA [C, 8], bitmap int32 CUDA [words] -> the cages' set words, int32 CUDA
+    [C] (the uint32's bits).  dedup.sets_numpy gives the same bytes."""
+    _require_gpu()
+    G, Cn = int(group.shape[0]), int(cage.shape[0])
+    for name, t_, dt, shape in (("group", group, torch.int32, (G, 16)), ("cage", cage, torch.int32, (Cn, 8)), ("bitmap", bitmap, torch.int32, (None,))):
+        _dedup_tensor(name, t_, dt, shape)
+    gh = np.ascontiguousarray(group_host, dtype=np.int32)
+    if gh.shape != (G, 16):
+        raise ValueError("dedup: the host copy does not have the group table's shape")
+    words = torch.empty(Cn, dtype=torch.int32, device=cage.device)
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    _check(load_library().aq_dedup_sets_u32(ptr(group), gh.ctypes.data, G, ptr(cage), Cn, ptr(bitmap), int(bitmap.shape[0]), ptr(words), _stream_ptr()))
+    for t_ in (group, cage, bitmap, words):
+        t_.record_stream(torch.cuda.current_stream())
+    return words
+
+
+def dedup_select(group: torch.Tensor, cage_start: torch.Tensor, cage: torch.Tensor, words: torch.Tensor, area: torch.Tensor,
+                 random_order: torch.Tensor, group_host: np.ndarray, cage_start_host: np.ndarray) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """aq_dedup_select_f64: group int32 CUDA [G, 16], cage_start int32 CUDA [G + 1], cage int32 CUDA [C, 8], words int32 CUDA [C], area
+    float64 CUDA [C], random_order int32 CUDA [G, 5] -> (sel uint8 CUDA [C], zero for the cages outside the G groups; chosen int32 CUDA
+    [G, 4]: min, max, random, n!; sums float64 CUDA [G, 120]).  dedup.select_numpy gives the same bytes."""
+    _require_gpu()
+    G, Cn = int(group.shape[0]), int(cage.shape[0])
+    for name, t_, dt, shape in (("group", group, torch.int32, (G, 16)), ("cage_start", cage_start, torch.int32, (G + 1,)), ("cage", cage, torch.int32, (Cn, 8)),
+                                ("words", words, torch.int32, (Cn,)), ("area", area, torch.float64, (Cn,)), ("random_order", random_order, torch.int32, (G, 5))):
+        _dedup_tensor(name, t_, dt, shape)
+    gh, ch = np.ascontiguousarray(group_host, dtype=np.int32), np.ascontiguousarray(cage_start_host, dtype=np.int32)
+    if gh.shape != (G, 16) or ch.shape != (G + 1,):
+        raise ValueError("dedup: the host copies do not have the device tables' shapes")
+    dev = group.device
+    sel = torch.zeros(Cn, dtype=torch.uint8, device=dev)
+    chosen = torch.empty((G, 4), dtype=torch.int32, device=dev)
+    sums = torch.empty((G, DEDUP_MAX_PERMS), dtype=torch.float64, device=dev)
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    _check(load_library().aq_dedup_select_f64(ptr(group), gh.ctypes.data, ptr(cage_start), ch.ctypes.data, G, ptr(cage), ptr(words), ptr(area), Cn,
+                                              ptr(random_order), ptr(sel), ptr(chosen), ptr(sums), _stream_ptr()))
+    for t_ in (group, cage_start, cage, words, area, random_order, sel, chosen, sums):
+        t_.record_stream(torch.cuda.current_stream())
+    return sel, chosen, sums
 
 
 # ---- --land-filter: aq_land_filter_f64 (detection boxes against the segments of the land polygons) ----

@@ -298,11 +298,19 @@ def write_facility_detections_geojson(path: str, table: Dict[str, np.ndarray], f
 
 def facilities_from_table(table: Dict[str, np.ndarray], out_geojson: str, by: str = "year", conf_thresh: float = 0.5, eps: float = 10.0,
                           min_cages: int = 5, widths=geocode.IM_WIDTH, heights=geocode.IM_HEIGHT, cpu: bool = False, keep=None,
-                          bathymetry: Optional[dict] = None) -> Dict[str, list]:
+                          bathymetry: Optional[dict] = None, dedup: Optional[dict] = None) -> Dict[str, list]:
     """cluster() and both files: `out_geojson` and <out>_detections.geojson.  cpu = labels from dbscan_numpy instead of the GPU; keep =
     cluster()'s (the land filter's ocean rows).  bathymetry (bathymetry.settings' result): the facilities also get the reference's
-    add_facility_depth columns bathy_depth, cage_depth, bathy_min, bathy_max, bathy_mean (null without a valid cell)."""
-    fac = cluster(table, by, conf_thresh, eps, min_cages, widths, heights, labels_fn=dbscan_numpy if cpu else None, keep=keep)
+    add_facility_depth columns bathy_depth, cage_depth, bathy_min, bathy_max, bathy_mean (null without a valid cell).  dedup
+    (dedup.dedup_from_table's result, made with the same conf_thresh and keep; by = "pass" only): the survivors of its selection are
+    clustered and the facilities get cage_ids_min and cage_ids_max."""
+    if dedup is not None:
+        if by != "pass":
+            raise ValueError("facilities: the years of a pass are de-duplicated, so --dedup-years clusters by 'pass', not by 'year'")
+        from . import dedup as aqdedup
+        fac = aqdedup.cluster(table, dedup, conf_thresh, eps, min_cages, widths, heights, labels_fn=dbscan_numpy if cpu else None)
+    else:
+        fac = cluster(table, by, conf_thresh, eps, min_cages, widths, heights, labels_fn=dbscan_numpy if cpu else None, keep=keep)
     if bathymetry is not None:
         from . import bathymetry as aqbathy
         cols = aqbathy.depths_of(fac, table, bathymetry, cpu=cpu)

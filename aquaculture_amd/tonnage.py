@@ -461,16 +461,21 @@ def write_files(out_dir: str, est: dict, params: dict) -> None:
 def tonnage_from_table(table, out_dir: str, factors_path: str, errors_path: Optional[str] = None, depths_path: Optional[str] = None,
                        K: int = 10000, seed: int = 0, mix: float = 0.5, min_depth: float = DEFAULT_MIN_DEPTH, default_depth: float = DEFAULT_DEPTH,
                        conf_thresh: float = 0.5, eps: float = 10.0, min_cages: int = 5, widths=geocode.IM_WIDTH, heights=geocode.IM_HEIGHT,
-                       cpu: bool = False, keep=None, bathymetry: Optional[dict] = None) -> dict:
+                       cpu: bool = False, keep=None, bathymetry: Optional[dict] = None, dedup: Optional[dict] = None) -> dict:
     """Facilities per image pass (facilities.cluster), their estimates and the three files in `out_dir`.  bathymetry (bathymetry.settings'
     result, instead of a depths file): the facilities' cage depths come from the depth raster and are written to facility_depths.csv
-    beside the three files, in the form `depths_path` takes."""
+    beside the three files, in the form `depths_path` takes.  dedup (dedup.dedup_from_table's result, made with the same conf_thresh and
+    keep): the survivors of its selection are clustered, and cage_ids_min / cage_ids_max widen the area bounds as the reference's do."""
     if bathymetry is not None and depths_path:
         raise ValueError("tonnage: cage depths come from --bathymetry or from --tonnage-depths, not from both")
     factors = read_factors(factors_path)
     errors = read_errors(errors_path) if errors_path else None
     depths = read_depths(depths_path) if depths_path else None
-    fac = aqfac.cluster(table, "pass", conf_thresh, eps, min_cages, widths, heights, labels_fn=aqfac.dbscan_numpy if cpu else None, keep=keep)
+    if dedup is not None:
+        from . import dedup as aqdedup
+        fac = aqdedup.cluster(table, dedup, conf_thresh, eps, min_cages, widths, heights, labels_fn=aqfac.dbscan_numpy if cpu else None)
+    else:
+        fac = aqfac.cluster(table, "pass", conf_thresh, eps, min_cages, widths, heights, labels_fn=aqfac.dbscan_numpy if cpu else None, keep=keep)
     extra = {}
     if bathymetry is not None:
         from . import bathymetry as aqbathy
@@ -487,7 +492,8 @@ def tonnage_from_table(table, out_dir: str, factors_path: str, errors_path: Opti
     write_files(out_dir, est, {"device": device, "cpu": bool(cpu), "mix": float(mix), "min_depth": float(min_depth), "default_depth": float(default_depth),
                                "factors": {p: list(v) for p, v in sorted(factors.items())},
                                "errors": [[*k, *v] for k, v in sorted((errors or {}).items())], "depths_file": bool(depths_path),
-                               "facilities_conf": float(conf_thresh), "facilities_eps": float(eps), "facilities_min_cages": int(min_cages), **extra})
+                               "facilities_conf": float(conf_thresh), "facilities_eps": float(eps), "facilities_min_cages": int(min_cages), **extra,
+                               **({"dedup_years": {"selection": dedup["selection"]}} if dedup is not None else {})})
     return est
 
 
@@ -522,6 +528,10 @@ def main(argv: Optional[List[str]] = None) -> int:
     add_options(p)
     from . import bathymetry as aqbathy
     aqbathy.add_options(p)
+    from . import dedup as aqdedup
+    p.add_argument("--dedup-years", nargs=2, default=None, metavar=("BLANK_KEY_CSV", "BLANK_GEOM_GEOJSON"),
+                   help="keep one year's cages per tile and pass before clustering (the --dedup-years step), from the sweep's two blank files")
+    aqdedup.add_options(p)
     opt = p.parse_args(argv)
     if not opt.tonnage_factors:
         p.error("--tonnage-factors FILE is needed")
@@ -535,9 +545,13 @@ def main(argv: Optional[List[str]] = None) -> int:
         segs = aqland.load_land_geojson(opt.land)
         keep = aqland.ocean_rows(table, segs, cpu=opt.cpu)
     bathy = aqbathy.settings(opt.bathymetry, table, keep, opt.bathymetry_statistic) if opt.bathymetry else None
+    dd = None
+    if opt.dedup_years:
+        dd = aqdedup.dedup_from_table(table, opt.dedup_years[0], opt.dedup_years[1], out, opt.dedup_selection, opt.dedup_seed, opt.facilities_conf, keep,
+                                      opt.image_size[0], opt.image_size[1], cpu=opt.cpu)
     est = tonnage_from_table(table, out, opt.tonnage_factors, opt.tonnage_errors, opt.tonnage_depths, opt.tonnage_K, opt.tonnage_seed, opt.tonnage_mix,
                              opt.tonnage_min_depth, opt.tonnage_default_depth, opt.facilities_conf, opt.facilities_eps, opt.facilities_min_cages,
-                             opt.image_size[0], opt.image_size[1], cpu=opt.cpu, keep=keep, bathymetry=bathy)
+                             opt.image_size[0], opt.image_size[1], cpu=opt.cpu, keep=keep, bathymetry=bathy, dedup=dd)
     print(f"{describe(est)} in {out}")
     return 0
 

@@ -760,6 +760,58 @@ int aq_depth_stats_f64(const int32_t* entry_start_dev, long long F, const int32_
                        int nrows, int ncols, double nodata, uint32_t* bitmap_dev, long long bitmap_words, double* stats_dev,
                        long long* count_dev, void* stream);
 
+/* ---- --dedup-years (dedup.hip): one year's cages per tile and image pass (reference src/utils_tonnage.py:668-911,
+ * dedup_cages_in_overlap_years_with_white_space).  The images of one (pass, tile key) group share a pixel grid of w x h pixels; each image
+ * that takes part is a slot (at most AQ_DEDUP_MAX_SLOTS, in ascending year) with a mask: the whole frame (AQ_DEDUP_FULL) or a bitmap
+ * (AQ_DEDUP_BITMAP) of h rows x ceil((w + 1) / 32) uint32 words, bit c % 32 of word c / 32 of row r = pixel (c, r).  Under an order of the
+ * slots, slot i is allotted its mask minus the masks before it; a cage of slot i with the closed pixel box [xmin, xmax] x [ymin, ymax]
+ * survives iff the box meets a pixel square of that region, i.e. iff the window columns max(xmin - 1, 0) .. min(xmax, w - 1), rows
+ * max(ymin - 1, 0) .. min(ymax, h - 1) holds a pixel of it.  All three launchers run on `stream`, allocate nothing, use integer atomics only
+ * (the same bytes on every call), keep every index inside its array on the device -- tables the caller got wrong give wrong numbers but no
+ * access outside the arrays -- and refuse before anything is launched: a count (vertices, rings, bitmap words, groups, cages) >= 2^31, a
+ * null pointer, an unaligned array, and what each lists below, checked on the *_host copies of the device tables.
+ * Tables: group [G][16] int32 (64 bytes; 16-byte aligned) = n, w, h, 0, kind[5], first bitmap word[5], 0, 0; cage [C][8] int32 (16-byte
+ * aligned) = group, slot, xmin, xmax, ymin, ymax, 0, 0. */
+#define AQ_DEDUP_MAX_SLOTS 5
+#define AQ_DEDUP_MAX_PERMS 120
+#define AQ_DEDUP_ABSENT 0
+#define AQ_DEDUP_FULL 1
+#define AQ_DEDUP_BITMAP 2
+#define AQ_DEDUP_SEL_MIN 4       /* the bits aquaculture_amd.tonnage gives the selections */
+#define AQ_DEDUP_SEL_MAX 8
+#define AQ_DEDUP_SEL_RANDOM 16
+/* aq_dedup_fill_u32: ring r = the vertices ring_start[r] .. ring_start[r + 1] - 1 of ring_xy_dev [V][2] int32 (x, y pixel corners, 8-byte
+ * aligned), a closed walk (first vertex repeated at the end); ring_frame [R][4] int32 (16-byte aligned) = first bitmap word, w, h, 0: every
+ * ring has a bitmap of its own in bitmap_dev [bitmap_words], which the caller zeroed.  Launch 1, one lane per vertex: the segment to the
+ * next vertex of the same ring, if vertical at 0 <= x <= w, toggles bit x of the rows min(y) .. max(y) - 1 inside the frame with atomicXor
+ * (x = w lands in the row's extra column); other segments toggle nothing.  Launch 2, one lane per row: the inclusive prefix XOR of the
+ * row's bits, so that pixel (c, r) is set iff an odd number of the ring's unit edges in row r lie at x <= c: the even-odd fill of the
+ * ring.  R = 0 does nothing.  Also refused: ring_start that decreases or leaves [0, V], a frame side outside [1, 32768], a bitmap that does
+ * not fit bitmap_words. */
+int aq_dedup_fill_u32(const int32_t* ring_xy_dev, long long V, const int32_t* ring_start_dev, const int32_t* ring_start_host,
+                      const int32_t* ring_frame_dev, const int32_t* ring_frame_host, long long R, uint32_t* bitmap_dev,
+                      long long bitmap_words, void* stream);
+/* aq_dedup_sets_u32: words_dev[e] for every cage e: bit S (S = a set of slots as a number, bit j = slot j) is set iff some pixel of the
+ * cage's window lies in the masks of exactly the slots of S among the group's n, and S holds the cage's own slot.  0 for a group outside
+ * [0, G), a slot outside [0, n), an AQ_DEDUP_ABSENT slot and an empty window.  One wavefront per cage: lanes stride over the (row, word
+ * column) positions of the window.  C = 0 does nothing.  Also refused: a group with n outside [1, 5] (the longest image pass has five
+ * years), a frame side outside [1, 32768], a kind that is none of the three, a slot's bitmap that does not fit bitmap_words. */
+int aq_dedup_sets_u32(const int32_t* group_dev, const int32_t* group_host, long long G, const int32_t* cage_dev, long long C,
+                      const uint32_t* bitmap_dev, long long bitmap_words, uint32_t* words_dev, void* stream);
+/* aq_dedup_select_f64: group g owns the cages cage_start[g] .. cage_start[g + 1] - 1.  Order number q of the n! is the q-th of
+ * itertools.permutations(range(n)); a cage of slot i survives an order iff its word has a set without any slot placed before i.
+ * sums_dev [G][120]: entry q < n! = the areas (area_dev [C]; a NaN counts as 0) of the order's survivors, added one cage at a time in
+ * ascending e from +0.0 (fp64 + only); entries from n! on are +0.0.  One ordered walk over the n! sums: max = the last order whose sum is
+ * >= the running best, which starts at 0; min = the first whose sum is < the running best, which starts at +inf (the reference's
+ * comparisons, :770-775); random = random_order_dev [G][5] int32, slot random_order[g][k] being the k-th (an entry that is no slot of the
+ * group is skipped, a slot that is not named comes last).  chosen_dev [G][4] int32 (16-byte aligned) = the order numbers of min, max and
+ * random and n!; -1 where no order qualified, and then no cage survives that selection.  sel_dev [C] uint8: for the cages of the G groups,
+ * AQ_DEDUP_SEL_MIN | _MAX | _RANDOM of the selections they survive (other cages are not written).  One wavefront per group, lanes over
+ * the orders.  G = 0 does nothing.  Also refused: n outside [1, 5], cage_start that decreases or leaves [0, C]. */
+int aq_dedup_select_f64(const int32_t* group_dev, const int32_t* group_host, const int32_t* cage_start_dev, const int32_t* cage_start_host,
+                        long long G, const int32_t* cage_dev, const uint32_t* words_dev, const double* area_dev, long long C,
+                        const int32_t* random_order_dev, uint8_t* sel_dev, int32_t* chosen_dev, double* sums_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
