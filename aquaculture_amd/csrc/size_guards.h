@@ -112,4 +112,8 @@ inline bool dedup_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }
 inline bool dedup_frame_fits(ll w, ll h) { return w >= 1 && h >= 1 && w <= kDedupMaxSide && h <= kDedupMaxSide; }
 constexpr ll dedup_pitch(ll w) { return cdiv(w + 1, 32); }  // words of a bitmap row: w pixels and the column x = w of the toggles
 
+// ---- model_errors.hip ----  (queries, keys and moment groups of a call are 31-bit indices; like dedup's, no line in oracle/guards.py:
+// tests/test_gpu_model_errors.py walks the edge through the launchers' refusals)
+inline bool model_error_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }
+
 }  // namespace sg

@@ -146,6 +146,15 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "--facilities-conf / -eps / -min-cages); with --land-filter the ocean detections are scored; needs --geocode-bboxes")
     from .evaluate import add_options as _evaluate_options
     _evaluate_options(p)
+    p.add_argument("--model-errors", default=None, metavar="TRUTH_GEOJSON",
+                   help="after the sweep, its geocoding and the land filter, join the circle and square detections of det_conf > "
+                        "--model-errors-conf to the human labels of TRUTH_GEOJSON (the reference's output/humanlabels.geojson, with the labels' "
+                        "pixel boxes and image sizes) -- each detection keeps the label of its year and type it overlaps most -- and fit one normal "
+                        "to label area - detection area per image pass and cage type (the reference's define_model_error_distributions, "
+                        "src/utils_tonnage.py:130-203), the join and the moments on the GPU; writes model_errors.csv, model_error_cages.csv and "
+                        "model_errors.json, and --tonnage uses the table as its model errors; needs --geocode-bboxes, excludes --tonnage-errors")
+    from .model_errors import add_options as _model_error_options
+    _model_error_options(p)
     p.add_argument("--tonnage", nargs="?", const="", default=None, metavar="DIR",
                    help="after the sweep, its geocoding and the land filter, cluster the detections into facilities per image pass and estimate "
                         "their live-weight production per pass by the reference's bootstrap (src/utils_tonnage.py, "
@@ -187,6 +196,10 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--land-filter filters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if opt.evaluate is not None and not opt.geocode_bboxes:
         p.error("--evaluate scores geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if opt.model_errors is not None and not opt.geocode_bboxes:
+        p.error(MODEL_ERRORS_NEED_GEOCODE)
+    if opt.model_errors is not None and opt.tonnage_errors:
+        p.error(MODEL_ERRORS_OR_FILE)
     if opt.evaluate is not None:
         from .evaluate import grids_from_options
         try:
@@ -201,6 +214,8 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
 
 DEDUP_NEEDS_GEOCODE = "--dedup-years works on geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)"
 DEDUP_BY_PASS = "--dedup-years keeps one year per tile and image pass: with it --facilities needs --facilities-by pass, not year"
+MODEL_ERRORS_NEED_GEOCODE = "--model-errors joins geocoded detections to the labels: it needs --geocode-bboxes CSV (and --save-txt --save-conf)"
+MODEL_ERRORS_OR_FILE = "the model errors of --tonnage come from --model-errors or from --tonnage-errors, not from both"
 
 
 def run_params(weights_id, conf_thres, iou_thres, max_det, imgsz, precision, save_conf, classes=None, agnostic_nms=False, augment=False,
@@ -229,7 +244,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         land_filter=None, ocean_out=None, evaluate=None, evaluate_out=None, evaluate_conf=None, evaluate_eps=None, evaluate_min_cages=None,
         evaluate_images=None, tonnage=None, tonnage_factors=None, tonnage_errors=None, tonnage_depths=None, tonnage_default_depth=4.84,
         tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, bathymetry=None, bathymetry_statistic="bathy_min", dedup_years=None,
-        dedup_selection="random", dedup_seed=0, log=print, **unsupported):
+        dedup_selection="random", dedup_seed=0, model_errors=None, model_errors_conf=None, model_errors_out=None, log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb_checked, jpeg_slots_to_rgb, JPEG_WS_MAX, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     if dedup_years is not None and not geocode_bboxes:
@@ -246,6 +261,10 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         raise ValueError("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if land_filter is not None and not geocode_bboxes:
         raise ValueError("--land-filter filters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if model_errors is not None and not geocode_bboxes:
+        raise ValueError(MODEL_ERRORS_NEED_GEOCODE)
+    if model_errors is not None and tonnage_errors:
+        raise ValueError(MODEL_ERRORS_OR_FILE)
     if evaluate is not None and not geocode_bboxes:
         raise ValueError("--evaluate scores geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if tonnage is not None and not geocode_bboxes:
@@ -1064,7 +1083,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 log(f"{n_ocean} of {ocean.shape[0]} detections at sea ({segs.shape[0]} land edges) in {ocean_path} in {time.perf_counter() - t_l:.2f}s")
             dd = None
             hw = None
-            if facilities is not None or tonnage is not None or dedup_years is not None:
+            if facilities is not None or tonnage is not None or dedup_years is not None or model_errors is not None:
                 # An image this rank's sweep did not see (another rank's, or one a resumed run had finished) counts as the 1024-px tile the
                 # geocoding assumes anyway.
                 hw = np.asarray([image_hw.get(str(s_), (geocode.IM_HEIGHT, geocode.IM_WIDTH)) for s_ in table["stems"]], np.int64).reshape(-1, 2)
@@ -1104,6 +1123,17 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 ev = aqeval.evaluate_table(table, evaluate, ev_out, *grids, op=(facilities_conf, facilities_eps, facilities_min_cages), keep=ocean,
                                            images=aqeval.read_image_list(evaluate_images) if evaluate_images else None)
                 log(f"{aqeval.describe(ev)} in {ev_out} in {time.perf_counter() - t_e:.2f}s")
+            computed_errors = None
+            if model_errors is not None:
+                # the model's cage-area error per pass and type (reference src/utils_tonnage.py:130-203) from the same table and the labels
+                # --evaluate reads, the ocean rows when there are any; what the bootstrap below then draws its model errors from
+                from . import model_errors as aqerr
+                t_m = time.perf_counter()
+                me_out = model_errors_out or str(save_dir)
+                me = aqerr.model_errors_from_table(table, model_errors, me_out, facilities_conf if model_errors_conf is None else model_errors_conf,
+                                                   keep=ocean, widths=hw[table["image"], 1], heights=hw[table["image"], 0])
+                computed_errors = me["errors"]
+                log(f"{aqerr.describe(me)} in {me_out} in {time.perf_counter() - t_m:.2f}s")
             if tonnage is not None:
                 # the reference's measuring step (src/utils_tonnage.py): facilities per image pass whatever --facilities-by says (the
                 # facility file above stays as it is), the ocean rows when there are any
@@ -1112,7 +1142,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 ton_out = tonnage or str(save_dir)
                 est = aqton.tonnage_from_table(table, ton_out, tonnage_factors, tonnage_errors, tonnage_depths, tonnage_K, tonnage_seed, tonnage_mix,
                                                tonnage_min_depth, tonnage_default_depth, facilities_conf, facilities_eps, facilities_min_cages,
-                                               hw[table["image"], 1], hw[table["image"], 0], keep=ocean, bathymetry=bathy, dedup=dd)
+                                               hw[table["image"], 1], hw[table["image"], 0], keep=ocean, bathymetry=bathy, dedup=dd,
+                                               **({"errors": computed_errors} if computed_errors is not None else {}))
                 log(f"tonnage: {aqton.describe(est)} in {ton_out} in {time.perf_counter() - t_t:.2f}s")
     manifest.close()
     eng.close()

@@ -79,6 +79,7 @@ EXPORTS = (
     "aq_facility_scratch_bytes", "aq_facility_dbscan_f64",
     "aq_land_scratch_bytes", "aq_land_filter_f64",
     "aq_eval_scratch_bytes", "aq_eval_member_conf_f64", "aq_box_match_f64",
+    "aq_model_error_match_f64", "aq_model_error_moments_f64",
     "aq_tonnage_simulate_f64", "aq_tonnage_reduce_f64", "aq_tonnage_ndtri_f64", "aq_tonnage_uniform_f64",
     "aq_depth_ranges_f64", "aq_depth_stats_f64",
     "aq_dedup_fill_u32", "aq_dedup_sets_u32", "aq_dedup_select_f64",
@@ -150,6 +151,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_eval_scratch_bytes.restype = sz
     lib.aq_eval_member_conf_f64.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, C.c_double, i32, vp, sz, vp, vp]
     lib.aq_box_match_f64.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, vp, i32, vp, i32, vp, vp, vp]
+    lib.aq_model_error_match_f64.argtypes = [vp, vp, vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, i32, vp, vp, vp, vp]
+    lib.aq_model_error_moments_f64.argtypes = [vp, vp, vp, C.c_longlong, C.c_longlong, vp, vp, vp, vp]
     lib.aq_tonnage_simulate_f64.argtypes = [C.c_ulonglong, C.c_longlong, C.c_longlong, vp, vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, i32,
                                             C.c_double, C.c_double, vp, vp, vp]
     lib.aq_tonnage_reduce_f64.argtypes = [vp, C.c_longlong, C.c_longlong, vp, i32, vp, vp, vp]
@@ -1431,6 +1434,82 @@ def box_match(qbox: torch.Tensor, qgroup: torch.Tensor, kbox: torch.Tensor, kgro
     for t_ in (qbox, qgroup, kb, start, hit) + ((pl, out) if pl is not None else ()):
         t_.record_stream(torch.cuda.current_stream())
     return hit, out
+
+
+# ---- --model-errors: aq_model_error_match_f64 and aq_model_error_moments_f64 (the cage-area error distributions) ----
+
+def model_error_match(qbox: torch.Tensor, qgroup: torch.Tensor, qarea: torch.Tensor, kbox: torch.Tensor, kgroup: torch.Tensor, karea: torch.Tensor,
+                      G: int, times: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """aq_model_error_match_f64 on the current stream: qbox float64 CUDA [Q, 4] (x0, y0, x1, y1), qgroup int32 CUDA [Q], qarea float64 CUDA [Q],
+    kbox float64 CUDA [N, 4], kgroup int32 CUDA [N] with ids in [0, G), karea float64 CUDA [N], the keys in any order (box_match_sort sorts
+    them) -> (match int32 CUDA [Q]: the row of the key of the query's group whose closed box overlaps the query's most, the smallest row among
+    equals, -1 without one; overlap float64 CUDA [Q]: 100 x the intersection's share of the query's box; error float64 CUDA [Q]:
+    karea[match] - qarea; both NaN without a match).  model_errors.match_numpy gives the same bytes.  times = a dict that receives "sort_ms"
+    and "kernel_ms"."""
+    _require_gpu()
+    lib = load_library()
+    assert qbox.is_cuda and qbox.dtype == torch.float64 and kbox.dtype == torch.float64 and qgroup.dtype == torch.int32 and kgroup.dtype == torch.int32
+    assert qarea.dtype == torch.float64 and karea.dtype == torch.float64
+    qbox, qgroup, qarea = qbox.contiguous(), qgroup.contiguous(), qarea.contiguous()
+    Q, N, G = qbox.shape[0], kbox.shape[0], int(G)
+    assert qbox.shape == (Q, 4) and kbox.shape == (N, 4) and qgroup.shape == (Q,) and kgroup.shape == (N,) and qarea.shape == (Q,) and karea.shape == (N,)
+    if G < 0 or (N and not (0 <= int(kgroup.min()) and int(kgroup.max()) < G)):
+        raise ValueError(f"model errors: the keys' group ids have to lie in [0, {G})")
+    match = torch.empty(Q, dtype=torch.int32, device=qbox.device)
+    overlap = torch.empty(Q, dtype=torch.float64, device=qbox.device)
+    error = torch.empty(Q, dtype=torch.float64, device=qbox.device)
+    if Q == 0:
+        return match, overlap, error
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
+    if ev:
+        ev[0].record()
+    order, start = box_match_sort(kbox, kgroup, G)
+    kb, ka, kr = kbox[order].contiguous(), karea[order].contiguous(), order.to(torch.int32)
+    if ev:
+        ev[1].record()
+    _check(lib.aq_model_error_match_f64(qbox.data_ptr(), qgroup.data_ptr(), qarea.data_ptr(), Q, kb.data_ptr() if N else None,
+                                        kr.data_ptr() if N else None, ka.data_ptr() if N else None, N, start.data_ptr(), G,
+                                        match.data_ptr(), overlap.data_ptr(), error.data_ptr(), _stream_ptr()))
+    if ev:
+        ev[2].record()
+        ev[2].synchronize()
+        times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+    for t_ in (qbox, qgroup, qarea, kb, ka, kr, start, match, overlap, error):
+        t_.record_stream(torch.cuda.current_stream())
+    return match, overlap, error
+
+
+def model_error_moments(error: torch.Tensor, match: torch.Tensor, mgroup: torch.Tensor, G: int,
+                        times: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """aq_model_error_moments_f64 on the current stream: error float64 CUDA [Q], match int32 CUDA [Q], mgroup int32 CUDA [Q] (a row outside
+    [0, G) belongs to no group) -> (n int64 CUDA [G], mean float64 CUDA [G], sd float64 CUDA [G]) over the rows with match >= 0 and a finite
+    error, per group, summed in the order include/aq_engine.h states; mean and sd are NaN where n = 0.  model_errors.moments_numpy gives the
+    same bytes.  times = a dict that receives "kernel_ms"."""
+    _require_gpu()
+    lib = load_library()
+    assert error.is_cuda and error.dtype == torch.float64 and match.dtype == torch.int32 and mgroup.dtype == torch.int32
+    error, match, mgroup = error.contiguous(), match.contiguous(), mgroup.contiguous()
+    Q, G = error.shape[0], int(G)
+    assert error.shape == (Q,) and match.shape == (Q,) and mgroup.shape == (Q,)
+    if G < 0:
+        raise ValueError(f"model errors: {G} moment groups")
+    n = torch.empty(G, dtype=torch.int64, device=error.device)
+    mean = torch.empty(G, dtype=torch.float64, device=error.device)
+    sd = torch.empty(G, dtype=torch.float64, device=error.device)
+    if G == 0:
+        return n, mean, sd
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if times is not None else None
+    if ev:
+        ev[0].record()
+    _check(lib.aq_model_error_moments_f64(error.data_ptr() if Q else None, match.data_ptr() if Q else None, mgroup.data_ptr() if Q else None, Q, G,
+                                          n.data_ptr(), mean.data_ptr(), sd.data_ptr(), _stream_ptr()))
+    if ev:
+        ev[1].record()
+        ev[1].synchronize()
+        times["kernel_ms"] = ev[0].elapsed_time(ev[1])
+    for t_ in (error, match, mgroup, n, mean, sd):
+        t_.record_stream(torch.cuda.current_stream())
+    return n, mean, sd
 
 
 # ---- --tonnage: aq_tonnage_simulate_f64 / aq_tonnage_reduce_f64 (the production bootstrap) and the two test hooks ----

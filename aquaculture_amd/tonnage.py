@@ -461,15 +461,19 @@ def write_files(out_dir: str, est: dict, params: dict) -> None:
 def tonnage_from_table(table, out_dir: str, factors_path: str, errors_path: Optional[str] = None, depths_path: Optional[str] = None,
                        K: int = 10000, seed: int = 0, mix: float = 0.5, min_depth: float = DEFAULT_MIN_DEPTH, default_depth: float = DEFAULT_DEPTH,
                        conf_thresh: float = 0.5, eps: float = 10.0, min_cages: int = 5, widths=geocode.IM_WIDTH, heights=geocode.IM_HEIGHT,
-                       cpu: bool = False, keep=None, bathymetry: Optional[dict] = None, dedup: Optional[dict] = None) -> dict:
-    """Facilities per image pass (facilities.cluster), their estimates and the three files in `out_dir`.  bathymetry (bathymetry.settings'
+                       cpu: bool = False, keep=None, bathymetry: Optional[dict] = None, dedup: Optional[dict] = None,
+                       errors: Optional[Dict[Tuple[str, str], Tuple[float, float]]] = None) -> dict:
+    """Facilities per image pass (facilities.cluster), their estimates and the three files in `out_dir`.  errors = read_errors' table made
+    in this process instead of a file (model_errors.distributions' ``errors``); tonnage.json records it as it records a file's.  bathymetry (bathymetry.settings'
     result, instead of a depths file): the facilities' cage depths come from the depth raster and are written to facility_depths.csv
     beside the three files, in the form `depths_path` takes.  dedup (dedup.dedup_from_table's result, made with the same conf_thresh and
     keep): the survivors of its selection are clustered, and cage_ids_min / cage_ids_max widen the area bounds as the reference's do."""
     if bathymetry is not None and depths_path:
         raise ValueError("tonnage: cage depths come from --bathymetry or from --tonnage-depths, not from both")
+    if errors is not None and errors_path:
+        raise ValueError("tonnage: model errors come from --model-errors or from --tonnage-errors, not from both")
     factors = read_factors(factors_path)
-    errors = read_errors(errors_path) if errors_path else None
+    errors = read_errors(errors_path) if errors_path else errors
     depths = read_depths(depths_path) if depths_path else None
     if dedup is not None:
         from . import dedup as aqdedup

@@ -658,6 +658,28 @@ int aq_eval_member_conf_f64(const long long* keys_sorted_dev, const int32_t* per
 int aq_box_match_f64(const double* qbox_dev, const int32_t* qgroup_dev, long long Q, const double* kbox_dev, long long N,
                      const int32_t* group_start_dev, int G, const double* payload_dev, int K, uint8_t* hit_dev, double* out_dev, void* stream);
 
+/* ---- --model-errors (model_errors.hip): the cage-area error distributions (reference src/utils_tonnage.py:130-203, :284-327) ----
+ * aq_model_error_match_f64: the queries, sorted keys and group starts of aq_box_match_f64, with qarea_dev [Q] (the queries' areas), krow_dev [N]
+ * (the original row number of each sorted key; rows are distinct and >= 0, a negative one is skipped) and karea_dev [N] (the keys' areas, in
+ * sorted order).  A key is a candidate of a query when aq_box_match_f64 would count it; inter = (min(q.x1, k.x1) - max(q.x0, k.x0)) *
+ * (min(q.y1, k.y1) - max(q.y0, k.y0)), two subtractions and one product.  The match is the candidate of the largest inter; among equal inter the
+ * smallest row wins; a NaN inter loses to every number.  match_dev[q] (int32) = that key's row, -1 without a candidate; overlap_dev[q] = 100 *
+ * inter / ((q.x1 - q.x0) * (q.y1 - q.y0)) (inf for a query without area); error_dev[q] = karea[match] - qarea[q]; both NaN without a candidate,
+ * and every NaN written is 0x7FF8000000000000.  On `stream`, one wavefront per query, no atomics, one launch; Q = 0 does nothing.  Q or N >= 2^31,
+ * G < 0, a null pointer (the three key arrays may be null when N = 0) and an unaligned array (boxes 32 bytes, doubles 8, int32 4) are refused
+ * before anything is launched; group starts are kept inside [0, N] on the device. */
+int aq_model_error_match_f64(const double* qbox_dev, const int32_t* qgroup_dev, const double* qarea_dev, long long Q, const double* kbox_dev,
+                             const int32_t* krow_dev, const double* karea_dev, long long N, const int32_t* group_start_dev, int G,
+                             int32_t* match_dev, double* overlap_dev, double* error_dev, void* stream);
+/* aq_model_error_moments_f64: query q is a member of moment group g when match_dev[q] >= 0, mgroup_dev[q] == g and error_dev[q] is finite.  Per
+ * group n_dev[g] (int64) = its members, mean_dev[g] = S / n, sd_dev[g] = sqrt(D / n) (the population sd, scipy.stats.norm.fit) with S = the sum
+ * of error and D = the sum of (error - mean)^2 in one written order: lane l of 64 adds the rows q = l, l + 64, ... in increasing q, +0.0 for a
+ * non-member; the 64 partials then fold as v[i] + v[i + 32], + 16, ... + 1.  n = 0: mean and sd are NaN (0x7FF8000000000000).  fp64 in + - x /
+ * sqrt only, nothing contracted.  On `stream`, one wavefront per group, no atomics, one launch; G = 0 does nothing.  Q or G >= 2^31, a null
+ * pointer (the three inputs may be null when Q = 0) and an unaligned array are refused before anything is launched. */
+int aq_model_error_moments_f64(const double* error_dev, const int32_t* match_dev, const int32_t* mgroup_dev, long long Q, long long G,
+                               long long* n_dev, double* mean_dev, double* sd_dev, void* stream);
+
 /* --land-filter: which of N boxes (x0, y0, x1, y1; x0 <= x1, y0 <= y1) lie on land (reference src/process_yolo/geocode_results.py:200-218:
  * sjoin with the predicate `intersects`), against the E segments (ax, ay, bx, by) of all rings of the land polygons, exterior and holes
  * alike; everything fp64, EPSG:3857 metres.  One byte per box: bit 0 = some segment meets the closed box (the bounding boxes overlap, closed,
