@@ -42,6 +42,7 @@ SOURCES = [
     ("facilities.hip", ["-ffp-contract=off"]),   # --facilities: DBSCAN of the detections' centroids; the fp64 distance test exactly as written (no fma)
     ("land_filter.hip", ["-ffp-contract=off"]),  # --land-filter: boxes against the land polygons' segments; the fp64 orientation determinant exactly as written (no fma)
     ("evaluate.hip", ["-ffp-contract=off"]),     # --evaluate: member confidences over the facilities' neighbour search (the same fp64 distance test) and the box joins
+    ("eval_subsets.hip", ["-ffp-contract=off"]), # --evaluate-kfold: the same two steps for up to 32 subsets (folds) of one point set per call, one bit of a mask word each
     ("model_errors.hip", ["-ffp-contract=off"]), # --model-errors: the best-overlap join (inter = two subtractions and one product) and the moments in one written order (no fma)
     ("tonnage.hip", ["-ffp-contract=off"]),      # --tonnage: the production bootstrap; fp64 in + - x / sqrt only, every product and sum rounded as written (no fma)
     ("depth.hip", ["-ffp-contract=off"]),        # --bathymetry: depth-raster cells under the facilities' cages; fp64 cell ranges and one written order of the sum (no fma)

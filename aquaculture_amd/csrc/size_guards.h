@@ -116,4 +116,12 @@ constexpr ll dedup_pitch(ll w) { return cdiv(w + 1, 32); }  // words of a bitmap
 // tests/test_gpu_model_errors.py walks the edge through the launchers' refusals)
 inline bool model_error_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }
 
+// ---- eval_subsets.hip ----  (n points, queries or keys of a call: a 31-bit index; the [S][n][K] arrays of doubles are indexed in 64 bits,
+// (s n + i) K, and S n K below 2^36 keeps every byte offset and the scratch size below 2^40; K = 0 (a join without payload) counts as 1.  S and
+// K are bounded here too (32 bits of a mask word; 16 list slots), so the product below is under 2^40 whatever a caller passes.  Both
+// launchers and both scratch queries call it; like dedup's, no line in oracle/guards.py: tests/test_gpu_kfold.py walks the launchers' refusals)
+inline bool eval_subsets_fit(ll n, ll K, ll S) {
+    return n >= 0 && n < (1LL << 31) && K >= 0 && K <= 16 && S >= 1 && S <= 32 && S * n * (K > 0 ? K : 1) < (1LL << 36);
+}
+
 }  // namespace sg

@@ -200,10 +200,15 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error(MODEL_ERRORS_NEED_GEOCODE)
     if opt.model_errors is not None and opt.tonnage_errors:
         p.error(MODEL_ERRORS_OR_FILE)
+    if opt.evaluate_kfold is not None and opt.evaluate is None:
+        p.error(KFOLD_NEEDS_EVALUATE)
+    if opt.evaluate_kfold is not None and opt.tile_scenes and not opt.evaluate_kfold_images:
+        p.error(KFOLD_SCENES_NEED_IMAGES)
     if opt.evaluate is not None:
-        from .evaluate import grids_from_options
+        from .evaluate import check_kfold_options, grids_from_options
         try:
             grids_from_options(opt.evaluate_conf, opt.evaluate_eps, opt.evaluate_min_cages)
+            check_kfold_options(opt.evaluate_kfold, opt.evaluate_kfold_test)
         except ValueError as e:
             p.error(str(e))
     if opt.blank_geom is not None and opt.blank_key is None:
@@ -214,6 +219,9 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
 
 DEDUP_NEEDS_GEOCODE = "--dedup-years works on geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)"
 DEDUP_BY_PASS = "--dedup-years keeps one year per tile and image pass: with it --facilities needs --facilities-by pass, not year"
+KFOLD_NEEDS_EVALUATE = "--evaluate-kfold cross-validates the tuning grid of --evaluate: it needs --evaluate TRUTH_GEOJSON"
+KFOLD_SCENES_NEED_IMAGES = ("--evaluate-kfold with --tile-scenes: the tiles cut from the scenes are not listed anywhere after the sweep (a tile without "
+                            "a detection leaves no label file), so the image table needs --evaluate-kfold-images FILE (the tile names, one per line)")
 MODEL_ERRORS_NEED_GEOCODE = "--model-errors joins geocoded detections to the labels: it needs --geocode-bboxes CSV (and --save-txt --save-conf)"
 MODEL_ERRORS_OR_FILE = "the model errors of --tonnage come from --model-errors or from --tonnage-errors, not from both"
 
@@ -242,7 +250,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         jpeg_decode="auto", augment=False, save_crop=False, line_thickness=3, hide_labels=False, hide_conf=False, blank_key=None, blank_geom=None,
         blank_geom_simplify=0.5, facilities=None, facilities_conf=0.5, facilities_eps=10.0, facilities_min_cages=5, facilities_by="year",
         land_filter=None, ocean_out=None, evaluate=None, evaluate_out=None, evaluate_conf=None, evaluate_eps=None, evaluate_min_cages=None,
-        evaluate_images=None, tonnage=None, tonnage_factors=None, tonnage_errors=None, tonnage_depths=None, tonnage_default_depth=4.84,
+        evaluate_images=None, evaluate_kfold=None, evaluate_kfold_images=None, evaluate_known_sites=None, evaluate_kfold_seed=1,
+        evaluate_kfold_test=0.1, tonnage=None, tonnage_factors=None, tonnage_errors=None, tonnage_depths=None, tonnage_default_depth=4.84,
         tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, bathymetry=None, bathymetry_statistic="bathy_min", dedup_years=None,
         dedup_selection="random", dedup_seed=0, model_errors=None, model_errors_conf=None, model_errors_out=None, log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb_checked, jpeg_slots_to_rgb, JPEG_WS_MAX, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
@@ -267,6 +276,13 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         raise ValueError(MODEL_ERRORS_OR_FILE)
     if evaluate is not None and not geocode_bboxes:
         raise ValueError("--evaluate scores geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if evaluate_kfold is not None and evaluate is None:
+        raise ValueError(KFOLD_NEEDS_EVALUATE)
+    if evaluate_kfold is not None and tile_scenes and not evaluate_kfold_images:
+        raise ValueError(KFOLD_SCENES_NEED_IMAGES)
+    if evaluate_kfold is not None:
+        from .evaluate import check_kfold_options
+        check_kfold_options(evaluate_kfold, evaluate_kfold_test)
     if tonnage is not None and not geocode_bboxes:
         raise ValueError("--tonnage estimates from geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if tonnage is not None and not tonnage_factors:
@@ -1123,6 +1139,22 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 ev = aqeval.evaluate_table(table, evaluate, ev_out, *grids, op=(facilities_conf, facilities_eps, facilities_min_cages), keep=ocean,
                                            images=aqeval.read_image_list(evaluate_images) if evaluate_images else None)
                 log(f"{aqeval.describe(ev)} in {ev_out} in {time.perf_counter() - t_e:.2f}s")
+                if evaluate_kfold is not None:
+                    # the rest of that script: the image table (every image of the sweep, with or without a detection: the source's
+                    # listing, the same on every rank; with --tile-scenes the list --evaluate-kfold-images gives, which run() insists on),
+                    # the hold-out, the stratified folds, the grid per fold and the winners on the test images, all folds in one call per
+                    # distance
+                    from . import kfold as aqkfold
+                    t_k = time.perf_counter()
+                    swept = None
+                    if not tile_scenes:
+                        from .dataloader import list_images
+                        swept = sorted({aqeval._stem(f_) for f_ in list_images(source)})
+                    kf = aqeval.kfold_from_options(table, evaluate, ev_out, grids, (facilities_conf, facilities_eps, facilities_min_cages), ocean,
+                                                   aqeval.read_image_list(evaluate_images) if evaluate_images else None, evaluate_kfold,
+                                                   evaluate_kfold_images, evaluate_known_sites, evaluate_kfold_seed, evaluate_kfold_test,
+                                                   geocode_bboxes, names=swept)
+                    log(f"{aqkfold.describe(kf)} in {ev_out} in {time.perf_counter() - t_k:.2f}s")
             computed_errors = None
             if model_errors is not None:
                 # the model's cage-area error per pass and type (reference src/utils_tonnage.py:130-203) from the same table and the labels

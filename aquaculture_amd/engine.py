@@ -79,6 +79,7 @@ EXPORTS = (
     "aq_facility_scratch_bytes", "aq_facility_dbscan_f64",
     "aq_land_scratch_bytes", "aq_land_filter_f64",
     "aq_eval_scratch_bytes", "aq_eval_member_conf_f64", "aq_box_match_f64",
+    "aq_eval_subsets_scratch_bytes", "aq_eval_member_conf_subsets_f64", "aq_box_match_subsets_scratch_bytes", "aq_box_match_subsets_f64",
     "aq_model_error_match_f64", "aq_model_error_moments_f64",
     "aq_tonnage_simulate_f64", "aq_tonnage_reduce_f64", "aq_tonnage_ndtri_f64", "aq_tonnage_uniform_f64",
     "aq_depth_ranges_f64", "aq_depth_stats_f64",
@@ -151,6 +152,12 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_eval_scratch_bytes.restype = sz
     lib.aq_eval_member_conf_f64.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, C.c_double, i32, vp, sz, vp, vp]
     lib.aq_box_match_f64.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, vp, i32, vp, i32, vp, vp, vp]
+    lib.aq_eval_subsets_scratch_bytes.argtypes = [C.c_longlong, i32, i32]
+    lib.aq_eval_subsets_scratch_bytes.restype = sz
+    lib.aq_eval_member_conf_subsets_f64.argtypes = [vp, vp, vp, vp, vp, vp, C.c_longlong, C.c_double, i32, i32, vp, sz, vp, vp]
+    lib.aq_box_match_subsets_scratch_bytes.argtypes = [C.c_longlong, C.c_longlong, i32, i32]
+    lib.aq_box_match_subsets_scratch_bytes.restype = sz
+    lib.aq_box_match_subsets_f64.argtypes = [vp, vp, vp, C.c_longlong, vp, vp, C.c_longlong, vp, i32, vp, i32, i32, vp, vp, vp]
     lib.aq_model_error_match_f64.argtypes = [vp, vp, vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, i32, vp, vp, vp, vp]
     lib.aq_model_error_moments_f64.argtypes = [vp, vp, vp, C.c_longlong, C.c_longlong, vp, vp, vp, vp]
     lib.aq_tonnage_simulate_f64.argtypes = [C.c_ulonglong, C.c_longlong, C.c_longlong, vp, vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, i32,
@@ -1432,6 +1439,109 @@ def box_match(qbox: torch.Tensor, qgroup: torch.Tensor, kbox: torch.Tensor, kgro
         ev[2].synchronize()
         times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
     for t_ in (qbox, qgroup, kb, start, hit) + ((pl, out) if pl is not None else ()):
+        t_.record_stream(torch.cuda.current_stream())
+    return hit, out
+
+
+# ---- --evaluate-kfold: aq_eval_member_conf_subsets_f64 and aq_box_match_subsets_f64 (the same two steps for up to 32 subsets of the points) ----
+
+EVAL_MAX_S = 32
+
+
+def _subset_words(mask: torch.Tensor, n: int, what: str) -> torch.Tensor:
+    """A mask of subset bits as the int32 words the library reads as uint32 (torch has no arithmetic on uint32): int32, or int64 in [0, 2^32)."""
+    assert mask.is_cuda and mask.shape == (n,) and mask.dtype in (torch.int32, torch.int64), f"{what}: int32 or int64 CUDA [{n}]"
+    if mask.dtype == torch.int64:
+        mask = torch.where(mask >= (1 << 31), mask - (1 << 32), mask).to(torch.int32)     # bit 31 is the sign bit of the word
+    return mask.contiguous()
+
+
+def eval_member_conf_subsets(xy: torch.Tensor, group: torch.Tensor, conf: torch.Tensor, mask: torch.Tensor, eps: float, K: int, S: int,
+                             times: Optional[dict] = None) -> torch.Tensor:
+    """aq_eval_member_conf_subsets_f64 on the current stream: the arguments of eval_member_conf plus mask (int32 CUDA [n], read as uint32, or
+    int64 in [0, 2^32): bit s set = the point is in subset s) and S in 1 .. 32 -> M float64 CUDA [S, n, K]: M[s, i] = eval_member_conf's row of
+    point i among the points of subset s alone, -inf for a point outside s; evaluate.member_conf_subsets_numpy gives the same bytes.  One sort
+    (facility_sort_keys), one gather and one set of key runs for all subsets.  times = a dict that receives "sort_ms" and "kernel_ms"."""
+    _require_gpu()
+    lib = load_library()
+    assert xy.is_cuda and group.is_cuda and conf.is_cuda and xy.dtype == torch.float64 and group.dtype == torch.int32 and conf.dtype == torch.float64
+    xy, group, conf = xy.contiguous(), group.contiguous(), conf.contiguous()
+    n = xy.shape[0]
+    assert xy.shape == (n, 2) and group.shape == (n,) and conf.shape == (n,)
+    if not eps > 0 or not 1 <= int(K) <= EVAL_MAX_K or not 1 <= int(S) <= EVAL_MAX_S:        # the library refuses these too; here before the sort
+        raise ValueError(f"evaluate subsets: eps = {eps}, K = {K}, S = {S} (eps > 0, 1 <= K <= {EVAL_MAX_K} and 1 <= S <= {EVAL_MAX_S})")
+    words = _subset_words(mask, n, "mask")
+    M = torch.empty((int(S), n, int(K)), dtype=torch.float64, device=xy.device)
+    if n == 0:
+        _check(lib.aq_eval_member_conf_subsets_f64(None, None, None, None, None, None, 0, float(eps), int(K), int(S), None, 0, None, _stream_ptr()))
+        return M
+    need = int(lib.aq_eval_subsets_scratch_bytes(n, int(K), int(S)))
+    if need == 0:
+        raise ValueError(f"evaluate subsets: {n} points x {K} sizes x {S} subsets is more than one call takes")
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
+    if ev:
+        ev[0].record()
+    keys, perm = facility_sort_keys(xy, group, eps)
+    scratch = torch.empty(need, dtype=torch.uint8, device=xy.device)
+    if ev:
+        ev[1].record()
+    _check(lib.aq_eval_member_conf_subsets_f64(keys.data_ptr(), perm.data_ptr(), xy.data_ptr(), group.data_ptr(), conf.data_ptr(), words.data_ptr(), n,
+                                               float(eps), int(K), int(S), scratch.data_ptr(), scratch.numel(), M.data_ptr(), _stream_ptr()))
+    if ev:
+        ev[2].record()
+        ev[2].synchronize()
+        times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+    for t_ in (keys, perm, xy, group, conf, words, scratch, M):
+        t_.record_stream(torch.cuda.current_stream())
+    return M
+
+
+def box_match_subsets(qbox: torch.Tensor, qgroup: torch.Tensor, qmask: torch.Tensor, kbox: torch.Tensor, kgroup: torch.Tensor, kmask: torch.Tensor,
+                      G: int, S: int, payload: Optional[torch.Tensor] = None, times: Optional[dict] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """aq_box_match_subsets_f64 on the current stream: the arguments of box_match plus qmask [Q] and kmask [N] (subset words as in
+    eval_member_conf_subsets, the keys' in the caller's order) and S; payload float64 CUDA [S, N, K] or None -> (hitmask int32 CUDA [Q], the
+    uint32 word qmask & OR of the matching keys' kmask; out float64 CUDA [S, Q, K]: per subset the elementwise maximum of its payload over the
+    matching keys of that subset, -inf without one or for a query outside it -- None without a payload).
+    evaluate.box_match_subsets_numpy gives the same bytes.  times = a dict that receives "sort_ms" and "kernel_ms"."""
+    _require_gpu()
+    lib = load_library()
+    assert qbox.is_cuda and qbox.dtype == torch.float64 and kbox.dtype == torch.float64 and qgroup.dtype == torch.int32 and kgroup.dtype == torch.int32
+    qbox, qgroup = qbox.contiguous(), qgroup.contiguous()
+    Q, N, G, S = qbox.shape[0], kbox.shape[0], int(G), int(S)
+    assert qbox.shape == (Q, 4) and kbox.shape == (N, 4) and qgroup.shape == (Q,) and kgroup.shape == (N,)
+    if not 1 <= S <= EVAL_MAX_S:
+        raise ValueError(f"box match subsets: S = {S} subsets (1 to {EVAL_MAX_S})")
+    if G < 0 or (N and not (0 <= int(kgroup.min()) and int(kgroup.max()) < G)):
+        raise ValueError(f"box match subsets: the keys' group ids have to lie in [0, {G})")
+    qwords, kwords = _subset_words(qmask, Q, "qmask"), _subset_words(kmask, N, "kmask")
+    K = 0
+    if payload is not None:
+        assert payload.is_cuda and payload.dtype == torch.float64 and payload.ndim == 3 and payload.shape[:2] == (S, N)
+        K = payload.shape[2]
+        if not 1 <= K <= EVAL_MAX_K:
+            raise ValueError(f"box match subsets: {K} payload columns (1 to {EVAL_MAX_K})")
+    if lib.aq_box_match_subsets_scratch_bytes(Q, N, K, S) != 0:
+        raise ValueError(f"box match subsets: {Q} queries x {N} keys x {K} columns x {S} subsets is more than one call takes")
+    hit = torch.empty(Q, dtype=torch.int32, device=qbox.device)
+    out = torch.empty((S, Q, K), dtype=torch.float64, device=qbox.device) if payload is not None else None
+    if Q == 0:
+        return hit, out
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
+    if ev:
+        ev[0].record()
+    order, start = box_match_sort(kbox, kgroup, G)
+    kb, km = kbox[order].contiguous(), kwords[order].contiguous()
+    pl = payload[:, order].contiguous() if payload is not None else None
+    if ev:
+        ev[1].record()
+    _check(lib.aq_box_match_subsets_f64(qbox.data_ptr(), qgroup.data_ptr(), qwords.data_ptr(), Q, kb.data_ptr() if N else None, km.data_ptr() if N else None,
+                                        N, start.data_ptr(), G, pl.data_ptr() if pl is not None and N else None, K, S, hit.data_ptr(),
+                                        out.data_ptr() if out is not None else None, _stream_ptr()))
+    if ev:
+        ev[2].record()
+        ev[2].synchronize()
+        times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+    for t_ in (qbox, qgroup, qwords, kb, km, start, hit) + ((pl, out) if pl is not None else ()):
         t_.record_stream(torch.cuda.current_stream())
     return hit, out
 

@@ -32,8 +32,9 @@ Pinned against scikit-learn's DBSCAN per combination plus a brute-force join (th
     reproduced: row 0 matches like any other;
   * the reference drops the detections of images that lie wholly on land ("surely_land"); here the land filter's ocean rows are used when
     given (``keep``), box by box;
-  * its stratified folds need an image table the reference does not ship; ``images`` (``--evaluate-images``) restricts detections and labels
-    to a list of images, which is how it applies a fold.
+  * ``images`` (``--evaluate-images``) restricts detections and labels to a list of images, which is how the reference applies a fold; its
+    stratified folds themselves -- the image table, the hold-out, the folds, the winners on the test images -- are ``--evaluate-kfold``
+    (kfold.py, whose docstring lists what is not reproduced there: the land stratum among others).
 """
 from __future__ import annotations
 
@@ -473,6 +474,45 @@ def add_options(p: argparse.ArgumentParser) -> None:
     p.add_argument("--evaluate-eps", default=None, metavar="GRID", help="DBSCAN distances in metres, the same forms (default 10:151:20)")
     p.add_argument("--evaluate-min-cages", default=None, metavar="GRID", help=f"minimum cluster sizes, the same forms, whole numbers up to {MAX_K} (default 1:11:1)")
     p.add_argument("--evaluate-images", default=None, metavar="FILE", help="image names, one per line: detections and labels of other images are left out (a fold)")
+    p.add_argument("--evaluate-kfold", nargs="?", const=5, default=None, type=int, metavar="N",
+                   help="cross-validate the tuning as the reference does (src/get_kfold_cluster_performance.py): a stratified image table, a hold-out, "
+                        "N stratified folds (a bare flag: 5), the grid on every fold's train images -- all folds in one GPU call per distance --, "
+                        f"the winners on its test images; writes {KFOLD_FILES[0]}, {KFOLD_FILES[1]} and {KFOLD_FILES[2]} beside the other two files; 2 to 15")
+    p.add_argument("--evaluate-kfold-images", default=None, metavar="FILE",
+                   help="the images of the cross-validation's table, one name per line, in this order (default: every image of the sweep, or of the "
+                        "label directory and the truth, sorted by name; required with --tile-scenes, whose tiles are listed nowhere)")
+    p.add_argument("--evaluate-known-sites", default=None, metavar="CSV",
+                   help="known sites (columns lat, lon; the reference's data/aquaculture_med_dedupe.csv): images without a detection are stratified by "
+                        "whether they meet the +-1000 m box of one")
+    p.add_argument("--evaluate-kfold-seed", default=1, type=int, metavar="SEED", help="random_state of the hold-out and of the folds (default 1, the reference's)")
+    p.add_argument("--evaluate-kfold-test", default=0.1, type=float, metavar="FRACTION", help="share of the images set aside before the folds (default 0.1; 0: none)")
+
+
+KFOLD_FILES = ("kfold_results.csv", "kfold_images.csv", "kfold.json")      # kfold.RESULTS_FILE, IMAGES_FILE, JSON_FILE
+
+
+def check_kfold_options(n_splits, test_frac) -> None:
+    """What the command lines refuse before any work: a fold count outside 2 .. 15 (2 N + 2 subset bits in a 32-bit word) and a hold-out
+    fraction outside [0, 1)."""
+    if n_splits is not None and not 2 <= int(n_splits) <= 15:
+        raise ValueError(f"--evaluate-kfold {n_splits}: 2 to 15 folds")
+    if not 0 <= float(test_frac) < 1:
+        raise ValueError(f"--evaluate-kfold-test {test_frac}: a fraction in [0, 1)")
+
+
+def kfold_from_options(table, truth_path: str, out_dir: str, grids, op, keep, images, n_splits: int, kfold_images: Optional[str], known_sites: Optional[str],
+                       seed: int, test_frac: float, wanted_bboxes_csv: Optional[str], names: Optional[Sequence[str]] = None, cpu: bool = False) -> dict:
+    """The cross-validation as both command lines run it: names = the images of the table when --evaluate-kfold-images gives none (None: those
+    with a detection or a label)."""
+    from . import kfold as aqkfold
+    if kfold_images:
+        names = read_image_list(kfold_images)
+    sites = aqkfold.load_known_sites(known_sites) if known_sites else None
+    if sites is not None and not wanted_bboxes_csv:
+        raise ValueError("--evaluate-known-sites needs the images' rectangles: --geocode-bboxes CSV")
+    rects = aqkfold.tile_rects(wanted_bboxes_csv) if sites is not None else None
+    return aqkfold.kfold(table, load_truth_geojson(truth_path), out_dir, n_splits, names=names, rects=rects, sites=sites, seed=seed, test_frac=test_frac,
+                         conf_grid=grids[0], eps_grid=grids[1], min_grid=grids[2], op=op, keep=keep, images=images, cpu=cpu)
 
 
 def grids_from_options(conf: Optional[str], eps: Optional[str], min_cages: Optional[str]):
@@ -493,6 +533,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     opt = p.parse_args(argv)
     try:
         grids = grids_from_options(opt.evaluate_conf, opt.evaluate_eps, opt.evaluate_min_cages)
+        check_kfold_options(opt.evaluate_kfold, opt.evaluate_kfold_test)
     except ValueError as e:
         p.error(str(e))
     out_dir = opt.evaluate_out or os.path.dirname(os.path.abspath(opt.labels.rstrip("/")))
@@ -505,7 +546,16 @@ def main(argv: Optional[List[str]] = None) -> int:
     s = evaluate_table(table, opt.truth, out_dir, *grids, op=(opt.facilities_conf, opt.facilities_eps, opt.facilities_min_cages),
                        keep=keep, images=images, cpu=opt.cpu)
     print(describe(s) + f" in {out_dir}")
+    if opt.evaluate_kfold is not None:
+        from . import kfold as aqkfold
+        k = kfold_from_options(table, opt.truth, out_dir, grids, (opt.facilities_conf, opt.facilities_eps, opt.facilities_min_cages), keep, images,
+                               opt.evaluate_kfold, opt.evaluate_kfold_images, opt.evaluate_known_sites, opt.evaluate_kfold_seed, opt.evaluate_kfold_test,
+                               opt.geocode_bboxes, cpu=opt.cpu)
+        print(aqkfold.describe(k) + f" in {out_dir}")
     return 0
+
+
+from .kfold import box_match_subsets_numpy, cross_validate, kfold, member_conf_subsets_numpy      # noqa: E402  (kfold.py reads this module's names when called)
 
 
 if __name__ == "__main__":

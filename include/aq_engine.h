@@ -658,6 +658,38 @@ int aq_eval_member_conf_f64(const long long* keys_sorted_dev, const int32_t* per
 int aq_box_match_f64(const double* qbox_dev, const int32_t* qgroup_dev, long long Q, const double* kbox_dev, long long N,
                      const int32_t* group_start_dev, int G, const double* payload_dev, int K, uint8_t* hit_dev, double* out_dev, void* stream);
 
+/* ---- --evaluate-kfold (eval_subsets.hip): the two steps above for up to 32 subsets of one point set in one call (the folds of the reference's
+ * StratifiedKFold).  A subset is one bit of a uint32 word per point: point i belongs to subset s (0 <= s < S) iff bit s of its word is set;
+ * bits at and above S are ignored.
+ * aq_eval_member_conf_subsets_f64: the arguments of aq_eval_member_conf_f64 plus mask_dev ([n] uint32, original order) and S in 1 .. 32.
+ * member_conf_dev (doubles [S][n][K]): row [s][i] = what aq_eval_member_conf_f64 gives point i when only the points of subset s exist, that is
+ *   T_s(i, m) = min(c_i, m-th largest confidence among the points of s within eps of i)     (-inf: fewer than m)
+ *   M_s(i, m) = min(c_i, max over the points j of s within eps of i of T_s(j, m))
+ * for i in s; a row of a point outside s is -inf.  Every value is one of the inputs, bit for bit, or -inf. */
+/* Scratch: 52 + 8 K S bytes per point (coordinates, key runs, confidences and mask words in sorted order, the core thresholds of every subset),
+ * each array rounded up to 16 bytes; 0 for n <= 0, K outside 1 .. 16, S outside 1 .. 32, n >= 2^31 or S n K >= 2^36. */
+size_t aq_eval_subsets_scratch_bytes(long long n, int K, int S);
+/* On `stream`; one gather and one set of key runs for all subsets; the call initialises what it reads of its scratch, allocates nothing and
+ * uses no atomics, so two calls give the same bytes.  n = 0 does nothing.  S outside 1 .. 32, K outside 1 .. 16, n >= 2^31, S n K >= 2^36,
+ * eps <= 0 (or not finite), a null pointer, an unaligned array and too little scratch are refused before anything is launched.  Keys and a
+ * perm_dev the caller got wrong give wrong values but no access outside the arrays; the rows of an entry of perm_dev outside [0, n) stay
+ * unwritten. */
+int aq_eval_member_conf_subsets_f64(const long long* keys_sorted_dev, const int32_t* perm_dev, const double* xy_dev, const int32_t* group_dev,
+                                    const double* conf_dev, const uint32_t* mask_dev, long long n, double eps, int K, int S,
+                                    void* scratch_dev, size_t scratch_bytes, double* member_conf_dev, void* stream);
+/* aq_box_match_subsets_f64: the arguments of aq_box_match_f64 plus qmask_dev ([Q] uint32), kmask_dev ([N] uint32, in the keys' sorted order) and
+ * S in 1 .. 32; payload_dev is [S][N][K] doubles (keys in sorted order) or null with K = 0.  hitmask_dev[q] (uint32) = qmask[q] & the OR of
+ * kmask[k] over the keys k of q's group whose closed boxes meet q's (bits at and above S cleared): bit s says that q is in subset s and meets
+ * a key of subset s.  With a payload, out_dev[s][q][m] (doubles [S][Q][K]) = the maximum of payload[s][k][m] over the matching keys k that have
+ * bit s, -inf when there is none or when q is not in s.  On `stream`, no atomics, one launch, every output element written; Q = 0 does
+ * nothing.  S or K out of range, Q or N >= 2^31, S Q K or S N K >= 2^36, G < 0, a null pointer and an unaligned array (boxes 32 bytes, doubles
+ * 8, words 4) are refused before anything is launched; group starts are kept inside [0, N] on the device. */
+/* Scratch of the join: none (0 bytes); (size_t)-1 for sizes the launcher refuses, so that a caller can ask before it allocates outputs. */
+size_t aq_box_match_subsets_scratch_bytes(long long Q, long long N, int K, int S);
+int aq_box_match_subsets_f64(const double* qbox_dev, const int32_t* qgroup_dev, const uint32_t* qmask_dev, long long Q, const double* kbox_dev,
+                             const uint32_t* kmask_dev, long long N, const int32_t* group_start_dev, int G, const double* payload_dev, int K, int S,
+                             uint32_t* hitmask_dev, double* out_dev, void* stream);
+
 /* ---- --model-errors (model_errors.hip): the cage-area error distributions (reference src/utils_tonnage.py:130-203, :284-327) ----
  * aq_model_error_match_f64: the queries, sorted keys and group starts of aq_box_match_f64, with qarea_dev [Q] (the queries' areas), krow_dev [N]
  * (the original row number of each sorted key; rows are distinct and >= 0, a negative one is skipped) and karea_dev [N] (the keys' areas, in
