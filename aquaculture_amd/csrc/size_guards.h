@@ -112,6 +112,12 @@ inline bool dedup_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }
 inline bool dedup_frame_fits(ll w, ll h) { return w >= 1 && h >= 1 && w <= kDedupMaxSide && h <= kDedupMaxSide; }
 constexpr ll dedup_pitch(ll w) { return cdiv(w + 1, 32); }  // words of a bitmap row: w pixels and the column x = w of the toggles
 
+// ---- coverage.hip ----  (images, ring vertices, band entries, queries and passes of a call are 31-bit indices -- ring_start holds the vertex
+// offsets as int32 -- and band_start has P nbands + 1 entries; like dedup's, no line in oracle/guards.py: tests/test_gpu_missing.py walks the
+// edges through the launcher's refusals)
+inline bool coverage_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }
+inline bool coverage_bands_fit(ll P, ll nbands) { return P >= 0 && nbands >= 1 && nbands < (1LL << 31) && P * nbands + 1 < (1LL << 31); }
+
 // ---- model_errors.hip ----  (queries, keys and moment groups of a call are 31-bit indices; like dedup's, no line in oracle/guards.py:
 // tests/test_gpu_model_errors.py walks the edge through the launchers' refusals)
 inline bool model_error_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }

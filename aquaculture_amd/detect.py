@@ -180,6 +180,16 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error(DEDUP_BY_PASS)
     if opt.dedup_years is not None and opt.blank_geom is None:
         opt.blank_geom = ""
+    if opt.tonnage_missing is not None and (opt.tonnage is None or opt.dedup_years is None):
+        p.error(MISSING_NEEDS_TONNAGE_DEDUP)
+    if opt.tonnage_missing is not None:
+        from .missing import parse_map
+        try:
+            parse_map(opt.tonnage_missing)
+        except ValueError as e:
+            p.error(str(e))
+    if opt.tonnage_near_sites and opt.tonnage is None:
+        p.error(NEAR_SITES_NEED_TONNAGE)
     if opt.bathymetry and not opt.geocode_bboxes:
         p.error("--bathymetry takes the depth under geocoded facilities: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if opt.bathymetry and opt.tonnage is None and opt.facilities is None:
@@ -219,6 +229,9 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
 
 DEDUP_NEEDS_GEOCODE = "--dedup-years works on geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)"
 DEDUP_BY_PASS = "--dedup-years keeps one year per tile and image pass: with it --facilities needs --facilities-by pass, not year"
+MISSING_NEEDS_TONNAGE_DEDUP = ("--tonnage-missing adds the facilities outside a pass's imagery to the estimates of --tonnage, from the key, the outlines "
+                               "and the cage_ids_min / cage_ids_max of --dedup-years: it needs both")
+NEAR_SITES_NEED_TONNAGE = "--tonnage-near-sites estimates the production near the known sites with the bootstrap of --tonnage: it needs --tonnage"
 KFOLD_NEEDS_EVALUATE = "--evaluate-kfold cross-validates the tuning grid of --evaluate: it needs --evaluate TRUTH_GEOJSON"
 KFOLD_SCENES_NEED_IMAGES = ("--evaluate-kfold with --tile-scenes: the tiles cut from the scenes are not listed anywhere after the sweep (a tile without "
                             "a detection leaves no label file), so the image table needs --evaluate-kfold-images FILE (the tile names, one per line)")
@@ -253,7 +266,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         evaluate_images=None, evaluate_kfold=None, evaluate_kfold_images=None, evaluate_known_sites=None, evaluate_kfold_seed=1,
         evaluate_kfold_test=0.1, tonnage=None, tonnage_factors=None, tonnage_errors=None, tonnage_depths=None, tonnage_default_depth=4.84,
         tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, bathymetry=None, bathymetry_statistic="bathy_min", dedup_years=None,
-        dedup_selection="random", dedup_seed=0, model_errors=None, model_errors_conf=None, model_errors_out=None, log=print, **unsupported):
+        dedup_selection="random", dedup_seed=0, model_errors=None, model_errors_conf=None, model_errors_out=None, tonnage_missing=None,
+        tonnage_near_sites=None, log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb_checked, jpeg_slots_to_rgb, JPEG_WS_MAX, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     if dedup_years is not None and not geocode_bboxes:
@@ -262,6 +276,13 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         raise ValueError(DEDUP_BY_PASS)
     if dedup_years is not None and dedup_selection not in ("random", "min", "max"):
         raise ValueError(f"--dedup-selection {dedup_selection!r}: random, min or max")
+    if tonnage_missing is not None and (tonnage is None or dedup_years is None):
+        raise ValueError(MISSING_NEEDS_TONNAGE_DEDUP)
+    if tonnage_near_sites and tonnage is None:
+        raise ValueError(NEAR_SITES_NEED_TONNAGE)
+    if tonnage_missing is not None:
+        from .missing import parse_map
+        parse_map(tonnage_missing)
     if dedup_years is not None and blank_geom is None:   # the masks of the partly blank images are their outlines
         blank_geom = ""
     if blank_geom is not None and blank_key is None:     # the outlines are made for the images the key calls partly blank
@@ -1170,12 +1191,16 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 # the reference's measuring step (src/utils_tonnage.py): facilities per image pass whatever --facilities-by says (the
                 # facility file above stays as it is), the ocean rows when there are any
                 from . import tonnage as aqton
+                from . import missing as aqmiss
                 t_t = time.perf_counter()
                 ton_out = tonnage or str(save_dir)
                 est = aqton.tonnage_from_table(table, ton_out, tonnage_factors, tonnage_errors, tonnage_depths, tonnage_K, tonnage_seed, tonnage_mix,
                                                tonnage_min_depth, tonnage_default_depth, facilities_conf, facilities_eps, facilities_min_cages,
                                                hw[table["image"], 1], hw[table["image"], 0], keep=ocean, bathymetry=bathy, dedup=dd,
-                                               **({"errors": computed_errors} if computed_errors is not None else {}))
+                                               **({"errors": computed_errors} if computed_errors is not None else {}),
+                                               **({"missing": aqmiss.settings(tonnage_missing, key_out, geom_out, geocode_bboxes)}
+                                                  if tonnage_missing is not None else {}),
+                                               **({"near_sites": tonnage_near_sites} if tonnage_near_sites else {}))
                 log(f"tonnage: {aqton.describe(est)} in {ton_out} in {time.perf_counter() - t_t:.2f}s")
     manifest.close()
     eng.close()

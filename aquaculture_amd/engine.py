@@ -84,6 +84,7 @@ EXPORTS = (
     "aq_tonnage_simulate_f64", "aq_tonnage_reduce_f64", "aq_tonnage_ndtri_f64", "aq_tonnage_uniform_f64",
     "aq_depth_ranges_f64", "aq_depth_stats_f64",
     "aq_dedup_fill_u32", "aq_dedup_sets_u32", "aq_dedup_select_f64",
+    "aq_coverage_first_i32",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -234,6 +235,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_dedup_fill_u32.argtypes = [vp, C.c_longlong, vp, vp, vp, vp, C.c_longlong, vp, C.c_longlong, vp]
     lib.aq_dedup_sets_u32.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, vp]
     lib.aq_dedup_select_f64.argtypes = [vp, vp, vp, vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp]
+    lib.aq_coverage_first_i32.argtypes = [vp, vp, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, vp, vp, vp, C.c_longlong, C.c_longlong,
+                                          vp, vp, C.c_longlong, vp, sz, vp, vp]
     lib.aq_augment_geometry.argtypes = [i32, i32, i32, vp, C.POINTER(i32)]
     lib.aq_augment_taps.argtypes = [i32, i32, i32, vp]
     lib.aq_stem_conv_scaled.argtypes = [vp, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]
@@ -1811,6 +1814,52 @@ def dedup_select(group: torch.Tensor, cage_start: torch.Tensor, cage: torch.Tens
     for t_ in (group, cage_start, cage, words, area, random_order, sel, chosen, sums):
         t_.record_stream(torch.cuda.current_stream())
     return sel, chosen, sums
+
+
+# ---- --tonnage-missing: aq_coverage_first_i32 (boxes against the union of a pass's image regions) ----
+
+def _coverage_tensor(name: str, t_: torch.Tensor, dt, shape) -> None:
+    if not t_.is_cuda or t_.dtype != dt or not t_.is_contiguous() or t_.ndim != len(shape) or any(b is not None and a != b for a, b in zip(t_.shape, shape)):
+        raise ValueError(f"coverage: {name} has to be a contiguous CUDA {dt} tensor of shape {shape}, not {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+
+
+def coverage_first(rect: torch.Tensor, ring_start: torch.Tensor, xy: torch.Tensor, entry_img: torch.Tensor, band_start: torch.Tensor,
+                   band: torch.Tensor, nbands: int, box: torch.Tensor, qpass: torch.Tensor, ring_start_host: np.ndarray,
+                   band_start_host: np.ndarray, band_host: np.ndarray, times: Optional[dict] = None) -> torch.Tensor:
+    """aq_coverage_first_i32 on the current stream: rect float64 CUDA [I, 4] (west, south, east, north), ring_start int32 CUDA [I + 1], xy
+    float64 CUDA [V, 2], entry_img int32 CUDA [entries], band_start int32 CUDA [P nbands + 1], band float64 CUDA [P, 2] (Y0, h), box
+    float64 CUDA [Q, 4], qpass int32 CUDA [Q]; the *_host arrays hold the same tables in host memory -> first int32 CUDA [Q].
+    include/aq_engine.h states the contract; missing.first_numpy gives the same bytes.  times = a dict that receives "kernel_ms" (HIP
+    events; the call then waits for them)."""
+    _require_gpu()
+    I, V, entries, P, Q = int(ring_start.shape[0]) - 1, int(xy.shape[0]), int(entry_img.shape[0]), int(band.shape[0]), int(box.shape[0])
+    nbands = int(nbands)
+    if I < 0 or nbands < 1:
+        raise ValueError(f"coverage: ring_start of {I + 1} entries, nbands = {nbands}")
+    for name, t_, dt, shape in (("rect", rect, torch.float64, (I, 4)), ("ring_start", ring_start, torch.int32, (I + 1,)), ("xy", xy, torch.float64, (V, 2)),
+                                ("entry_img", entry_img, torch.int32, (entries,)), ("band_start", band_start, torch.int32, (P * nbands + 1,)),
+                                ("band", band, torch.float64, (P, 2)), ("box", box, torch.float64, (Q, 4)), ("qpass", qpass, torch.int32, (Q,))):
+        _coverage_tensor(name, t_, dt, shape)
+    rs, bs = np.ascontiguousarray(ring_start_host, dtype=np.int32), np.ascontiguousarray(band_start_host, dtype=np.int32)
+    bh = np.ascontiguousarray(band_host, dtype=np.float64)
+    if rs.shape != (I + 1,) or bs.shape != (P * nbands + 1,) or bh.shape != (P, 2):
+        raise ValueError("coverage: the host copies do not have the device tables' shapes")
+    first = torch.empty(Q, dtype=torch.int32, device=box.device)
+    scratch = torch.empty(entries * 32, dtype=torch.uint8, device=box.device)
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if times is not None else None
+    if ev:
+        ev[0].record()
+    _check(load_library().aq_coverage_first_i32(ptr(rect), ptr(ring_start), rs.ctypes.data, I, ptr(xy), V, ptr(entry_img), entries, ptr(band_start),
+                                                bs.ctypes.data, ptr(band), bh.ctypes.data if P else None, P, nbands, ptr(box), ptr(qpass), Q,
+                                                ptr(scratch), scratch.numel(), ptr(first), _stream_ptr()))
+    if ev:
+        ev[1].record()
+        ev[1].synchronize()
+        times["kernel_ms"] = times.get("kernel_ms", 0.0) + ev[0].elapsed_time(ev[1])
+    for t_ in (rect, ring_start, xy, entry_img, band_start, band, box, qpass, scratch, first):
+        t_.record_stream(torch.cuda.current_stream())
+    return first
 
 
 # ---- --land-filter: aq_land_filter_f64 (detection boxes against the segments of the land polygons) ----

@@ -441,14 +441,17 @@ def estimate(fac, areas, table, factors, errors=None, depths=None, K: int = 1000
 ESTIMATES_FILE, FACILITIES_FILE, JSON_FILE = "tonnage_estimates.csv", "tonnage_facilities.csv", "tonnage.json"
 
 
-def write_files(out_dir: str, est: dict, params: dict) -> None:
+def write_files(out_dir: str, est: dict, params: dict, more_rows: Sequence[Tuple[str, str, float, float]] = ()) -> None:
     """tonnage_estimates.csv (the columns of the reference's tonnage_estimates_combined.csv), tonnage_facilities.csv and tonnage.json;
-    numbers by ``repr``, so the files of two runs compare byte for byte."""
+    numbers by ``repr``, so the files of two runs compare byte for byte.  more_rows: (source, pass, tonnage, tonnage_sd) rows that follow
+    the ``Model`` rows (--tonnage-missing)."""
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, ESTIMATES_FILE), "w") as f:
         f.write("source,pass,tonnage,tonnage_sd\n")
         for p, m, s in zip(est["pass"], est["tonnage"], est["tonnage_sd"]):
             f.write(f"Model,{p},{m!r},{s!r}\n")
+        for source, p, m, s in more_rows:
+            f.write(f"{source},{p},{m!r},{s!r}\n")
     with open(os.path.join(out_dir, FACILITIES_FILE), "w") as f:
         f.write("facility_index,pass,cages,tonnage,tonnage_sd\n")
         for row in zip(est["facility_index"], est["facility_pass"], est["facility_cages"], est["facility_tonnage"], est["facility_tonnage_sd"]):
@@ -462,12 +465,20 @@ def tonnage_from_table(table, out_dir: str, factors_path: str, errors_path: Opti
                        K: int = 10000, seed: int = 0, mix: float = 0.5, min_depth: float = DEFAULT_MIN_DEPTH, default_depth: float = DEFAULT_DEPTH,
                        conf_thresh: float = 0.5, eps: float = 10.0, min_cages: int = 5, widths=geocode.IM_WIDTH, heights=geocode.IM_HEIGHT,
                        cpu: bool = False, keep=None, bathymetry: Optional[dict] = None, dedup: Optional[dict] = None,
-                       errors: Optional[Dict[Tuple[str, str], Tuple[float, float]]] = None) -> dict:
+                       errors: Optional[Dict[Tuple[str, str], Tuple[float, float]]] = None, missing: Optional[dict] = None,
+                       near_sites: Optional[str] = None) -> dict:
     """Facilities per image pass (facilities.cluster), their estimates and the three files in `out_dir`.  errors = read_errors' table made
     in this process instead of a file (model_errors.distributions' ``errors``); tonnage.json records it as it records a file's.  bathymetry (bathymetry.settings'
     result, instead of a depths file): the facilities' cage depths come from the depth raster and are written to facility_depths.csv
     beside the three files, in the form `depths_path` takes.  dedup (dedup.dedup_from_table's result, made with the same conf_thresh and
-    keep): the survivors of its selection are clustered, and cage_ids_min / cage_ids_max widen the area bounds as the reference's do."""
+    keep): the survivors of its selection are clustered, and cage_ids_min / cage_ids_max widen the area bounds as the reference's do.
+    missing (missing.settings' result; needs dedup): per current pass of its map the facilities of the compare pass that lie outside the
+    pass's imagery are added (missing.impute), the imputed table gets one more simulation with the same K and seed, and the rows
+    ``Model + Estimate missing`` follow the ``Model`` rows, which stay what they are without it; tonnage_missing_cages.csv and
+    tonnage_missing_facilities.csv say why.  near_sites (the known sites' CSV): a further simulation of the facilities cut to the cages
+    within 1 km of a site, in tonnage_near_sites.csv."""
+    if missing is not None and dedup is None:
+        raise ValueError(MISSING_NEEDS_DEDUP)
     if bathymetry is not None and depths_path:
         raise ValueError("tonnage: cage depths come from --bathymetry or from --tonnage-depths, not from both")
     if errors is not None and errors_path:
@@ -486,9 +497,22 @@ def tonnage_from_table(table, out_dir: str, factors_path: str, errors_path: Opti
         cols = aqbathy.depths_of(fac, table, dict(bathymetry, default_depth=float(default_depth), min_depth=float(min_depth)), cpu=cpu)
         depths = {int(fi): float(d) for fi, d in zip(fac["facility_index"], cols["cage_depth"])}
         os.makedirs(out_dir, exist_ok=True)
-        missing = aqbathy.write_depths_csv(os.path.join(out_dir, aqbathy.DEPTHS_FILE), fac, cols, "pass")
-        extra = {"bathymetry": {**aqbathy.describe_settings(bathymetry), "default_depth_facilities": missing}}
+        defaulted = aqbathy.write_depths_csv(os.path.join(out_dir, aqbathy.DEPTHS_FILE), fac, cols, "pass")
+        extra = {"bathymetry": {**aqbathy.describe_settings(bathymetry), "default_depth_facilities": defaulted}}
     est = estimate(fac, None, table, factors, errors, depths, K, seed, mix, min_depth, cpu, default_depth)
+    more_rows = []
+    if missing is not None or near_sites:
+        from . import missing as aqmiss
+        again = lambda cut: estimate(cut, None, table, factors, errors, depths, K, seed, mix, min_depth, cpu, default_depth)
+        if missing is not None:
+            res = aqmiss.missing_estimates(fac, table, missing, again, out_dir, cpu)
+            more_rows = [(aqmiss.SOURCE, *row) for row in res["rows"]]
+            extra = {**extra, "missing": res["json"]}
+            est["missing"] = res
+        if near_sites:
+            res = aqmiss.near_estimates(fac, table, near_sites, again, out_dir, cpu)
+            extra = {**extra, "near_sites": res["json"]}
+            est["near_sites"] = res
     device = "cpu"
     if not cpu:
         import torch
@@ -497,13 +521,21 @@ def tonnage_from_table(table, out_dir: str, factors_path: str, errors_path: Opti
                                "factors": {p: list(v) for p, v in sorted(factors.items())},
                                "errors": [[*k, *v] for k, v in sorted((errors or {}).items())], "depths_file": bool(depths_path),
                                "facilities_conf": float(conf_thresh), "facilities_eps": float(eps), "facilities_min_cages": int(min_cages), **extra,
-                               **({"dedup_years": {"selection": dedup["selection"]}} if dedup is not None else {})})
+                               **({"dedup_years": {"selection": dedup["selection"]}} if dedup is not None else {})}, more_rows)
     return est
 
 
 def describe(est: dict) -> str:
-    return f"{len(est['facility_index'])} facilities, {len(est['pass'])} passes, K = {est['K']}: " + \
+    text = f"{len(est['facility_index'])} facilities, {len(est['pass'])} passes, K = {est['K']}: " + \
         ", ".join(f"{p} {m:.1f} t (sd {s:.1f})" for p, m, s in zip(est["pass"], est["tonnage"], est["tonnage_sd"]))
+    if "missing" in est:
+        text += "; with missing imagery: " + ", ".join(f"{p} {m:.1f} t (sd {s:.1f}; {est['missing']['json']['passes'][p]['own']} + "
+                                                        f"{est['missing']['json']['passes'][p]['added']} facilities)" for p, m, s in est["missing"]["rows"])
+    return text
+
+
+MISSING_NEEDS_DEDUP = ("--tonnage-missing fills a pass's missing imagery from the sweep's blank key and outlines and the facilities' "
+                       "cage_ids_min / cage_ids_max: it needs --dedup-years")
 
 
 def add_options(p: argparse.ArgumentParser) -> None:
@@ -516,6 +548,13 @@ def add_options(p: argparse.ArgumentParser) -> None:
     p.add_argument("--tonnage-K", type=int, default=10000, metavar="K", help="simulations of the bootstrap")
     p.add_argument("--tonnage-seed", type=int, default=0, metavar="SEED", help="64-bit seed (the Philox key)")
     p.add_argument("--tonnage-mix", type=float, default=0.5, metavar="P", help="probability of the shallow depth distribution (reference depth_dist_mixture_param)")
+    p.add_argument("--tonnage-missing", nargs="?", const="", default=None, metavar="CUR=CMP[,CUR=CMP...]",
+                   help="add the rows 'Model + Estimate missing' to tonnage_estimates.csv: per current pass the facilities of the compare pass whose cages "
+                        "lie outside the current pass's imagery are added (the reference's compute_complete_period_tonnage_estimates; the box-against-"
+                        "coverage test on the GPU); default map: the reference's period_comparison_dict; needs --tonnage and --dedup-years")
+    p.add_argument("--tonnage-near-sites", default=None, metavar="CSV",
+                   help="also estimate the production of the cages within 1 km of a known site (columns lat, lon; the reference's "
+                        "trujillo_comparison) and write tonnage_near_sites.csv; needs --tonnage")
 
 
 def main(argv: Optional[List[str]] = None) -> int:
@@ -541,6 +580,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         p.error("--tonnage-factors FILE is needed")
     if opt.bathymetry and opt.tonnage_depths:
         p.error("cage depths come from --bathymetry or from --tonnage-depths, not from both")
+    miss = None
+    if opt.tonnage_missing is not None:
+        from . import missing as aqmiss
+        if not opt.dedup_years:
+            p.error(MISSING_NEEDS_DEDUP)
+        try:
+            miss = aqmiss.settings(opt.tonnage_missing, opt.dedup_years[0], opt.dedup_years[1], opt.geocode_bboxes)
+        except ValueError as e:
+            p.error(str(e))
     out = opt.out or os.path.dirname(os.path.abspath(opt.labels.rstrip("/")))
     table = geocode.geocode_label_dir(opt.labels, opt.geocode_bboxes)
     keep = None
@@ -555,7 +603,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                                       opt.image_size[0], opt.image_size[1], cpu=opt.cpu)
     est = tonnage_from_table(table, out, opt.tonnage_factors, opt.tonnage_errors, opt.tonnage_depths, opt.tonnage_K, opt.tonnage_seed, opt.tonnage_mix,
                              opt.tonnage_min_depth, opt.tonnage_default_depth, opt.facilities_conf, opt.facilities_eps, opt.facilities_min_cages,
-                             opt.image_size[0], opt.image_size[1], cpu=opt.cpu, keep=keep, bathymetry=bathy, dedup=dd)
+                             opt.image_size[0], opt.image_size[1], cpu=opt.cpu, keep=keep, bathymetry=bathy, dedup=dd, missing=miss,
+                             near_sites=opt.tonnage_near_sites)
     print(f"{describe(est)} in {out}")
     return 0
 

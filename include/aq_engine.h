@@ -866,6 +866,40 @@ int aq_dedup_select_f64(const int32_t* group_dev, const int32_t* group_host, con
                         long long G, const int32_t* cage_dev, const uint32_t* words_dev, const double* area_dev, long long C,
                         const int32_t* random_order_dev, uint8_t* sel_dev, int32_t* chosen_dev, double* sums_dev, void* stream);
 
+/* ---- --tonnage-missing / --tonnage-near-sites: does a closed box meet a union of image regions (csrc/coverage.hip) ----
+ * The reference's modify_cage_list_using_geometry (src/utils_tonnage.py:1108-1136): cage.intersects(the union of a pass's image polygons).
+ * Definitions:
+ *   image region   an image takes part under the rule of aquaculture_amd.dedup.build_problem -- status `complete`, or `partly blank` with a
+ *                  ring in the blank-geom file -- if its name parses to a bbox_ind the wanted-bboxes table lists.  Its rectangle is
+ *                  blank_geom.tile_bounds(name, wanted) = (west, south, east, north), EPSG:3857, fp64.  Complete image: the closed
+ *                  rectangle.  Partly blank image: the closed even-odd region of the ring blank_geom.to_bounds(ring_px, west, south, east,
+ *                  north), the vertices computed on the host in numpy by that expression, so both ends of a vertical segment hold the same
+ *                  double; the kernel receives metres and only compares.
+ *   coverage of p  the union of the regions of the images whose year maps to pass p; it does not depend on the de-duplication order.
+ *   meets(B, i)    for a closed box B = (x0, y0, x1, y1).  Rectangle image: x0 <= east && x1 >= west && y0 <= north && y1 >= south.
+ *                  Ring image: its rectangle meets B and (some segment's closed bounding box overlaps B -- the segments are axis-parallel,
+ *                  so the segment meets B -- or an odd number of segments have (ay <= y0) != (by <= y0) && ax > x0: the corner (x0, y0)
+ *                  strictly inside; the parity only decides when no segment meets B).  A box with a NaN meets nothing.
+ *   first[q]       for query q = (box, target pass): the smallest image number of that pass whose region meets the box, or -1.  Images
+ *                  are numbered in the host's order, sorted by (pass, image name).  Covered: first >= 0.
+ * Everything is comparisons and integer minima: aquaculture_amd.missing.first_numpy gives the same bytes, and so do two launches.
+ * Arrays: rect_dev [I][4] fp64 (32-byte aligned); ring_start [I + 1] int32, image i a ring image iff ring_start[i + 1] > ring_start[i], its
+ * closed walk (first vertex repeated at the end) xy_dev [ring_start[i] .. ring_start[i + 1])[2] fp64 (16-byte aligned); band [P][2] fp64 =
+ * Y0, h of every pass: band(y) = floor((y - Y0) / h) clamped to [0, nbands), image i of pass p entered in every band from band(south) to
+ * band(north) by the same expression; entry_img_dev [entries] int32 lists the entries pass by pass and band by band, band_start
+ * [P nbands + 1] int32 their first entries; box_dev [Q][4] fp64 (32-byte aligned), qpass_dev [Q] int32 (a pass outside [0, P): -1);
+ * scratch_dev: 32 bytes per entry (32-byte aligned); first_dev [Q] int32, the only memory written beside the scratch.  Two launches on
+ * `stream` (gather the rectangles into entry order; one wavefront per query), no atomics, plain vector stores.  Q = 0 does nothing; no
+ * image, pass or entry: every first is -1.  Refused before anything is launched, by the arguments and the *_host copies alone: a negative
+ * count or one >= 2^31 (ring vertices included: the starts are 32-bit), nbands < 1 or P nbands + 1 >= 2^31, ring starts or band starts that
+ * are not sorted or leave [0, V] / [0, entries], a band height that is not positive and finite or a Y0 that is not finite, a null pointer,
+ * an unaligned array, too little scratch. */
+int aq_coverage_first_i32(const double* rect_dev, const int32_t* ring_start_dev, const int32_t* ring_start_host, long long I,
+                          const double* xy_dev, long long V, const int32_t* entry_img_dev, long long entries,
+                          const int32_t* band_start_dev, const int32_t* band_start_host, const double* band_dev, const double* band_host,
+                          long long P, long long nbands, const double* box_dev, const int32_t* qpass_dev, long long Q, void* scratch_dev,
+                          size_t scratch_bytes, int32_t* first_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
