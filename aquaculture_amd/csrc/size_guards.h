@@ -130,4 +130,9 @@ inline bool eval_subsets_fit(ll n, ll K, ll S) {
     return n >= 0 && n < (1LL << 31) && K >= 0 && K <= 16 && S >= 1 && S <= 32 && S * n * (K > 0 ? K : 1) < (1LL << 36);
 }
 
+// ---- overlaps.hip ----  (boxes, band entries, list entries and detections of a call are 31-bit indices; band_start has nbands + 1 entries;
+// like dedup's, no line in oracle/guards.py: tests/test_gpu_overlaps.py walks the edges through the launchers' refusals)
+inline bool overlap_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }
+inline bool overlap_bands_fit(ll nbands) { return nbands >= 1 && nbands + 1 < (1LL << 31); }
+
 }  // namespace sg

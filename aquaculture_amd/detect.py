@@ -138,6 +138,13 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "box-against-polygon test on the GPU, and write what is left as the reference's ocean_detections.geojson; with "
                         "--facilities the ocean detections are clustered, as the reference does; needs --geocode-bboxes")
     p.add_argument("--ocean-out", default=None, metavar="GEOJSON", help="where --land-filter writes (default <save_dir>/ocean_detections.geojson)")
+    p.add_argument("--dedup-overlaps", nargs="?", const="", default=None, metavar="DIR",
+                   help="right after the geocoding and before the land filter, count every cage once where the download boxes of the "
+                        "--geocode-bboxes file overlap (the reference's deduplicate_download_boxes and deduplicate_gdf_with_bboxes, "
+                        "src/utils.py:241-322: a box yields to every box before it in the file), the partner lists and the clip on the GPU; "
+                        "writes dedup_detections.geojson, wanted_bboxes_dedup.geojson and dedup_overlaps.json (default <save_dir>); every "
+                        "later step works on the survivors, and --evaluate, --evaluate-kfold and --model-errors pass their labels through "
+                        "the same clip; detections.geojson stays as it is; needs --geocode-bboxes")
     p.add_argument("--evaluate", default=None, metavar="TRUTH_GEOJSON",
                    help="after the sweep, its geocoding, the land filter and the facilities, score the circle and square detections against the "
                         "human labels of TRUTH_GEOJSON (the reference's output/humanlabels.geojson) over the tuning grid of confidence threshold x "
@@ -204,6 +211,8 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if opt.land_filter is not None and not opt.geocode_bboxes:
         p.error("--land-filter filters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if opt.dedup_overlaps is not None and not opt.geocode_bboxes:
+        p.error(DEDUP_OVERLAPS_NEEDS_GEOCODE)
     if opt.evaluate is not None and not opt.geocode_bboxes:
         p.error("--evaluate scores geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if opt.model_errors is not None and not opt.geocode_bboxes:
@@ -235,6 +244,7 @@ NEAR_SITES_NEED_TONNAGE = "--tonnage-near-sites estimates the production near th
 KFOLD_NEEDS_EVALUATE = "--evaluate-kfold cross-validates the tuning grid of --evaluate: it needs --evaluate TRUTH_GEOJSON"
 KFOLD_SCENES_NEED_IMAGES = ("--evaluate-kfold with --tile-scenes: the tiles cut from the scenes are not listed anywhere after the sweep (a tile without "
                             "a detection leaves no label file), so the image table needs --evaluate-kfold-images FILE (the tile names, one per line)")
+DEDUP_OVERLAPS_NEEDS_GEOCODE = "--dedup-overlaps needs --geocode-bboxes CSV: the download boxes whose overlaps it resolves (and --save-txt --save-conf)"
 MODEL_ERRORS_NEED_GEOCODE = "--model-errors joins geocoded detections to the labels: it needs --geocode-bboxes CSV (and --save-txt --save-conf)"
 MODEL_ERRORS_OR_FILE = "the model errors of --tonnage come from --model-errors or from --tonnage-errors, not from both"
 
@@ -267,7 +277,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         evaluate_kfold_test=0.1, tonnage=None, tonnage_factors=None, tonnage_errors=None, tonnage_depths=None, tonnage_default_depth=4.84,
         tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, bathymetry=None, bathymetry_statistic="bathy_min", dedup_years=None,
         dedup_selection="random", dedup_seed=0, model_errors=None, model_errors_conf=None, model_errors_out=None, tonnage_missing=None,
-        tonnage_near_sites=None, log=print, **unsupported):
+        tonnage_near_sites=None, dedup_overlaps=None, log=print, **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb_checked, jpeg_slots_to_rgb, JPEG_WS_MAX, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     if dedup_years is not None and not geocode_bboxes:
@@ -291,6 +301,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         raise ValueError("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if land_filter is not None and not geocode_bboxes:
         raise ValueError("--land-filter filters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if dedup_overlaps is not None and not geocode_bboxes:
+        raise ValueError(DEDUP_OVERLAPS_NEEDS_GEOCODE)
     if model_errors is not None and not geocode_bboxes:
         raise ValueError(MODEL_ERRORS_NEED_GEOCODE)
     if model_errors is not None and tonnage_errors:
@@ -1109,12 +1121,22 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             table = geocode.geocode_label_dir(labels_dir, geocode_bboxes, out)
             log(f"{table['image'].shape[0]} detections geocoded to {out} in {time.perf_counter() - t_g:.2f}s")
             ocean = None
+            if dedup_overlaps is not None:
+                # the reference's next statement (geocode_results.py:256-262): every cage once where the download boxes overlap.  The
+                # survivors are the one keep mask of every later step; detections.geojson stays as it is
+                from . import overlaps as aqover
+                t_o = time.perf_counter()
+                ov_out = dedup_overlaps or str(save_dir)
+                ov = aqover.dedup_from_table(table, geocode_bboxes, ov_out)
+                ocean = ov["keep"]
+                log(f"dedup overlaps: {aqover.describe(ov['summary'])} in {ov_out} in {time.perf_counter() - t_o:.2f}s")
             if land_filter is not None:
                 # the step between them (reference geocode_results.py:200-218, :267-271): detections.geojson stays as it is
                 from . import land as aqland
                 t_l = time.perf_counter()
                 segs = aqland.load_land_geojson(land_filter)
-                ocean = aqland.ocean_rows(table, segs)
+                at_sea = aqland.ocean_rows(table, segs)
+                ocean = at_sea if ocean is None else ocean & at_sea       # with --dedup-overlaps: both unique and at sea
                 ocean_path = ocean_out or str(save_dir / "ocean_detections.geojson")
                 n_ocean = aqland.write_ocean_geojson(ocean_path, table["stems"], table, ocean)
                 log(f"{n_ocean} of {ocean.shape[0]} detections at sea ({segs.shape[0]} land edges) in {ocean_path} in {time.perf_counter() - t_l:.2f}s")
@@ -1158,7 +1180,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 grids = aqeval.grids_from_options(evaluate_conf, evaluate_eps, evaluate_min_cages)
                 ev_out = evaluate_out or str(save_dir)
                 ev = aqeval.evaluate_table(table, evaluate, ev_out, *grids, op=(facilities_conf, facilities_eps, facilities_min_cages), keep=ocean,
-                                           images=aqeval.read_image_list(evaluate_images) if evaluate_images else None)
+                                           images=aqeval.read_image_list(evaluate_images) if evaluate_images else None,
+                                           dedup_overlaps=geocode_bboxes if dedup_overlaps is not None else None)
                 log(f"{aqeval.describe(ev)} in {ev_out} in {time.perf_counter() - t_e:.2f}s")
                 if evaluate_kfold is not None:
                     # the rest of that script: the image table (every image of the sweep, with or without a detection: the source's
@@ -1174,7 +1197,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     kf = aqeval.kfold_from_options(table, evaluate, ev_out, grids, (facilities_conf, facilities_eps, facilities_min_cages), ocean,
                                                    aqeval.read_image_list(evaluate_images) if evaluate_images else None, evaluate_kfold,
                                                    evaluate_kfold_images, evaluate_known_sites, evaluate_kfold_seed, evaluate_kfold_test,
-                                                   geocode_bboxes, names=swept)
+                                                   geocode_bboxes, names=swept, dedup_overlaps=geocode_bboxes if dedup_overlaps is not None else None)
                     log(f"{aqkfold.describe(kf)} in {ev_out} in {time.perf_counter() - t_k:.2f}s")
             computed_errors = None
             if model_errors is not None:
@@ -1184,7 +1207,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 t_m = time.perf_counter()
                 me_out = model_errors_out or str(save_dir)
                 me = aqerr.model_errors_from_table(table, model_errors, me_out, facilities_conf if model_errors_conf is None else model_errors_conf,
-                                                   keep=ocean, widths=hw[table["image"], 1], heights=hw[table["image"], 0])
+                                                   keep=ocean, widths=hw[table["image"], 1], heights=hw[table["image"], 0],
+                                                   dedup_overlaps=geocode_bboxes if dedup_overlaps is not None else None)
                 computed_errors = me["errors"]
                 log(f"{aqerr.describe(me)} in {me_out} in {time.perf_counter() - t_m:.2f}s")
             if tonnage is not None:

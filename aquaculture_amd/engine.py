@@ -85,6 +85,7 @@ EXPORTS = (
     "aq_depth_ranges_f64", "aq_depth_stats_f64",
     "aq_dedup_fill_u32", "aq_dedup_sets_u32", "aq_dedup_select_f64",
     "aq_coverage_first_i32",
+    "aq_overlap_partners_f64", "aq_overlap_clip_f64",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -237,6 +238,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_dedup_select_f64.argtypes = [vp, vp, vp, vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp]
     lib.aq_coverage_first_i32.argtypes = [vp, vp, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, vp, vp, vp, C.c_longlong, C.c_longlong,
                                           vp, vp, C.c_longlong, vp, sz, vp, vp]
+    lib.aq_overlap_partners_f64.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, C.c_double, C.c_double, vp, vp, C.c_longlong, vp]
+    lib.aq_overlap_clip_f64.argtypes = [vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp, vp, vp, vp]
     lib.aq_augment_geometry.argtypes = [i32, i32, i32, vp, C.POINTER(i32)]
     lib.aq_augment_taps.argtypes = [i32, i32, i32, vp]
     lib.aq_stem_conv_scaled.argtypes = [vp, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]
@@ -1860,6 +1863,77 @@ def coverage_first(rect: torch.Tensor, ring_start: torch.Tensor, xy: torch.Tenso
     for t_ in (rect, ring_start, xy, entry_img, band_start, band, box, qpass, scratch, first):
         t_.record_stream(torch.cuda.current_stream())
     return first
+
+
+# ---- --dedup-overlaps: aq_overlap_partners_f64, aq_overlap_clip_f64 (every cage once where the download boxes overlap) ----
+
+def _overlap_tensor(name: str, t_: torch.Tensor, dt, shape) -> None:
+    if not t_.is_cuda or t_.dtype != dt or not t_.is_contiguous() or t_.ndim != len(shape) or any(a != b for a, b in zip(t_.shape, shape)):
+        raise ValueError(f"overlaps: {name} has to be a contiguous CUDA {dt} tensor of shape {shape}, not {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+
+
+def overlap_partners(boxes: torch.Tensor, entry_box: torch.Tensor, band_start: torch.Tensor, nbands: int, Y0: float, h: float,
+                     times: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """aq_overlap_partners_f64 on the current stream, both calls: boxes float64 CUDA [n, 4] (x0, y0, x1, y1) in file order, entry_box int32
+    CUDA [entries] and band_start int32 CUDA [nbands + 1] from overlaps.band_table -> (start int64 CUDA [n + 1], partner int32 CUDA
+    [start[n]]): box i's earlier partners, ascending, at partner[start[i] : start[i + 1]].  The list's size crosses to the host between the
+    count and the fill.  include/aq_engine.h states the contract; overlaps.partners_numpy gives the same arrays.  times = a dict that
+    receives "partners_ms" (HIP events around both calls, the host's wait for the size included)."""
+    _require_gpu()
+    n, entries, nbands = int(boxes.shape[0]), int(entry_box.shape[0]), int(nbands)
+    for name, t_, dt, shape in (("boxes", boxes, torch.float64, (n, 4)), ("entry_box", entry_box, torch.int32, (entries,)),
+                                ("band_start", band_start, torch.int32, (nbands + 1,))):
+        _overlap_tensor(name, t_, dt, shape)
+    lib = load_library()
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    start = torch.empty(n + 1, dtype=torch.int64, device=boxes.device)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if times is not None else None
+    if ev:
+        ev[0].record()
+    args = (ptr(boxes), n, ptr(entry_box), entries, ptr(band_start), nbands, float(Y0), float(h), start.data_ptr())
+    _check(lib.aq_overlap_partners_f64(*args, None, 0, _stream_ptr()))
+    total = int(start[n].item())
+    partner = torch.empty(total, dtype=torch.int32, device=boxes.device)
+    if total:
+        _check(lib.aq_overlap_partners_f64(*args, partner.data_ptr(), total, _stream_ptr()))
+    if ev:
+        ev[1].record()
+        ev[1].synchronize()
+        times["partners_ms"] = times.get("partners_ms", 0.0) + ev[0].elapsed_time(ev[1])
+    for t_ in (boxes, entry_box, band_start, start, partner):
+        t_.record_stream(torch.cuda.current_stream())
+    return start, partner
+
+
+def overlap_clip(boxes: torch.Tensor, start: torch.Tensor, partner: torch.Tensor, det_row: torch.Tensor, dets: torch.Tensor,
+                 times: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """aq_overlap_clip_f64 on the current stream: boxes float64 CUDA [n, 4], (start int64 CUDA [n + 1], partner int32 CUDA [T]) the partner
+    lists, det_row int32 CUDA [m] the detections' box rows, dets float64 CUDA [m, 4] -> (state uint8 CUDA [m], clip_bounds float64 CUDA
+    [m, 4], clip_area float64 CUDA [m], has_region uint8 CUDA [n]).  overlaps.clip_numpy gives the same bytes.  times = a dict that
+    receives "clip_ms" (HIP events; the call then waits for them)."""
+    _require_gpu()
+    n, T, m = int(boxes.shape[0]), int(partner.shape[0]), int(dets.shape[0])
+    for name, t_, dt, shape in (("boxes", boxes, torch.float64, (n, 4)), ("start", start, torch.int64, (n + 1,)), ("partner", partner, torch.int32, (T,)),
+                                ("det_row", det_row, torch.int32, (m,)), ("dets", dets, torch.float64, (m, 4))):
+        _overlap_tensor(name, t_, dt, shape)
+    dev = boxes.device
+    state = torch.empty(m, dtype=torch.uint8, device=dev)
+    bounds = torch.empty((m, 4), dtype=torch.float64, device=dev)
+    area = torch.empty(m, dtype=torch.float64, device=dev)
+    has_region = torch.empty(n, dtype=torch.uint8, device=dev)
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if times is not None else None
+    if ev:
+        ev[0].record()
+    _check(load_library().aq_overlap_clip_f64(ptr(boxes), n, start.data_ptr(), ptr(partner), T, ptr(det_row), ptr(dets), m, ptr(state), ptr(bounds),
+                                              ptr(area), ptr(has_region), _stream_ptr()))
+    if ev:
+        ev[1].record()
+        ev[1].synchronize()
+        times["clip_ms"] = times.get("clip_ms", 0.0) + ev[0].elapsed_time(ev[1])
+    for t_ in (boxes, start, partner, det_row, dets, state, bounds, area, has_region):
+        t_.record_stream(torch.cuda.current_stream())
+    return state, bounds, area, has_region
 
 
 # ---- --land-filter: aq_land_filter_f64 (detection boxes against the segments of the land polygons) ----

@@ -27,7 +27,9 @@ members' EPSG:3857 boxes, matched per year.
 
 Pinned against scikit-learn's DBSCAN per combination plus a brute-force join (the four counts, exactly).  NOT pinned, and what differs:
   * the centroid chain (facilities.centroids_3035) has the status facilities.py describes: no pyproj / shapely to compare with;
-  * the reference's overlap de-duplication (deduplicate_gdf_with_bboxes) of labels and detections is not applied;
+  * the reference's overlap de-duplication (deduplicate_gdf_with_bboxes) of labels and detections is applied under ``--dedup-overlaps``
+    only (overlaps.py: the detections through ``keep``, the labels through overlaps.filter_truth, ``dedup_overlaps`` = the box file); a
+    clipped survivor keeps its full box here, where the reference goes on with the clipped polygon;
   * the reference's get_tp tests ``r['index_key']`` for truth, so a match with row 0 of the key table never counts; that slip is not
     reproduced: row 0 matches like any other;
   * the reference drops the detections of images that lie wholly on land ("surely_land"); here the land filter's ocean rows are used when
@@ -441,9 +443,11 @@ def summary(data: Dict[str, dict], table: Dict[str, np.ndarray], op: Dict[str, d
 
 def evaluate_table(table: Dict[str, np.ndarray], truth_path: str, out_dir: str, conf_grid=DEFAULT_CONF, eps_grid=DEFAULT_EPS, min_grid=DEFAULT_MIN,
                    op: Tuple[float, float, int] = (0.5, 10.0, 5), keep=None, images: Optional[Sequence[str]] = None, cpu: bool = False,
-                   times: Optional[dict] = None) -> dict:
-    """inputs(), grid(), operating_point(*op) and both files in out_dir: cluster_performance.csv and evaluation.json -> summary()."""
-    data = inputs(table, load_truth_geojson(truth_path), keep, images)
+                   times: Optional[dict] = None, dedup_overlaps: Optional[str] = None) -> dict:
+    """inputs(), grid(), operating_point(*op) and both files in out_dir: cluster_performance.csv and evaluation.json -> summary().
+    dedup_overlaps = the download-box file: the labels pass through overlaps.filter_truth first."""
+    from . import overlaps
+    data = inputs(table, overlaps.filter_truth(load_truth_geojson(truth_path), dedup_overlaps, cpu=cpu), keep, images)
     perf = grid(data, conf_grid, eps_grid, min_grid, cpu=cpu, times=times)
     point = operating_point(data, float(op[0]), float(op[1]), int(op[2]), cpu=cpu)
     t0 = time.perf_counter()
@@ -501,17 +505,19 @@ def check_kfold_options(n_splits, test_frac) -> None:
 
 
 def kfold_from_options(table, truth_path: str, out_dir: str, grids, op, keep, images, n_splits: int, kfold_images: Optional[str], known_sites: Optional[str],
-                       seed: int, test_frac: float, wanted_bboxes_csv: Optional[str], names: Optional[Sequence[str]] = None, cpu: bool = False) -> dict:
+                       seed: int, test_frac: float, wanted_bboxes_csv: Optional[str], names: Optional[Sequence[str]] = None, cpu: bool = False,
+                       dedup_overlaps: Optional[str] = None) -> dict:
     """The cross-validation as both command lines run it: names = the images of the table when --evaluate-kfold-images gives none (None: those
-    with a detection or a label)."""
+    with a detection or a label).  dedup_overlaps = the download-box file: the labels pass through overlaps.filter_truth first."""
     from . import kfold as aqkfold
+    from . import overlaps
     if kfold_images:
         names = read_image_list(kfold_images)
     sites = aqkfold.load_known_sites(known_sites) if known_sites else None
     if sites is not None and not wanted_bboxes_csv:
         raise ValueError("--evaluate-known-sites needs the images' rectangles: --geocode-bboxes CSV")
     rects = aqkfold.tile_rects(wanted_bboxes_csv) if sites is not None else None
-    return aqkfold.kfold(table, load_truth_geojson(truth_path), out_dir, n_splits, names=names, rects=rects, sites=sites, seed=seed, test_frac=test_frac,
+    return aqkfold.kfold(table, overlaps.filter_truth(load_truth_geojson(truth_path), dedup_overlaps, cpu=cpu), out_dir, n_splits, names=names, rects=rects, sites=sites, seed=seed, test_frac=test_frac,
                          conf_grid=grids[0], eps_grid=grids[1], min_grid=grids[2], op=op, keep=keep, images=images, cpu=cpu)
 
 

@@ -17,8 +17,8 @@ EPSG:3035 columns follow the published IOGP formulas and are checked against the
 available here): they are returned as explicit easting / northing, because which of the reference's `xmin_m`/`ymin_m` columns
 receives which depends on pyproj's axis-order handling for EPSG:3035 (northing-first by authority), which cannot be checked
 without pyproj.  The reverse directions (lonlat_to_mercator, laea_europe_to_lonlat) serve facilities.py, which holds the reference's
-area estimates and facility clustering; land.py holds the land filter that the reference runs in between.  Out of scope, as in the
-reference's later steps: the de-duplication (a polygon overlay).
+area estimates and facility clustering; overlaps.py holds the de-duplication of overlapping download boxes that the reference runs next
+(for rectangles the polygon overlay is a rule of comparisons), land.py the land filter after it.
 """
 from __future__ import annotations
 

@@ -38,8 +38,9 @@ Pinned against literal_numpy and scipy.stats.norm.fit (tests/test_model_errors.p
     relative, and only the part of that within one query's reach could change which label wins -- where two candidates' overlaps agree
     to within that local distortion.  tests/test_model_errors.py compares the choice with a polygon clip in EPSG:3035 on its fixture;
   * ties: the reference sorts with pandas' unstable quicksort and keeps the first, which is not reproducible; here the smallest label row;
-  * the reference's overlap de-duplication (deduplicate_gdf_with_bboxes) is not applied -- the status evaluate.py gives it, and the
-    reference itself notes that it "isn't really needed" for the detections;
+  * the reference's overlap de-duplication (deduplicate_gdf_with_bboxes) is applied under ``--dedup-overlaps`` only -- the status
+    evaluate.py gives it: the detections through ``keep``, the labels through overlaps.filter_truth (``dedup_overlaps`` = the box file);
+    the reference itself notes that it "isn't really needed" for the detections;
   * areas, centroids and the EPSG:3035 chain have the status facilities.py and geocode.py describe (no pyproj / shapely to compare with).
 """
 from __future__ import annotations
@@ -329,9 +330,12 @@ def summary(res: Dict[str, object], truth_path: Optional[str], cpu: bool) -> dic
 
 
 def model_errors_from_table(table: Dict[str, np.ndarray], truth_path: str, out_dir: str, conf: float = 0.5, keep=None, cpu: bool = False,
-                            widths=geocode.IM_WIDTH, heights=geocode.IM_HEIGHT, times: Optional[dict] = None) -> Dict[str, object]:
-    """load_truth_geojson, distributions() and the three files in out_dir -> distributions()' result."""
-    res = distributions(table, load_truth_geojson(truth_path), conf, keep, cpu, widths, heights, times)
+                            widths=geocode.IM_WIDTH, heights=geocode.IM_HEIGHT, times: Optional[dict] = None,
+                            dedup_overlaps: Optional[str] = None) -> Dict[str, object]:
+    """load_truth_geojson, distributions() and the three files in out_dir -> distributions()' result.  dedup_overlaps = the download-box
+    file: the labels pass through overlaps.filter_truth first."""
+    from . import overlaps
+    res = distributions(table, overlaps.filter_truth(load_truth_geojson(truth_path), dedup_overlaps, cpu=cpu), conf, keep, cpu, widths, heights, times)
     t0 = time.perf_counter()
     os.makedirs(out_dir, exist_ok=True)
     write_errors_csv(os.path.join(out_dir, CSV_FILE), res)

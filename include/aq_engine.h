@@ -900,6 +900,41 @@ int aq_coverage_first_i32(const double* rect_dev, const int32_t* ring_start_dev,
                           long long P, long long nbands, const double* box_dev, const int32_t* qpass_dev, long long Q, void* scratch_dev,
                           size_t scratch_bytes, int32_t* first_dev, void* stream);
 
+/* ---- --dedup-overlaps: every cage once where the download boxes overlap (csrc/overlaps.hip) ----
+ * The reference's deduplicate_download_boxes / deduplicate_gdf_with_bboxes (src/utils.py:241-322) for closed axis-parallel boxes
+ * R_i = (x0, y0, x1, y1), fp64 EPSG:3857, in file order: a box yields to every box before it.  Definitions (DESIGN.md section 24;
+ * aquaculture_amd.overlaps restates them in numpy and in plain loops), comparisons only:
+ *   C_i          the earlier boxes j < i whose open interiors meet R_i's: x0_j < x1_i && x1_j > x0_i, likewise in y.
+ *   grid         of box i over some boxes of C_i: xs = the distinct values of x0_i, x1_i and of those boxes' x0_j, x1_j clamped into
+ *                [x0_i, x1_i], ys likewise; cell [xs[a], xs[a+1]] x [ys[b], ys[b+1]] is covered iff one of the boxes contains it.
+ *   detection D  of box i, on the grid over P(D) = the boxes of C_i that meet the closed D.  state 0 (dropped): no uncovered cell meets
+ *                the closed D; 1 (whole): uncovered cells and no covered one meet D's open interior; 2 (clipped): both kinds do;
+ *                3 (touching): an uncovered cell meets the closed D, none its open interior.  For states 1 - 3, over the pieces cell ^ D
+ *                of the uncovered cells that meet the closed D: clip_bounds = (min x0, min y0, max x1, max y1), clip_area = the sum of
+ *                (x1 - x0) * (y1 - y0), added per grid row (left to right, from 0) and the row sums bottom to top.  State 0: NaN, area 0.
+ *   has_region   of box i: D = R_i is not dropped (the box keeps a region of its own).
+ *
+ * aq_overlap_partners_f64: the lists C_i through horizontal bands: band(y) = floor((y - Y0) / h) clamped to [0, nbands); the host entered
+ * box j in every band from band(y0_j) to band(y1_j) by the same expression; entry_box_dev [entries] int32 lists the entries band by band,
+ * ascending inside a band, band_start_dev [nbands + 1] int32 the bands' first entries.  Two calls on the same tables.  partner_dev null:
+ * the count pass and an exclusive scan -- start_dev [n + 1] int64 (8-byte aligned) receives the lists' first entries, start[n] their
+ * total.  partner_dev [partner_cap] int32 given: the fill pass -- box i's partners at partner[start[i] .. start[i + 1]), ascending;
+ * nothing beyond partner_cap entries is written.  One wavefront per box.  boxes_dev [n][4] fp64 (32-byte aligned).  n = 0: start[0] = 0.
+ *
+ * aq_overlap_clip_f64: det_row_dev [m] int32 = the box of every detection (a row outside [0, n) is dropped), dets_dev [m][4] fp64 (32-byte
+ * aligned); state_dev [m] uint8, bounds_dev [m][4] fp64, area_dev [m] fp64, has_region_dev [n] uint8: the only memory written.  One
+ * wavefront per detection, lanes over the partners, 64 at a time: no partner count and no grid is too large.  List entries outside [0, n)
+ * and starts outside [0, T] are kept out on the device.  n = 0 and m = 0 does nothing.
+ * Both: no atomics, plain vector stores, the caller's stream; two calls give the same bytes.  Refused before anything is launched: a count
+ * outside [0, 2^31), nbands outside [1, 2^31 - 2], a band height that is not positive and finite, a Y0 that is not finite, a null pointer,
+ * an unaligned array. */
+int aq_overlap_partners_f64(const double* boxes_dev, long long n, const int32_t* entry_box_dev, long long entries,
+                            const int32_t* band_start_dev, long long nbands, double Y0, double h, long long* start_dev,
+                            int32_t* partner_dev, long long partner_cap, void* stream);
+int aq_overlap_clip_f64(const double* boxes_dev, long long n, const long long* start_dev, const int32_t* partner_dev, long long T,
+                        const int32_t* det_row_dev, const double* dets_dev, long long m, uint8_t* state_dev, double* bounds_dev,
+                        double* area_dev, uint8_t* has_region_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
