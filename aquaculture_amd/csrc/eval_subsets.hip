@@ -20,91 +20,13 @@
 //   out[s][q][m] = max of payload[s][k][m] over the matching keys k that have bit s; -inf when there is none or q is not in s
 // A first pass over the run ORs the matching keys' words (wave reduction); the loop over the set bits of the result -- the same word in every
 // lane -- then takes one more pass per subset that has a match, every lane in every exchange.  Subsets without a match are filled with -inf.
-#include "facility_runs.h"
-#include "size_guards.h"
+//
+// The three member-confidence kernels are eval_member.h's with SUBSETS = true: evaluate.hip's source, not a copy of it.  The join's run bound,
+// predicate, reductions and per-subset pass are box_join.h's.
+#include "eval_member.h"
+#include "box_join.h"
 
 namespace {
-
-constexpr int EVAL_MAX_K = 16;
-constexpr int EVAL_MAX_S = 32;
-
-struct SubsetParams : FacRuns {
-    const double* conf;        // [n], original order
-    const unsigned* mask;      // [n], original order
-    int K, S;
-    double* sconf;             // scratch [n]: confidences by sorted position; -inf for an entry of perm that is no index
-    unsigned* smask;           // scratch [n]: mask words by sorted position, bits >= S cleared; 0 for an entry of perm that is no index
-    double* T;                 // scratch [S][n][K], by sorted position; rows of points outside the subset are never written nor read
-    double* M;                 // out [S][n][K], original order
-};
-
-__device__ __forceinline__ unsigned low_bits(int S) { return S >= 32 ? 0xFFFFFFFFu : ((1u << S) - 1u); }
-
-__global__ __launch_bounds__(256) void subsets_gather_kernel(const SubsetParams p) {
-    const long long i = blockIdx.x * 256LL + threadIdx.x;
-    if (i >= p.n) return;
-    const int o = fac_gather(p, i);
-    p.sconf[i] = o >= 0 ? p.conf[o] : -__builtin_inf();
-    p.smask[i] = o >= 0 ? (p.mask[o] & low_bits(p.S)) : 0u;
-}
-
-template <int KC>
-__global__ __launch_bounds__(256) void subsets_topk_kernel(const SubsetParams p) {
-    const long long i = blockIdx.x * 256LL + threadIdx.x;
-    const unsigned s = blockIdx.y;                                              // < S <= 32
-    if (i >= p.n) return;
-    if (!((p.smask[i] >> s) & 1u)) return;
-    double top[KC];                                                             // descending; static indices only, so it stays in registers
-#pragma unroll
-    for (int m = 0; m < KC; ++m) top[m] = -__builtin_inf();
-    fac_neighbours(p, i, [&](int k) {
-        if (!((p.smask[k] >> s) & 1u)) return;
-        double v = p.sconf[k];
-#pragma unroll
-        for (int m = 0; m < KC; ++m) {                                          // v sinks to its place, what it displaces sinks on
-            const double t = top[m];
-            const bool gt = v > t;
-            top[m] = gt ? v : t;
-            v = gt ? t : v;
-        }
-    });
-    const double c = p.sconf[i];
-    double* out = p.T + ((long long)s * p.n + i) * p.K;
-#pragma unroll
-    for (int m = 0; m < KC; ++m)
-        if (m < p.K) out[m] = top[m] < c ? top[m] : c;
-}
-
-template <int KC>
-__global__ __launch_bounds__(256) void subsets_member_kernel(const SubsetParams p) {
-    const long long i = blockIdx.x * 256LL + threadIdx.x;
-    const unsigned s = blockIdx.y;
-    if (i >= p.n) return;
-    const int o = fac_orig(p, (int)i);
-    if (o < 0) return;
-    double* out = p.M + ((long long)s * p.n + o) * p.K;
-    if (!((p.smask[i] >> s) & 1u)) {
-#pragma unroll
-        for (int m = 0; m < KC; ++m)
-            if (m < p.K) out[m] = -__builtin_inf();
-        return;
-    }
-    double mx[KC];
-#pragma unroll
-    for (int m = 0; m < KC; ++m) mx[m] = -__builtin_inf();
-    const double* Ts = p.T + (long long)s * p.n * p.K;
-    fac_neighbours(p, i, [&](int k) {
-        if (!((p.smask[k] >> s) & 1u)) return;
-        const double* t = Ts + (long long)k * p.K;
-#pragma unroll
-        for (int m = 0; m < KC; ++m)
-            if (m < p.K) { const double v = t[m]; mx[m] = v > mx[m] ? v : mx[m]; }
-    });
-    const double c = p.sconf[i];
-#pragma unroll
-    for (int m = 0; m < KC; ++m)
-        if (m < p.K) out[m] = mx[m] < c ? mx[m] : c;
-}
 
 struct SubsetMatchParams {
     const double4* qbox;       // [Q] (x0, y0, x1, y1)
@@ -119,34 +41,17 @@ struct SubsetMatchParams {
     double* out;               // out [S][Q][K] or null
 };
 
-__device__ __forceinline__ bool boxes_meet(const double4& a, const double4& b) {
-    return a.x <= b.z && b.x <= a.z && a.y <= b.w && b.y <= a.w;
-}
-
 __global__ __launch_bounds__(256) void box_match_subsets_kernel(const SubsetMatchParams p) {
     const int lane = threadIdx.x & 63;
     const long long q = blockIdx.x * 4LL + (threadIdx.x >> 6);                  // one wavefront per query: uniform from here on
     if (q >= p.Q) return;
     const double4 b = p.qbox[q];
-    const int g = p.qgroup[q];
     const unsigned qm = p.qmask[q] & low_bits(p.S);
-    int first = 0, end = 0;
-    if ((unsigned)g < (unsigned)p.G) {                                          // (a table the caller got wrong stays inside [0, N])
-        first = min(max(p.group_start[g], 0), p.N);
-        end = min(max(p.group_start[g + 1], first), p.N);
-    }
-    int lo = first, hi = end;                                                   // the first key of the run with x0 > query.x1; NaN: an empty run
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (p.kbox[mid].x <= b.z) lo = mid + 1; else hi = mid;
-    }
-    end = lo;
+    const KeyRun run = box_join_run(p.group_start, p.G, p.N, p.kbox, p.qgroup[q], b.z);
     unsigned km = 0;
-    for (int k = first + lane; k < end; k += 64)
+    for (int k = run.first + lane; k < run.end; k += 64)
         if (boxes_meet(p.kbox[k], b)) km |= p.kmask[k];
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) km |= (unsigned)__shfl_xor((int)km, s, 64);
-    const unsigned live = (unsigned)__builtin_amdgcn_readfirstlane((int)(km & qm));     // the same in every lane: the loops below are uniform
+    const unsigned live = (unsigned)__builtin_amdgcn_readfirstlane((int)(wave_or(km) & qm));    // the same in every lane: the loops below are uniform
     if (lane == 0) p.hitmask[q] = live;
     if (p.K == 0) return;
     for (int s = 0; s < p.S; ++s) {
@@ -155,39 +60,9 @@ __global__ __launch_bounds__(256) void box_match_subsets_kernel(const SubsetMatc
             if (lane < p.K) out[lane] = -__builtin_inf();
             continue;
         }
-        const double* pay = p.payload + (long long)s * p.N * p.K;
-        double mx[EVAL_MAX_K];
-#pragma unroll
-        for (int m = 0; m < EVAL_MAX_K; ++m) mx[m] = -__builtin_inf();
-        for (int k = first + lane; k < end; k += 64) {
-            if (((p.kmask[k] >> s) & 1u) && boxes_meet(p.kbox[k], b)) {
-                const double* t = pay + (long long)k * p.K;
-#pragma unroll
-                for (int m = 0; m < EVAL_MAX_K; ++m)
-                    if (m < p.K) { const double v = t[m]; mx[m] = v > mx[m] ? v : mx[m]; }
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < EVAL_MAX_K; ++m) {
-            if (m < p.K) {                                                      // uniform: every lane of the wave takes part in the exchange
-                double v = mx[m];
-#pragma unroll
-                for (int x = 32; x >= 1; x >>= 1) {
-                    const double w = __shfl_xor(v, x, 64);
-                    v = w > v ? w : v;
-                }
-                if (lane == 0) out[m] = v;
-            }
-        }
+        box_join_max<EVAL_MAX_K>(run, lane, p.payload + (long long)s * p.N * p.K, p.K, out,
+                                 [&](int k) { return ((p.kmask[k] >> s) & 1u) && boxes_meet(p.kbox[k], b); });
     }
-}
-
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-template <int KC>
-void launch_subsets(const SubsetParams& p, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL(subsets_topk_kernel<KC>, grid, dim3(256), 0, st, p);
-    hipLaunchKernelGGL(subsets_member_kernel<KC>, grid, dim3(256), 0, st, p);
 }
 
 bool shape_ok(int K, int S, bool payload_optional) {
@@ -201,8 +76,8 @@ bool shape_ok(int K, int S, bool payload_optional) {
 // sg::eval_subsets_fit refuses.
 extern "C" size_t aq_eval_subsets_scratch_bytes(long long n, int K, int S) {
     if (n <= 0 || !shape_ok(K, S, false) || !sg::eval_subsets_fit(n, K, S)) return 0;
-    return align16((size_t)n * 16) + align16((size_t)n * 24) + align16((size_t)n * 8) + align16((size_t)n * 4) +
-           align16((size_t)n * 8 * (size_t)K * (size_t)S);
+    EvalParams p = {};
+    return eval_scratch_layout<true>(p, nullptr, (size_t)n, (size_t)K, (size_t)S);
 }
 
 // Bytes of scratch aq_box_match_subsets_f64 needs: none today (0); the query is there so that a caller sizes through it and the size guard
@@ -226,32 +101,13 @@ extern "C" int aq_eval_member_conf_subsets_f64(const long long* keys_sorted_dev,
                ((uintptr_t)scratch_dev & 15) == 0 && ((uintptr_t)member_conf_dev & 7) == 0, "evaluate subsets: unaligned array");
     const size_t need = aq_eval_subsets_scratch_bytes(n, K, S);
     AQ_REQUIRE(scratch_bytes >= need, "evaluate subsets: %zu bytes of scratch, %zu needed (aq_eval_subsets_scratch_bytes)", scratch_bytes, need);
-    SubsetParams p = {};
+    EvalParams p = {};
     p.keys = keys_sorted_dev; p.perm = perm_dev; p.xy = xy_dev; p.group = group_dev;
     p.n = (int)n; p.eps2 = eps * eps;
     p.conf = conf_dev; p.mask = mask_dev; p.K = K; p.S = S;
-    char* s = (char*)scratch_dev;
-    p.sxy = (double2*)s;
-    s += align16((size_t)n * 16);
-    p.runs = (int2*)s;
-    s += align16((size_t)n * 24);
-    p.sconf = (double*)s;
-    s += align16((size_t)n * 8);
-    p.smask = (unsigned*)s;
-    s += align16((size_t)n * 4);
-    p.T = (double*)s;
+    eval_scratch_layout<true>(p, scratch_dev, (size_t)n, (size_t)K, (size_t)S);
     p.M = member_conf_dev;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(subsets_gather_kernel, dim3(blocks), dim3(256), 0, st, p);
-    AQ_CHECK_HIP(hipGetLastError());
-    const dim3 grid(blocks, (unsigned)S);
-    if (K == 1) launch_subsets<1>(p, grid, st);
-    else if (K <= 4) launch_subsets<4>(p, grid, st);
-    else if (K <= 8) launch_subsets<8>(p, grid, st);
-    else launch_subsets<EVAL_MAX_K>(p, grid, st);
-    AQ_CHECK_HIP(hipGetLastError());
-    return AQ_OK;
+    return eval_member_launch<true>(p, (hipStream_t)stream);
 }
 
 extern "C" int aq_box_match_subsets_f64(const double* qbox_dev, const int32_t* qgroup_dev, const uint32_t* qmask_dev, long long Q,

@@ -18,72 +18,13 @@
 // intersect (touching edges and corners count, as shapely's `intersects`).  One wavefront (64 lanes) per query: a binary search bounds the
 // group's run by key.x0 <= query.x1, the lanes stride over what is left, then a wave reduction: hit = any match; with a payload [N][K], the
 // elementwise maximum over the matching keys (-inf when none).
-#include "facility_runs.h"
+//
+// The three member-confidence kernels are eval_member.h's with SUBSETS = false (eval_subsets.hip runs the same source with masks); the join
+// is built from box_join.h, which eval_subsets.hip's and model_errors.hip's joins share.
+#include "eval_member.h"
+#include "box_join.h"
 
 namespace {
-
-constexpr int EVAL_MAX_K = 16;
-
-struct EvalParams : FacRuns {
-    const double* conf;        // [n], original order
-    int K;
-    double* sconf;             // scratch [n]: confidences by sorted position; -inf for an entry of perm that is no index
-    double* T;                 // scratch [n][K], by sorted position
-    double* M;                 // out [n][K], original order
-};
-
-__global__ __launch_bounds__(256) void eval_gather_kernel(const EvalParams p) {
-    const long long i = blockIdx.x * 256LL + threadIdx.x;
-    if (i >= p.n) return;
-    const int o = fac_gather(p, i);
-    p.sconf[i] = o >= 0 ? p.conf[o] : -__builtin_inf();
-}
-
-template <int KC>
-__global__ __launch_bounds__(256) void eval_topk_kernel(const EvalParams p) {
-    const long long i = blockIdx.x * 256LL + threadIdx.x;
-    if (i >= p.n) return;
-    double top[KC];                                                             // descending; static indices only, so it stays in registers
-#pragma unroll
-    for (int m = 0; m < KC; ++m) top[m] = -__builtin_inf();
-    fac_neighbours(p, i, [&](int k) {
-        double v = p.sconf[k];
-#pragma unroll
-        for (int m = 0; m < KC; ++m) {                                          // v sinks to its place, what it displaces sinks on
-            const double t = top[m];
-            const bool gt = v > t;
-            top[m] = gt ? v : t;
-            v = gt ? t : v;
-        }
-    });
-    const double c = p.sconf[i];
-    double* out = p.T + i * p.K;
-#pragma unroll
-    for (int m = 0; m < KC; ++m)
-        if (m < p.K) out[m] = top[m] < c ? top[m] : c;
-}
-
-template <int KC>
-__global__ __launch_bounds__(256) void eval_member_kernel(const EvalParams p) {
-    const long long i = blockIdx.x * 256LL + threadIdx.x;
-    if (i >= p.n) return;
-    const int o = fac_orig(p, (int)i);
-    if (o < 0) return;
-    double mx[KC];
-#pragma unroll
-    for (int m = 0; m < KC; ++m) mx[m] = -__builtin_inf();
-    fac_neighbours(p, i, [&](int k) {
-        const double* t = p.T + (long long)k * p.K;
-#pragma unroll
-        for (int m = 0; m < KC; ++m)
-            if (m < p.K) { const double v = t[m]; mx[m] = v > mx[m] ? v : mx[m]; }
-    });
-    const double c = p.sconf[i];
-    double* out = p.M + (long long)o * p.K;
-#pragma unroll
-    for (int m = 0; m < KC; ++m)
-        if (m < p.K) out[m] = mx[m] < c ? mx[m] : c;
-}
 
 struct MatchParams {
     const double4* qbox;       // [Q] (x0, y0, x1, y1)
@@ -101,54 +42,11 @@ __global__ __launch_bounds__(256) void box_match_kernel(const MatchParams p) {
     const long long q = blockIdx.x * 4LL + (threadIdx.x >> 6);                  // one wavefront per query: uniform from here on
     if (q >= p.Q) return;
     const double4 b = p.qbox[q];
-    const int g = p.qgroup[q];
-    int first = 0, end = 0;
-    if ((unsigned)g < (unsigned)p.G) {                                          // (a table the caller got wrong stays inside [0, N])
-        first = min(max(p.group_start[g], 0), p.N);
-        end = min(max(p.group_start[g + 1], first), p.N);
-    }
-    int lo = first, hi = end;                                                   // the first key of the run with x0 > query.x1; NaN: an empty run
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (p.kbox[mid].x <= b.z) lo = mid + 1; else hi = mid;
-    }
-    end = lo;
-    double mx[EVAL_MAX_K];
-#pragma unroll
-    for (int m = 0; m < EVAL_MAX_K; ++m) mx[m] = -__builtin_inf();
-    bool any = false;
-    for (int k = first + lane; k < end; k += 64) {
-        const double4 a = p.kbox[k];
-        if (a.x <= b.z && b.x <= a.z && a.y <= b.w && b.y <= a.w) {
-            any = true;
-            const double* t = p.payload + (long long)k * p.K;                   // (never read when K = 0)
-#pragma unroll
-            for (int m = 0; m < EVAL_MAX_K; ++m)
-                if (m < p.K) { const double v = t[m]; mx[m] = v > mx[m] ? v : mx[m]; }
-        }
-    }
+    const KeyRun run = box_join_run(p.group_start, p.G, p.N, p.kbox, p.qgroup[q], b.z);
+    const bool any = box_join_max<EVAL_MAX_K>(run, lane, p.payload, p.K, p.out + q * p.K,      // one pass: the hit and the payload maxima together
+                                              [&](int k) { const double4 a = p.kbox[k]; return boxes_meet(a, b); });
     const bool hit = __any(any) != 0;
     if (lane == 0) p.hit[q] = hit ? 1 : 0;
-#pragma unroll
-    for (int m = 0; m < EVAL_MAX_K; ++m) {
-        if (m < p.K) {                                                          // uniform: every lane of the wave takes part in the exchange
-            double v = mx[m];
-#pragma unroll
-            for (int s = 32; s >= 1; s >>= 1) {
-                const double w = __shfl_xor(v, s, 64);
-                v = w > v ? w : v;
-            }
-            if (lane == 0) p.out[q * p.K + m] = v;
-        }
-    }
-}
-
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-template <int KC>
-void launch_member(const EvalParams& p, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL(eval_topk_kernel<KC>, grid, dim3(256), 0, st, p);
-    hipLaunchKernelGGL(eval_member_kernel<KC>, grid, dim3(256), 0, st, p);
 }
 
 }  // namespace
@@ -157,7 +55,8 @@ void launch_member(const EvalParams& p, dim3 grid, hipStream_t st) {
 // each array rounded up to 16 bytes; 0 for n <= 0, n >= 2^31 or K outside 1 .. 16.
 extern "C" size_t aq_eval_scratch_bytes(long long n, int K) {
     if (n <= 0 || n >= (1LL << 31) || K < 1 || K > EVAL_MAX_K) return 0;
-    return align16((size_t)n * 16) + align16((size_t)n * 24) + align16((size_t)n * 8) + align16((size_t)n * 8 * (size_t)K);
+    EvalParams p = {};
+    return eval_scratch_layout<false>(p, nullptr, (size_t)n, (size_t)K, 1);
 }
 
 extern "C" int aq_eval_member_conf_f64(const long long* keys_sorted_dev, const int32_t* perm_dev, const double* xy_dev, const int32_t* group_dev,
@@ -176,26 +75,10 @@ extern "C" int aq_eval_member_conf_f64(const long long* keys_sorted_dev, const i
     EvalParams p = {};
     p.keys = keys_sorted_dev; p.perm = perm_dev; p.xy = xy_dev; p.group = group_dev;
     p.n = (int)n; p.eps2 = eps * eps;
-    p.conf = conf_dev; p.K = K;
-    char* s = (char*)scratch_dev;
-    p.sxy = (double2*)s;
-    s += align16((size_t)n * 16);
-    p.runs = (int2*)s;
-    s += align16((size_t)n * 24);
-    p.sconf = (double*)s;
-    s += align16((size_t)n * 8);
-    p.T = (double*)s;
+    p.conf = conf_dev; p.K = K; p.S = 1;
+    eval_scratch_layout<false>(p, scratch_dev, (size_t)n, (size_t)K, 1);
     p.M = member_conf_dev;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(eval_gather_kernel, grid, dim3(256), 0, st, p);
-    AQ_CHECK_HIP(hipGetLastError());
-    if (K == 1) launch_member<1>(p, grid, st);
-    else if (K <= 4) launch_member<4>(p, grid, st);
-    else if (K <= 8) launch_member<8>(p, grid, st);
-    else launch_member<EVAL_MAX_K>(p, grid, st);
-    AQ_CHECK_HIP(hipGetLastError());
-    return AQ_OK;
+    return eval_member_launch<false>(p, (hipStream_t)stream);
 }
 
 extern "C" int aq_box_match_f64(const double* qbox_dev, const int32_t* qgroup_dev, long long Q, const double* kbox_dev, long long N,

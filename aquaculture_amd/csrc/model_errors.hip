@@ -6,7 +6,7 @@
 // query q when the groups agree and the closed boxes intersect (box_match_kernel's predicate); with
 //   inter(q, k) = (min(q.x1, k.x1) - max(q.x0, k.x0)) * (min(q.y1, k.y1) - max(q.y0, k.y0))       two subtractions and one product, as written
 // the match is the candidate with the largest inter; among equal inter the smallest original row (krow) wins; a NaN inter never wins over a
-// number (among NaNs the smallest row).  One wavefront per query: the binary search of box_match_kernel bounds the group's run by
+// number (among NaNs the smallest row).  One wavefront per query: box_join.h's run bound, box_match_kernel's, cuts the group's run at
 // key.x0 <= query.x1, the lanes stride over what is left, each keeping its best (inter, row, position), then six exchange steps under the
 // same rule -- a total order, since rows are distinct, so every lane ends with the same winner.  Lane 0 writes
 //   match    the winner's original row, -1 without a candidate
@@ -20,7 +20,7 @@
 //   the 64 partials fold as v[i] + v[i + 32], then + 16, ... + 1 (the xor exchange: lane i + s computes the same sum, + is commutative);
 //   pass 1: S = sum of error, the count in integers, mean = S / n;   pass 2: D = sum of (error - mean)^2, sd = sqrt(D / n).
 // n = 0: mean and sd are NaN.  fp64 in + - x / sqrt only, each rounded as written (this file is built with -ffp-contract=off).
-#include "aq_common.h"
+#include "box_join.h"
 
 namespace {
 
@@ -55,23 +55,12 @@ __global__ __launch_bounds__(256) void model_error_match_kernel(const ErrMatchPa
     const long long q = blockIdx.x * 4LL + (threadIdx.x >> 6);                  // one wavefront per query: uniform from here on
     if (q >= p.Q) return;
     const double4 b = p.qbox[q];
-    const int g = p.qgroup[q];
-    int first = 0, end = 0;
-    if ((unsigned)g < (unsigned)p.G) {                                          // (a table the caller got wrong stays inside [0, N])
-        first = min(max(p.group_start[g], 0), p.N);
-        end = min(max(p.group_start[g + 1], first), p.N);
-    }
-    int lo = first, hi = end;                                                   // the first key of the run with x0 > query.x1; NaN: an empty run
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (p.kbox[mid].x <= b.z) lo = mid + 1; else hi = mid;
-    }
-    end = lo;
+    const KeyRun run = box_join_run(p.group_start, p.G, p.N, p.kbox, p.qgroup[q], b.z);
     double bi = 0.0;
     int br = -1, bk = -1;
-    for (int k = first + lane; k < end; k += 64) {
+    for (int k = run.first + lane; k < run.end; k += 64) {
         const double4 a = p.kbox[k];
-        if (a.x <= b.z && b.x <= a.z && a.y <= b.w && b.y <= a.w) {
+        if (boxes_meet(a, b)) {
             const double w = (b.z < a.z ? b.z : a.z) - (b.x > a.x ? b.x : a.x);
             const double h = (b.w < a.w ? b.w : a.w) - (b.y > a.y ? b.y : a.y);
             const double ci = w * h;

@@ -1314,6 +1314,26 @@ def facility_sort_keys(xy: torch.Tensor, group: torch.Tensor, eps: float) -> Tup
     return keys, perm.to(torch.int32)
 
 
+class _Phases:
+    """HIP events around the phases of a wrapper's call on the current stream: mark() before each phase, done(key, ...) after the last one
+    writes the phases' milliseconds into `times` under those keys (the call then waits for them).  With times = None nothing is recorded."""
+
+    def __init__(self, times: Optional[dict]):
+        self.times, self.events = times, []
+
+    def mark(self) -> None:
+        if self.times is not None:
+            self.events.append(torch.cuda.Event(enable_timing=True))
+            self.events[-1].record()
+
+    def done(self, *keys: str) -> None:
+        if self.times is not None:
+            self.mark()
+            self.events[-1].synchronize()
+            for key, a, b in zip(keys, self.events, self.events[1:]):
+                self.times[key] = a.elapsed_time(b)
+
+
 def facility_dbscan(xy: torch.Tensor, group: torch.Tensor, eps: float, min_samples: int, stream: Optional[torch.cuda.Stream] = None,
                     scratch: Optional[torch.Tensor] = None, times: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """aq_facility_dbscan_f64 on `stream` (default: the current one): xy float64 CUDA [n, 2] (metres), group int32 CUDA [n] (dense ids; points
@@ -1334,21 +1354,16 @@ def facility_dbscan(xy: torch.Tensor, group: torch.Tensor, eps: float, min_sampl
         if n == 0:
             _check(lib.aq_facility_dbscan_f64(None, None, None, None, 0, float(eps), int(min_samples), None, 0, None, None, _stream_ptr()))
             return core, root
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
-        if ev:
-            ev[0].record()
+        ph = _Phases(times)
+        ph.mark()
         keys, perm = facility_sort_keys(xy, group, eps)
         need = int(lib.aq_facility_scratch_bytes(n))
         if scratch is None or scratch.numel() < need:
             scratch = torch.empty(need, dtype=torch.uint8, device=xy.device)
-        if ev:
-            ev[1].record()
+        ph.mark()
         _check(lib.aq_facility_dbscan_f64(keys.data_ptr(), perm.data_ptr(), xy.data_ptr(), group.data_ptr(), n, float(eps), int(min_samples),
                                           scratch.data_ptr(), scratch.numel(), core.data_ptr(), root.data_ptr(), _stream_ptr()))
-        if ev:
-            ev[2].record()
-            ev[2].synchronize()
-            times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+        ph.done("sort_ms", "kernel_ms")
         for t_ in (keys, perm, xy, group, scratch, core, root):
             t_.record_stream(torch.cuda.current_stream())
     return core, root
@@ -1365,32 +1380,42 @@ def eval_member_conf(xy: torch.Tensor, group: torch.Tensor, conf: torch.Tensor, 
     the points of at least that confidence makes point i a member of a cluster (-inf: none); evaluate.member_conf_numpy gives the same
     bytes.  The sort is torch's (facility_sort_keys).  times = a dict that receives "sort_ms" and "kernel_ms" (HIP events; the call then
     waits for them)."""
+    return _eval_member_conf(xy, group, conf, eps, K, times)
+
+
+def _eval_member_conf(xy, group, conf, eps, K, times, mask=None, S=None):
+    """The body of eval_member_conf (S = None) and of eval_member_conf_subsets (mask and S given): the same checks, sort, scratch and call,
+    with the mask words and S passed on to the subsets entry."""
     _require_gpu()
     lib = load_library()
     assert xy.is_cuda and group.is_cuda and conf.is_cuda and xy.dtype == torch.float64 and group.dtype == torch.int32 and conf.dtype == torch.float64
     xy, group, conf = xy.contiguous(), group.contiguous(), conf.contiguous()
     n = xy.shape[0]
     assert xy.shape == (n, 2) and group.shape == (n,) and conf.shape == (n,)
-    if not eps > 0 or not 1 <= int(K) <= EVAL_MAX_K:        # the library refuses these too; here before the sort
-        raise ValueError(f"evaluate: eps = {eps}, K = {K} (eps > 0 and 1 <= K <= {EVAL_MAX_K})")
-    M = torch.empty((n, int(K)), dtype=torch.float64, device=xy.device)
-    if n == 0:
-        _check(lib.aq_eval_member_conf_f64(None, None, None, None, None, 0, float(eps), int(K), None, 0, None, _stream_ptr()))
+    if S is None:                                           # the library refuses these too; here before the sort
+        if not eps > 0 or not 1 <= int(K) <= EVAL_MAX_K:
+            raise ValueError(f"evaluate: eps = {eps}, K = {K} (eps > 0 and 1 <= K <= {EVAL_MAX_K})")
+        fn, scratch_bytes, sizes, arrays = lib.aq_eval_member_conf_f64, lib.aq_eval_scratch_bytes, (int(K),), (xy, group, conf)
+    else:
+        if not eps > 0 or not 1 <= int(K) <= EVAL_MAX_K or not 1 <= int(S) <= EVAL_MAX_S:
+            raise ValueError(f"evaluate subsets: eps = {eps}, K = {K}, S = {S} (eps > 0, 1 <= K <= {EVAL_MAX_K} and 1 <= S <= {EVAL_MAX_S})")
+        fn, scratch_bytes, sizes = lib.aq_eval_member_conf_subsets_f64, lib.aq_eval_subsets_scratch_bytes, (int(K), int(S))
+        arrays = (xy, group, conf, _subset_words(mask, n, "mask"))
+    M = torch.empty(sizes[1:] + (n, int(K)), dtype=torch.float64, device=xy.device)
+    if n == 0:                                              # null pointers: the library still validates eps, K and S
+        _check(fn(None, None, *(None for _ in arrays), 0, float(eps), *sizes, None, 0, None, _stream_ptr()))
         return M
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
-    if ev:
-        ev[0].record()
-    keys, perm = facility_sort_keys(xy, group, eps)
-    scratch = torch.empty(int(lib.aq_eval_scratch_bytes(n, int(K))), dtype=torch.uint8, device=xy.device)
-    if ev:
-        ev[1].record()
-    _check(lib.aq_eval_member_conf_f64(keys.data_ptr(), perm.data_ptr(), xy.data_ptr(), group.data_ptr(), conf.data_ptr(), n, float(eps), int(K),
-                                       scratch.data_ptr(), scratch.numel(), M.data_ptr(), _stream_ptr()))
-    if ev:
-        ev[2].record()
-        ev[2].synchronize()
-        times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
-    for t_ in (keys, perm, xy, group, conf, scratch, M):
+    need = int(scratch_bytes(n, *sizes))
+    if S is not None and need == 0:
+        raise ValueError(f"evaluate subsets: {n} points x {K} sizes x {S} subsets is more than one call takes")
+    ph = _Phases(times)
+    ph.mark()
+    arrays = facility_sort_keys(xy, group, eps) + arrays
+    scratch = torch.empty(need, dtype=torch.uint8, device=xy.device)
+    ph.mark()
+    _check(fn(*(t_.data_ptr() for t_ in arrays), n, float(eps), *sizes, scratch.data_ptr(), scratch.numel(), M.data_ptr(), _stream_ptr()))
+    ph.done("sort_ms", "kernel_ms")
+    for t_ in arrays + (scratch, M):
         t_.record_stream(torch.cuda.current_stream())
     return M
 
@@ -1404,6 +1429,22 @@ def box_match_sort(kbox: torch.Tensor, kgroup: torch.Tensor, G: int) -> Tuple[to
     return order, start.to(torch.int32)
 
 
+def _join_inputs(what: str, qbox, qgroup, kbox, kgroup, G, S=None):
+    """What the three box joins check before anything else, under the caller's message prefix: dtypes and shapes, S when there are subsets,
+    the keys' group ids -> (the library, qbox and qgroup contiguous, Q, N, G)."""
+    _require_gpu()
+    lib = load_library()
+    assert qbox.is_cuda and qbox.dtype == torch.float64 and kbox.dtype == torch.float64 and qgroup.dtype == torch.int32 and kgroup.dtype == torch.int32
+    qbox, qgroup = qbox.contiguous(), qgroup.contiguous()
+    Q, N, G = qbox.shape[0], kbox.shape[0], int(G)
+    assert qbox.shape == (Q, 4) and kbox.shape == (N, 4) and qgroup.shape == (Q,) and kgroup.shape == (N,)
+    if S is not None and not 1 <= S <= EVAL_MAX_S:
+        raise ValueError(f"{what}: S = {S} subsets (1 to {EVAL_MAX_S})")
+    if G < 0 or (N and not (0 <= int(kgroup.min()) and int(kgroup.max()) < G)):
+        raise ValueError(f"{what}: the keys' group ids have to lie in [0, {G})")
+    return lib, qbox, qgroup, Q, N, G
+
+
 def box_match(qbox: torch.Tensor, qgroup: torch.Tensor, kbox: torch.Tensor, kgroup: torch.Tensor, G: int, payload: Optional[torch.Tensor] = None,
               times: Optional[dict] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """aq_box_match_f64 on the current stream: qbox float64 CUDA [Q, 4] (x0, y0, x1, y1), qgroup int32 CUDA [Q], kbox float64 CUDA [N, 4],
@@ -1411,14 +1452,7 @@ def box_match(qbox: torch.Tensor, qgroup: torch.Tensor, kbox: torch.Tensor, kgro
     (hit uint8 CUDA [Q]: the query's closed box meets the closed box of a key of its group; out float64 CUDA [Q, K]: the elementwise
     maximum of the payload over those keys, -inf without one -- None without a payload).  evaluate.box_match_numpy gives the same bytes.
     times = a dict that receives "sort_ms" and "kernel_ms"."""
-    _require_gpu()
-    lib = load_library()
-    assert qbox.is_cuda and qbox.dtype == torch.float64 and kbox.dtype == torch.float64 and qgroup.dtype == torch.int32 and kgroup.dtype == torch.int32
-    qbox, qgroup = qbox.contiguous(), qgroup.contiguous()
-    Q, N, G = qbox.shape[0], kbox.shape[0], int(G)
-    assert qbox.shape == (Q, 4) and kbox.shape == (N, 4) and qgroup.shape == (Q,) and kgroup.shape == (N,)
-    if G < 0 or (N and not (0 <= int(kgroup.min()) and int(kgroup.max()) < G)):
-        raise ValueError(f"box match: the keys' group ids have to lie in [0, {G})")
+    lib, qbox, qgroup, Q, N, G = _join_inputs("box match", qbox, qgroup, kbox, kgroup, G)
     K = 0
     if payload is not None:
         assert payload.is_cuda and payload.dtype == torch.float64 and payload.ndim == 2 and payload.shape[0] == N
@@ -1429,21 +1463,16 @@ def box_match(qbox: torch.Tensor, qgroup: torch.Tensor, kbox: torch.Tensor, kgro
     out = torch.empty((Q, K), dtype=torch.float64, device=qbox.device) if payload is not None else None
     if Q == 0:
         return hit, out
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
-    if ev:
-        ev[0].record()
+    ph = _Phases(times)
+    ph.mark()
     order, start = box_match_sort(kbox, kgroup, G)
     kb = kbox[order].contiguous()
     pl = payload[order].contiguous() if payload is not None else None
-    if ev:
-        ev[1].record()
+    ph.mark()
     _check(lib.aq_box_match_f64(qbox.data_ptr(), qgroup.data_ptr(), Q, kb.data_ptr() if N else None, N, start.data_ptr(), G,
                                 pl.data_ptr() if pl is not None and N else None, K, hit.data_ptr(), out.data_ptr() if out is not None else None,
                                 _stream_ptr()))
-    if ev:
-        ev[2].record()
-        ev[2].synchronize()
-        times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+    ph.done("sort_ms", "kernel_ms")
     for t_ in (qbox, qgroup, kb, start, hit) + ((pl, out) if pl is not None else ()):
         t_.record_stream(torch.cuda.current_stream())
     return hit, out
@@ -1468,38 +1497,7 @@ def eval_member_conf_subsets(xy: torch.Tensor, group: torch.Tensor, conf: torch.
     int64 in [0, 2^32): bit s set = the point is in subset s) and S in 1 .. 32 -> M float64 CUDA [S, n, K]: M[s, i] = eval_member_conf's row of
     point i among the points of subset s alone, -inf for a point outside s; evaluate.member_conf_subsets_numpy gives the same bytes.  One sort
     (facility_sort_keys), one gather and one set of key runs for all subsets.  times = a dict that receives "sort_ms" and "kernel_ms"."""
-    _require_gpu()
-    lib = load_library()
-    assert xy.is_cuda and group.is_cuda and conf.is_cuda and xy.dtype == torch.float64 and group.dtype == torch.int32 and conf.dtype == torch.float64
-    xy, group, conf = xy.contiguous(), group.contiguous(), conf.contiguous()
-    n = xy.shape[0]
-    assert xy.shape == (n, 2) and group.shape == (n,) and conf.shape == (n,)
-    if not eps > 0 or not 1 <= int(K) <= EVAL_MAX_K or not 1 <= int(S) <= EVAL_MAX_S:        # the library refuses these too; here before the sort
-        raise ValueError(f"evaluate subsets: eps = {eps}, K = {K}, S = {S} (eps > 0, 1 <= K <= {EVAL_MAX_K} and 1 <= S <= {EVAL_MAX_S})")
-    words = _subset_words(mask, n, "mask")
-    M = torch.empty((int(S), n, int(K)), dtype=torch.float64, device=xy.device)
-    if n == 0:
-        _check(lib.aq_eval_member_conf_subsets_f64(None, None, None, None, None, None, 0, float(eps), int(K), int(S), None, 0, None, _stream_ptr()))
-        return M
-    need = int(lib.aq_eval_subsets_scratch_bytes(n, int(K), int(S)))
-    if need == 0:
-        raise ValueError(f"evaluate subsets: {n} points x {K} sizes x {S} subsets is more than one call takes")
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
-    if ev:
-        ev[0].record()
-    keys, perm = facility_sort_keys(xy, group, eps)
-    scratch = torch.empty(need, dtype=torch.uint8, device=xy.device)
-    if ev:
-        ev[1].record()
-    _check(lib.aq_eval_member_conf_subsets_f64(keys.data_ptr(), perm.data_ptr(), xy.data_ptr(), group.data_ptr(), conf.data_ptr(), words.data_ptr(), n,
-                                               float(eps), int(K), int(S), scratch.data_ptr(), scratch.numel(), M.data_ptr(), _stream_ptr()))
-    if ev:
-        ev[2].record()
-        ev[2].synchronize()
-        times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
-    for t_ in (keys, perm, xy, group, conf, words, scratch, M):
-        t_.record_stream(torch.cuda.current_stream())
-    return M
+    return _eval_member_conf(xy, group, conf, eps, K, times, mask, S)
 
 
 def box_match_subsets(qbox: torch.Tensor, qgroup: torch.Tensor, qmask: torch.Tensor, kbox: torch.Tensor, kgroup: torch.Tensor, kmask: torch.Tensor,
@@ -1509,16 +1507,8 @@ def box_match_subsets(qbox: torch.Tensor, qgroup: torch.Tensor, qmask: torch.Ten
     uint32 word qmask & OR of the matching keys' kmask; out float64 CUDA [S, Q, K]: per subset the elementwise maximum of its payload over the
     matching keys of that subset, -inf without one or for a query outside it -- None without a payload).
     evaluate.box_match_subsets_numpy gives the same bytes.  times = a dict that receives "sort_ms" and "kernel_ms"."""
-    _require_gpu()
-    lib = load_library()
-    assert qbox.is_cuda and qbox.dtype == torch.float64 and kbox.dtype == torch.float64 and qgroup.dtype == torch.int32 and kgroup.dtype == torch.int32
-    qbox, qgroup = qbox.contiguous(), qgroup.contiguous()
-    Q, N, G, S = qbox.shape[0], kbox.shape[0], int(G), int(S)
-    assert qbox.shape == (Q, 4) and kbox.shape == (N, 4) and qgroup.shape == (Q,) and kgroup.shape == (N,)
-    if not 1 <= S <= EVAL_MAX_S:
-        raise ValueError(f"box match subsets: S = {S} subsets (1 to {EVAL_MAX_S})")
-    if G < 0 or (N and not (0 <= int(kgroup.min()) and int(kgroup.max()) < G)):
-        raise ValueError(f"box match subsets: the keys' group ids have to lie in [0, {G})")
+    S = int(S)
+    lib, qbox, qgroup, Q, N, G = _join_inputs("box match subsets", qbox, qgroup, kbox, kgroup, G, S)
     qwords, kwords = _subset_words(qmask, Q, "qmask"), _subset_words(kmask, N, "kmask")
     K = 0
     if payload is not None:
@@ -1532,21 +1522,16 @@ def box_match_subsets(qbox: torch.Tensor, qgroup: torch.Tensor, qmask: torch.Ten
     out = torch.empty((S, Q, K), dtype=torch.float64, device=qbox.device) if payload is not None else None
     if Q == 0:
         return hit, out
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
-    if ev:
-        ev[0].record()
+    ph = _Phases(times)
+    ph.mark()
     order, start = box_match_sort(kbox, kgroup, G)
     kb, km = kbox[order].contiguous(), kwords[order].contiguous()
     pl = payload[:, order].contiguous() if payload is not None else None
-    if ev:
-        ev[1].record()
+    ph.mark()
     _check(lib.aq_box_match_subsets_f64(qbox.data_ptr(), qgroup.data_ptr(), qwords.data_ptr(), Q, kb.data_ptr() if N else None, km.data_ptr() if N else None,
                                         N, start.data_ptr(), G, pl.data_ptr() if pl is not None and N else None, K, S, hit.data_ptr(),
                                         out.data_ptr() if out is not None else None, _stream_ptr()))
-    if ev:
-        ev[2].record()
-        ev[2].synchronize()
-        times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+    ph.done("sort_ms", "kernel_ms")
     for t_ in (qbox, qgroup, qwords, kb, km, start, hit) + ((pl, out) if pl is not None else ()):
         t_.record_stream(torch.cuda.current_stream())
     return hit, out
@@ -1562,34 +1547,23 @@ def model_error_match(qbox: torch.Tensor, qgroup: torch.Tensor, qarea: torch.Ten
     equals, -1 without one; overlap float64 CUDA [Q]: 100 x the intersection's share of the query's box; error float64 CUDA [Q]:
     karea[match] - qarea; both NaN without a match).  model_errors.match_numpy gives the same bytes.  times = a dict that receives "sort_ms"
     and "kernel_ms"."""
-    _require_gpu()
-    lib = load_library()
-    assert qbox.is_cuda and qbox.dtype == torch.float64 and kbox.dtype == torch.float64 and qgroup.dtype == torch.int32 and kgroup.dtype == torch.int32
-    assert qarea.dtype == torch.float64 and karea.dtype == torch.float64
-    qbox, qgroup, qarea = qbox.contiguous(), qgroup.contiguous(), qarea.contiguous()
-    Q, N, G = qbox.shape[0], kbox.shape[0], int(G)
-    assert qbox.shape == (Q, 4) and kbox.shape == (N, 4) and qgroup.shape == (Q,) and kgroup.shape == (N,) and qarea.shape == (Q,) and karea.shape == (N,)
-    if G < 0 or (N and not (0 <= int(kgroup.min()) and int(kgroup.max()) < G)):
-        raise ValueError(f"model errors: the keys' group ids have to lie in [0, {G})")
+    assert qarea.dtype == torch.float64 and karea.dtype == torch.float64 and qarea.shape == qbox.shape[:1] and karea.shape == kbox.shape[:1]
+    lib, qbox, qgroup, Q, N, G = _join_inputs("model errors", qbox, qgroup, kbox, kgroup, G)
+    qarea = qarea.contiguous()
     match = torch.empty(Q, dtype=torch.int32, device=qbox.device)
     overlap = torch.empty(Q, dtype=torch.float64, device=qbox.device)
     error = torch.empty(Q, dtype=torch.float64, device=qbox.device)
     if Q == 0:
         return match, overlap, error
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
-    if ev:
-        ev[0].record()
+    ph = _Phases(times)
+    ph.mark()
     order, start = box_match_sort(kbox, kgroup, G)
     kb, ka, kr = kbox[order].contiguous(), karea[order].contiguous(), order.to(torch.int32)
-    if ev:
-        ev[1].record()
+    ph.mark()
     _check(lib.aq_model_error_match_f64(qbox.data_ptr(), qgroup.data_ptr(), qarea.data_ptr(), Q, kb.data_ptr() if N else None,
                                         kr.data_ptr() if N else None, ka.data_ptr() if N else None, N, start.data_ptr(), G,
                                         match.data_ptr(), overlap.data_ptr(), error.data_ptr(), _stream_ptr()))
-    if ev:
-        ev[2].record()
-        ev[2].synchronize()
-        times["sort_ms"], times["kernel_ms"] = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+    ph.done("sort_ms", "kernel_ms")
     for t_ in (qbox, qgroup, qarea, kb, ka, kr, start, match, overlap, error):
         t_.record_stream(torch.cuda.current_stream())
     return match, overlap, error
@@ -1614,15 +1588,11 @@ def model_error_moments(error: torch.Tensor, match: torch.Tensor, mgroup: torch.
     sd = torch.empty(G, dtype=torch.float64, device=error.device)
     if G == 0:
         return n, mean, sd
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if times is not None else None
-    if ev:
-        ev[0].record()
+    ph = _Phases(times)
+    ph.mark()
     _check(lib.aq_model_error_moments_f64(error.data_ptr() if Q else None, match.data_ptr() if Q else None, mgroup.data_ptr() if Q else None, Q, G,
                                           n.data_ptr(), mean.data_ptr(), sd.data_ptr(), _stream_ptr()))
-    if ev:
-        ev[1].record()
-        ev[1].synchronize()
-        times["kernel_ms"] = ev[0].elapsed_time(ev[1])
+    ph.done("kernel_ms")
     for t_ in (error, match, mgroup, n, mean, sd):
         t_.record_stream(torch.cuda.current_stream())
     return n, mean, sd

@@ -2,6 +2,7 @@
 engine.eval_member_conf_subsets / engine.box_match_subsets against the numpy restatements, bit for bit; under the poisoned allocator; their
 refusals through the C ABI; the cross-validation's three files against the host path's, and the two command lines in child processes under
 their own time limits.  Shapes are the smallest at which the kernels can go wrong."""
+import functools
 import json
 import os
 import re
@@ -15,7 +16,7 @@ import torch
 from poison import poisoned
 from test_evaluate import SMALL_GRID, detection_table, fixture_data, truth
 from test_facilities import CASES, TIE
-from test_gpu_evaluate import GRID_ARGS, GRIDS, confidences, lattice_truth, member_gpu
+from test_gpu_evaluate import GRID_ARGS, GRIDS, confidences, lattice_truth, match_gpu, member_gpu
 from test_gpu_facilities import synthetic_run
 from test_kfold import kfold_inputs, subset_masks
 
@@ -181,6 +182,93 @@ def test_box_match_subsets_of_the_fixture_respects_the_subsets(lib):
     check_match(lab["box"], lab["group"], lm, det["box"], det["group"], dm, G, 12, M)
     whole = evaluate.box_match_numpy(det["box"], det["group"], lab["box"], lab["group"])[0]
     assert ((hit != 0) <= whole).all() and (whole & (hit != dm)).any()      # a detection of a subset whose labels lie in others
+
+
+# ---- one kernel source for both forms: all-ones masks give the plain entries' bytes ----
+
+ALL = 0xFFFFFFFF
+
+
+def lattice_points():
+    """257 points (a full workgroup of 256 and one thread of the next) of a 0.5 m lattice, two groups, eps = 1.0: a point has up to 13
+    neighbours, four of them at exactly eps, and the confidences take 7 values, so that equal confidences meet in every list."""
+    i = np.arange(257)
+    xy = np.stack([i % 17, i // 17], 1) * 0.5 + [4.0e6, 2.2e6]
+    conf = np.array([0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9])[np.random.default_rng(12).integers(0, 7, 257)]
+    return xy, (i >= 128).astype(np.int32), conf, 1.0
+
+
+@pytest.mark.parametrize("K", [1, 3, 5, 16])                 # one per list size the launcher instantiates: 1, 4, 8, 16
+def test_member_conf_with_all_ones_masks_is_the_plain_entrys_bytes(lib, K):
+    xy, group, conf, eps = lattice_points()
+    want = evaluate.member_conf_numpy(xy, group, conf, eps, K)
+    assert np.unique(conf).size == 7 and np.isfinite(want[:, 0]).all() and (K < 14 or (want[:, 13:] == NEG_INF).all())
+    plain = member_gpu(xy, group, conf, eps, K).cpu().numpy()
+    assert plain.tobytes() == want.tobytes()
+    for S in (1, 32):
+        sub = member_subsets_gpu(xy, group, conf, np.full(257, ALL, np.uint32), eps, K, S).cpu().numpy()
+        assert sub.shape == (S, 257, K)
+        for s in range(S):
+            assert sub[s].tobytes() == plain.tobytes(), s
+
+
+@functools.lru_cache(None)
+def join_case(N):
+    """5 queries (a second workgroup with one busy wave) against a run of N keys of group 0 (group 1 has none), integer boxes, 3 payload
+    columns.  Query 0 covers every key, 1 touches the key with the largest x0 -- the last of the sorted run -- at a corner, 2 touches the
+    first key along an edge, 3 covers everything but is of group 1, 4 lies apart."""
+    r = np.random.default_rng(7)
+    x0, y0 = r.integers(0, 12, N), r.integers(0, 12, N)
+    k = np.stack([x0, y0, x0 + r.integers(1, 4, N), y0 + r.integers(1, 4, N)], 1).astype(np.float64)
+    if N:
+        k[-1] = [14.0, 3.0, 16.0, 5.0]                      # alone at the largest x0
+    last, first = (k[-1], k[0]) if N else (np.array([14.0, 3.0, 16.0, 5.0]), np.array([0.0, 0.0, 1.0, 1.0]))
+    q = np.array([[0.0, 0.0, 20.0, 20.0], [last[2], last[3], last[2] + 1.0, last[3] + 1.0], [first[0] - 1.0, first[1], first[0], first[3]],
+                  [0.0, 0.0, 20.0, 20.0], [30.0, 30.0, 31.0, 31.0]])
+    qg = np.array([0, 0, 0, 1, 0], np.int32)
+    return q, qg, k, np.zeros(N, np.int32), r.permutation(3 * N).reshape(N, 3).astype(np.float64)
+
+
+@functools.lru_cache(None)
+def join_reference(N):
+    """box_match_numpy of join_case(N), and that the case holds what it is built for: no case but N = 0 is empty."""
+    q, qg, k, kg, pay = join_case(N)
+    hit, out = evaluate.box_match_numpy(q, qg, k, kg, pay)
+    if N == 0:
+        assert not hit.any() and (out == NEG_INF).all()
+        return hit, out
+    assert hit.tolist() == [True, True, True, False, False]
+    w = np.minimum(q[1:3, None, 2], k[None, :, 2]) - np.maximum(q[1:3, None, 0], k[None, :, 0])
+    h = np.minimum(q[1:3, None, 3], k[None, :, 3]) - np.maximum(q[1:3, None, 1], k[None, :, 1])
+    meet = (w >= 0) & (h >= 0)
+    assert (meet & (w * h == 0)).any(1).all()               # queries 1 and 2 each touch a key without overlapping it: a corner, an edge
+    # query 1 meets the last key of the sorted run and no other: with N = 65 that is position 64, the second step of lane 0
+    assert np.lexsort((k[:, 0], kg))[-1] == N - 1 and meet[0].nonzero()[0].tolist() == [N - 1] and np.array_equal(out[1], pay[N - 1])
+    return hit, out
+
+
+@pytest.mark.parametrize("N", [0, 63, 65])                   # no key; one short of the lanes' stride; one past it
+def test_box_match_with_all_ones_masks_is_the_plain_entrys_bytes(lib, N):
+    q, qg, k, kg, pay = join_case(N)
+    want_hit, want_out = join_reference(N)
+    hit, out = match_gpu(q, qg, k, kg, 2, pay)
+    assert np.array_equal(hit, want_hit) and out.tobytes() == want_out.tobytes()
+    for S in (1, 32):
+        hitmask, outs = match_subsets_gpu(q, qg, np.full(5, ALL, np.uint32), k, kg, np.full(N, ALL, np.uint32), 2, S, np.tile(pay, (S, 1, 1)))
+        assert np.array_equal(hitmask, np.where(hit, np.uint32(ALL >> (32 - S)), np.uint32(0)))
+        assert outs.shape == (S, 5, 3)
+        for s in range(S):
+            assert outs[s].tobytes() == out.tobytes(), s
+
+
+@pytest.mark.parametrize("N", [0, 63, 65])
+def test_model_error_match_has_box_matchs_candidates(lib, N):
+    from aquaculture_amd.engine import model_error_match
+    q, qg, k, kg, _ = join_case(N)
+    want_hit, _ = join_reference(N)
+    match = model_error_match(dev(q, np.float64), dev(qg, np.int32), dev(np.ones(5), np.float64), dev(k.reshape(-1, 4), np.float64), dev(kg, np.int32),
+                              dev(np.ones(N), np.float64), 2)[0].cpu().numpy()
+    assert np.array_equal(match >= 0, want_hit) and np.array_equal(match_gpu(q, qg, k, kg, 2)[0], want_hit)
 
 
 # ---- the poisoned allocator ----

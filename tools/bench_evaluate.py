@@ -54,7 +54,7 @@ def scaled_inputs(copies):
 
 
 def spread(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
+    return {"median": statistics.median(v), "min": min(v), "max": max(v), "values": list(v)}
 
 
 def per_combination(data, conf, eps, m):

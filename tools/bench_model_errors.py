@@ -49,7 +49,7 @@ def scaled_inputs(labels):
 
 
 def spread(v):
-    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
+    return {"median": statistics.median(v), "min": min(v), "max": max(v), "values": list(v)}
 
 
 def run_size(labels, repeats, cpu):
