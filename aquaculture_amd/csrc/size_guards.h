@@ -135,4 +135,8 @@ inline bool eval_subsets_fit(ll n, ll K, ll S) {
 inline bool overlap_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }
 inline bool overlap_bands_fit(ll nbands) { return nbands >= 1 && nbands + 1 < (1LL << 31); }
 
+// ---- facility_sites.hip ----  (facilities, entries, queries, keys, groups and list entries of a call are 31-bit indices; like dedup's, no
+// line in oracle/guards.py: tests/test_gpu_facility_sites.py walks the edge through the launchers' refusals)
+inline bool facility_sites_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }
+
 }  // namespace sg

@@ -162,6 +162,14 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "model_errors.json, and --tonnage uses the table as its model errors; needs --geocode-bboxes, excludes --tonnage-errors")
     from .model_errors import add_options as _model_error_options
     _model_error_options(p)
+    p.add_argument("--facility-sites", default=None, metavar="CSV",
+                   help="directly after --facilities, on its facility table: which facilities lie within 1 km of a site the literature already "
+                        "knew (CSV: lat, lon, num_cages; the reference's data/aquaculture_med_dedupe.csv) and which are additional production "
+                        "locations, and how many distinct additional locations there are (the data behind the reference's "
+                        "src/Results/FacilitiesMaps.py, without the plots), the facility rectangles and the box joins on the GPU; writes "
+                        "facility_sites.geojson, facility_sites.csv and facility_sites.json; needs --facilities and --geocode-bboxes")
+    from .facility_sites import add_options as _facility_sites_options
+    _facility_sites_options(p)
     p.add_argument("--tonnage", nargs="?", const="", default=None, metavar="DIR",
                    help="after the sweep, its geocoding and the land filter, cluster the detections into facilities per image pass and estimate "
                         "their live-weight production per pass by the reference's bootstrap (src/utils_tonnage.py, "
@@ -219,6 +227,8 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error(MODEL_ERRORS_NEED_GEOCODE)
     if opt.model_errors is not None and opt.tonnage_errors:
         p.error(MODEL_ERRORS_OR_FILE)
+    if opt.facility_sites is not None and (opt.facilities is None or not opt.geocode_bboxes):
+        p.error(FACILITY_SITES_NEED_FACILITIES)
     if opt.evaluate_kfold is not None and opt.evaluate is None:
         p.error(KFOLD_NEEDS_EVALUATE)
     if opt.evaluate_kfold is not None and opt.tile_scenes and not opt.evaluate_kfold_images:
@@ -247,6 +257,8 @@ KFOLD_SCENES_NEED_IMAGES = ("--evaluate-kfold with --tile-scenes: the tiles cut 
 DEDUP_OVERLAPS_NEEDS_GEOCODE = "--dedup-overlaps needs --geocode-bboxes CSV: the download boxes whose overlaps it resolves (and --save-txt --save-conf)"
 MODEL_ERRORS_NEED_GEOCODE = "--model-errors joins geocoded detections to the labels: it needs --geocode-bboxes CSV (and --save-txt --save-conf)"
 MODEL_ERRORS_OR_FILE = "the model errors of --tonnage come from --model-errors or from --tonnage-errors, not from both"
+FACILITY_SITES_NEED_FACILITIES = ("--facility-sites compares the facilities of --facilities with the known sites inside the download boxes: it needs "
+                                  "--facilities and --geocode-bboxes CSV (and --save-txt --save-conf)")
 
 
 def run_params(weights_id, conf_thres, iou_thres, max_det, imgsz, precision, save_conf, classes=None, agnostic_nms=False, augment=False,
@@ -277,7 +289,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         evaluate_kfold_test=0.1, tonnage=None, tonnage_factors=None, tonnage_errors=None, tonnage_depths=None, tonnage_default_depth=4.84,
         tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, bathymetry=None, bathymetry_statistic="bathy_min", dedup_years=None,
         dedup_selection="random", dedup_seed=0, model_errors=None, model_errors_conf=None, model_errors_out=None, tonnage_missing=None,
-        tonnage_near_sites=None, dedup_overlaps=None, log=print, **unsupported):
+        tonnage_near_sites=None, dedup_overlaps=None, facility_sites=None, facility_sites_truth=None, facility_sites_out=None, log=print,
+        **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb_checked, jpeg_slots_to_rgb, JPEG_WS_MAX, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
     if dedup_years is not None and not geocode_bboxes:
@@ -297,6 +310,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         blank_geom = ""
     if blank_geom is not None and blank_key is None:     # the outlines are made for the images the key calls partly blank
         blank_key = ""
+    if facility_sites is not None and (facilities is None or not geocode_bboxes):
+        raise ValueError(FACILITY_SITES_NEED_FACILITIES)
     if facilities is not None and not geocode_bboxes:
         raise ValueError("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if land_filter is not None and not geocode_bboxes:
@@ -1173,6 +1188,13 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                                                   hw[table["image"], 1], hw[table["image"], 0], keep=ocean, bathymetry=bathy, dedup=dd)
                 log(f"{len(fac['facility_index'])} facilities of {int((fac['_members'] >= 0).sum())} cages in {fac_out} "
                     f"in {time.perf_counter() - t_f:.2f}s")
+                if facility_sites is not None:
+                    # known against additional facilities (reference src/Results/FacilitiesMaps.py:64-188) on the table just made
+                    from . import facility_sites as aqsites
+                    t_s = time.perf_counter()
+                    fs_out = facility_sites_out or str(save_dir)
+                    fs_res = aqsites.facility_sites_from_table(fac, table, facility_sites, geocode_bboxes, fs_out, facility_sites_truth)
+                    log(f"{aqsites.describe(fs_res)} in {fs_out} in {time.perf_counter() - t_s:.2f}s")
             if evaluate is not None:
                 # the reference's tuning step (src/get_kfold_cluster_performance.py) on the same table, the ocean rows when there are any
                 from . import evaluate as aqeval

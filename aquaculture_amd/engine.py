@@ -86,6 +86,7 @@ EXPORTS = (
     "aq_dedup_fill_u32", "aq_dedup_sets_u32", "aq_dedup_select_f64",
     "aq_coverage_first_i32",
     "aq_overlap_partners_f64", "aq_overlap_clip_f64",
+    "aq_facility_bounds_f64", "aq_box_join_count_i32", "aq_box_join_list_i32",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -240,6 +241,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                           vp, vp, C.c_longlong, vp, sz, vp, vp]
     lib.aq_overlap_partners_f64.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, C.c_double, C.c_double, vp, vp, C.c_longlong, vp]
     lib.aq_overlap_clip_f64.argtypes = [vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp, vp, vp, vp]
+    lib.aq_facility_bounds_f64.argtypes = [vp, vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp]
+    lib.aq_box_join_count_i32.argtypes = [vp, vp, C.c_longlong, vp, vp, vp, vp, C.c_longlong, C.c_longlong, vp, vp, vp]
+    lib.aq_box_join_list_i32.argtypes = [vp, vp, C.c_longlong, vp, vp, vp, vp, C.c_longlong, C.c_longlong, vp, vp, vp, C.c_longlong, vp]
     lib.aq_augment_geometry.argtypes = [i32, i32, i32, vp, C.POINTER(i32)]
     lib.aq_augment_taps.argtypes = [i32, i32, i32, vp]
     lib.aq_stem_conv_scaled.argtypes = [vp, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]
@@ -1904,6 +1908,111 @@ def overlap_clip(boxes: torch.Tensor, start: torch.Tensor, partner: torch.Tensor
     for t_ in (boxes, start, partner, det_row, dets, state, bounds, area, has_region):
         t_.record_stream(torch.cuda.current_stream())
     return state, bounds, area, has_region
+
+
+# ---- --facility-sites: aq_facility_bounds_f64, aq_box_join_count_i32, aq_box_join_list_i32 (known and additional facilities) ----
+
+def _sites_tensor(name: str, t_: torch.Tensor, dt, shape) -> None:
+    if not t_.is_cuda or t_.dtype != dt or not t_.is_contiguous() or t_.ndim != len(shape) or any(a != b for a, b in zip(t_.shape, shape)):
+        raise ValueError(f"facility sites: {name} has to be a contiguous CUDA {dt} tensor of shape {shape}, not {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+
+
+def facility_bounds(entry_start: torch.Tensor, entry_box: torch.Tensor, entry_use: torch.Tensor, entry_start_host: np.ndarray,
+                    times: Optional[dict] = None) -> torch.Tensor:
+    """aq_facility_bounds_f64 on the current stream: entry_start int32 CUDA [F + 1] (facility f owns the entries entry_start[f] ..
+    entry_start[f + 1] - 1), entry_box float64 CUDA [E, 4] (x0, y0, x1, y1), entry_use uint8 CUDA [E] (0: the entry does not take part);
+    entry_start_host holds the starts in host memory -> bounds float64 CUDA [F, 4]: the rectangle around the facility's entries that take
+    part, four NaNs without one.  include/aq_engine.h states the contract; facility_sites.bounds_numpy gives the same bytes.  times = a dict
+    that receives "bounds_ms" (HIP events; the call then waits for them)."""
+    _require_gpu()
+    F, E = int(entry_start.shape[0]) - 1, int(entry_box.shape[0])
+    if F < 0:
+        raise ValueError("facility sites: entry_start needs at least one entry")
+    for name, t_, dt, shape in (("entry_start", entry_start, torch.int32, (F + 1,)), ("entry_box", entry_box, torch.float64, (E, 4)),
+                                ("entry_use", entry_use, torch.uint8, (E,))):
+        _sites_tensor(name, t_, dt, shape)
+    es = np.ascontiguousarray(entry_start_host, dtype=np.int32)
+    if es.shape != (F + 1,):
+        raise ValueError("facility sites: the host copy does not have the entry starts' shape")
+    bounds = torch.empty((F, 4), dtype=torch.float64, device=entry_start.device)
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    ph = _Phases(times)
+    ph.mark()
+    _check(load_library().aq_facility_bounds_f64(ptr(entry_start), es.ctypes.data, F, ptr(entry_box), ptr(entry_use), E, ptr(bounds), _stream_ptr()))
+    ph.done("bounds_ms")
+    for t_ in (entry_start, entry_box, entry_use, bounds):
+        t_.record_stream(torch.cuda.current_stream())
+    return bounds
+
+
+def box_join_keys(kbox: torch.Tensor, kgroup: torch.Tensor, G: int) -> dict:
+    """The keys of box_join_count / box_join_list, sorted once for both: kbox float64 CUDA [N, 4], kgroup int32 CUDA [N] with ids in [0, G),
+    in any order -> {"box": the boxes in box_match_sort's order, "kid" int32 [N]: their original rows, "start" int32 CUDA [G + 1],
+    "start_host" the same in host memory, "N", "G"}."""
+    _require_gpu()
+    N, G = int(kbox.shape[0]), int(G)
+    _sites_tensor("kbox", kbox, torch.float64, (N, 4))
+    _sites_tensor("kgroup", kgroup, torch.int32, (N,))
+    if G < 0 or (N and not (0 <= int(kgroup.min()) and int(kgroup.max()) < G)):
+        raise ValueError(f"facility sites: the keys' group ids have to lie in [0, {G})")
+    order, start = box_match_sort(kbox, kgroup, G)
+    return {"box": kbox[order].contiguous(), "kid": order.to(torch.int32), "start": start.contiguous(),
+            "start_host": np.ascontiguousarray(start.cpu().numpy(), dtype=np.int32), "N": N, "G": G}
+
+
+def _box_join_queries(qbox: torch.Tensor, qgroup: torch.Tensor, kbox, kgroup, G, keys: Optional[dict]):
+    _require_gpu()
+    Q = int(qbox.shape[0])
+    _sites_tensor("qbox", qbox, torch.float64, (Q, 4))
+    _sites_tensor("qgroup", qgroup, torch.int32, (Q,))
+    keys = box_join_keys(kbox, kgroup, G) if keys is None else keys
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    args = (ptr(qbox), ptr(qgroup), Q, ptr(keys["box"]), ptr(keys["kid"]), keys["start"].data_ptr(), keys["start_host"].ctypes.data, keys["N"], keys["G"])
+    return Q, keys, args
+
+
+def box_join_count(qbox: torch.Tensor, qgroup: torch.Tensor, kbox: Optional[torch.Tensor] = None, kgroup: Optional[torch.Tensor] = None, G: int = 0,
+                   keys: Optional[dict] = None, times: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """aq_box_join_count_i32 on the current stream: qbox float64 CUDA [Q, 4] (x0, y0, x1, y1), qgroup int32 CUDA [Q], and the keys -- kbox,
+    kgroup, G in any order, or keys = box_join_keys' result -> (count int32 CUDA [Q]: the keys of the query's group whose closed box meets
+    the query's; first int32 CUDA [Q]: the smallest row among them, -1 without one).  facility_sites.join_count_numpy gives the same bytes.
+    times = a dict that receives "count_ms"."""
+    Q, keys, args = _box_join_queries(qbox, qgroup, kbox, kgroup, G, keys)
+    count = torch.empty(Q, dtype=torch.int32, device=qbox.device)
+    first = torch.empty(Q, dtype=torch.int32, device=qbox.device)
+    ph = _Phases(times)
+    ph.mark()
+    _check(load_library().aq_box_join_count_i32(*args, count.data_ptr() if Q else None, first.data_ptr() if Q else None, _stream_ptr()))
+    ph.done("count_ms")
+    for t_ in (qbox, qgroup, keys["box"], keys["kid"], keys["start"], count, first):
+        t_.record_stream(torch.cuda.current_stream())
+    return count, first
+
+
+def box_join_list(qbox: torch.Tensor, qgroup: torch.Tensor, kbox: Optional[torch.Tensor] = None, kgroup: Optional[torch.Tensor] = None, G: int = 0,
+                  keys: Optional[dict] = None, count: Optional[torch.Tensor] = None, times: Optional[dict] = None) -> Tuple[np.ndarray, torch.Tensor]:
+    """aq_box_join_list_i32 on the current stream, after box_join_count (count = its first result, computed here when not given): the
+    same arguments -> (offset int64 [Q + 1] in host memory: the exclusive scan of the counts; list int32 CUDA [offset[Q]]: the rows of the
+    keys that meet query q at list[offset[q] : offset[q + 1]], in the order of the sorted keys).  The counts cross to the host between the
+    two launches.  facility_sites.join_list_numpy gives the same arrays.  times = a dict that receives "list_ms" (and "count_ms")."""
+    Q, keys, args = _box_join_queries(qbox, qgroup, kbox, kgroup, G, keys)
+    if count is None:
+        count = box_join_count(qbox, qgroup, keys=keys, times=times)[0]
+    _sites_tensor("count", count, torch.int32, (Q,))
+    offset_h = np.zeros(Q + 1, np.int64)
+    np.cumsum(count.cpu().numpy(), dtype=np.int64, out=offset_h[1:])
+    total = int(offset_h[-1])
+    if total >= 1 << 31:
+        raise ValueError(f"facility sites: {total} list entries (fewer than 2^31 in one call): pass fewer queries at a time")
+    offset = torch.from_numpy(offset_h).to(qbox.device)
+    out = torch.empty(total, dtype=torch.int32, device=qbox.device)
+    ph = _Phases(times)
+    ph.mark()
+    _check(load_library().aq_box_join_list_i32(*args, offset.data_ptr(), offset_h.ctypes.data, out.data_ptr() if total else None, total, _stream_ptr()))
+    ph.done("list_ms")
+    for t_ in (qbox, qgroup, keys["box"], keys["kid"], keys["start"], offset, out):
+        t_.record_stream(torch.cuda.current_stream())
+    return offset_h, out
 
 
 # ---- --land-filter: aq_land_filter_f64 (detection boxes against the segments of the land polygons) ----

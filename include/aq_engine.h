@@ -935,6 +935,57 @@ int aq_overlap_clip_f64(const double* boxes_dev, long long n, const long long* s
                         const int32_t* det_row_dev, const double* dets_dev, long long m, uint8_t* state_dev, double* bounds_dev,
                         double* area_dev, uint8_t* has_region_dev, void* stream);
 
+/* ---- --facility-sites: which facilities lie at a site the literature knew, which are additional (csrc/facility_sites.hip) ----
+ * The data behind the reference's map of known and additional production locations (src/Results/FacilitiesMaps.py: get_true_facilities
+ * :64-94, classify_our_facilities :117-188, count_unique_locations :97-114).  All boxes are closed, (x0, y0, x1, y1), fp64, EPSG:3857;
+ * meet(a, b) = a.x0 <= b.x1 && b.x0 <= a.x1 && a.y0 <= b.y1 && b.y0 <= a.y1: touching counts, a NaN meets nothing.  Definitions (DESIGN.md
+ * section 25; aquaculture_amd.facility_sites restates them in numpy and in plain loops):
+ *   bounds[f]      the minimum of xmin_3857 and ymin_3857 and the maximum of xmax_3857 and ymax_3857 over the facility's cage_ids of class
+ *                  circle or square (rectangle cages do not enter), by selections v < m ? v : m from +inf and v > m ? v : m from -inf, so
+ *                  a NaN coordinate is never selected.  No such cage, or a selection that is not finite: four NaNs, state no_bounds.
+ *   pass           the facility's pass column, or image_pass(year).  EARLY = 2000-2004, 2005-2009, 2010-2012; LATE = 2013-2015,
+ *                  2016-2018, 2019-2021; any other: state no_period.
+ *   true           (with a truth file only) label_hits[f] = the circle and square labels whose year's pass is f's pass and whose box
+ *                  bounds[f] meets; first_label[f] = the smallest such label row, -1 without; label_hits = 0: state not_true.
+ *   sites          the rows of the site file grouped by distinct (lat, lon) ascending, num_cages summed; those whose EPSG:3857 point lies
+ *                  inside the closed total bounds of the wanted-bboxes table, numbered in that order (site_index); the site box is
+ *                  (x - 1000, y - 1000, x + 1000, y + 1000) in EPSG:3857.  site_hits[f], first_site[f]: as above, one group.
+ *   type           early pass: site_hits = 0 additional, else known_early; late pass: site_hits > 0 known, else additional.
+ *   unique         per period, over its additional facilities: N(i) = the j of the set whose bounds meet bounds[i] (i is in N(i)); in
+ *                  ascending facility_index an unmarked i is unique and marks N(i); location[i] = i if unique, else the smallest unique
+ *                  g < i with i in N(g).  The walk is sequential and runs on the host over the lists the device wrote.
+ * Three launchers.  Each runs on `stream`, one launch, one wavefront per facility or query, no atomics, plain vector stores, no allocation;
+ * comparisons, selections, integer adds and minima only, so two calls give the same bytes and the numpy restatements (bounds_numpy,
+ * join_count_numpy, join_list_numpy) give them too.  Refused before anything is launched, by the arguments and the *_host copies alone:
+ * a count that is negative or >= 2^31, starts or offsets that decrease or leave their array, a null pointer, an unaligned array.  On the
+ * device every start and offset is kept inside its array all the same: tables the caller got wrong give wrong numbers but no access
+ * outside the arrays.
+ *
+ * aq_facility_bounds_f64: facility f owns the entries entry_start[f] .. entry_start[f + 1] - 1 (int32 [F + 1], the CSR layout of
+ * aq_depth_ranges_f64) of entry_box_dev [E][4] fp64 (32-byte aligned); entry_use_dev [E] uint8: 0 = the entry does not take part.  Lane l of
+ * 64 walks the entries start + l, start + l + 64, ... in ascending order under the selections above; the 64 partials fold by halves,
+ * m[i] = m[i + 32] < m[i] ? m[i + 32] : m[i] (> for the maxima), then 16, ... 1.  bounds_dev [F][4] fp64 (32-byte aligned), the only
+ * memory written; every NaN is the canonical quiet NaN.  F = 0 does nothing. */
+int aq_facility_bounds_f64(const int32_t* entry_start_dev, const int32_t* entry_start_host, long long F, const double* entry_box_dev,
+                           const uint8_t* entry_use_dev, long long E, double* bounds_dev, void* stream);
+/* aq_box_join_count_i32: qbox_dev [Q][4], qgroup_dev [Q] int32, kbox_dev [N][4] sorted by (group, x0) with group_start [G + 1] int32 -- the
+ * queries, sorted keys and group starts of aq_box_match_f64 -- and kid_dev [N] int32, the original row of every sorted key.  count_dev [Q]
+ * int32 = the number of keys of the query's group that meet it (the run is cut at key.x0 <= query.x1 by a binary search, the lanes stride
+ * over the rest); first_dev [Q] int32 = the smallest kid among them, -1 when count is 0.  A group outside [0, G) and a NaN query: 0, -1.
+ * Q = 0 does nothing; N = 0: every count is 0. */
+int aq_box_join_count_i32(const double* qbox_dev, const int32_t* qgroup_dev, long long Q, const double* kbox_dev, const int32_t* kid_dev,
+                          const int32_t* group_start_dev, const int32_t* group_start_host, long long N, long long G, int32_t* count_dev,
+                          int32_t* first_dev, void* stream);
+/* aq_box_join_list_i32: the same join; the kid of every meeting key, in ascending position of the sorted run, goes to
+ * list_dev[offset[q] .. offset[q + 1]) (int32 [total]); offset [Q + 1] int64 (8-byte aligned) = the exclusive scan of
+ * aq_box_join_count_i32's counts, made by the caller.  Per chunk of 64 keys: a ballot of the lanes whose key meets the query, lane l's
+ * slot = running base + the number of set ballot bits below l, base += the ballot's popcount (uniform over the wavefront).  A slot at or
+ * beyond offset[q + 1] is not written, so a query writes inside its own slice whatever the offsets say, and the slice of a query without a
+ * match is left as it was.  Q = 0 does nothing. */
+int aq_box_join_list_i32(const double* qbox_dev, const int32_t* qgroup_dev, long long Q, const double* kbox_dev, const int32_t* kid_dev,
+                         const int32_t* group_start_dev, const int32_t* group_start_host, long long N, long long G,
+                         const long long* offset_dev, const long long* offset_host, int32_t* list_dev, long long total, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
