@@ -109,7 +109,8 @@ extern "C" int aq_conv_num_configs(void);
 // ---- launch-time device state (launch_state.hip): kept per device, under one mutex ----
 // Compute units the persistent grids are sized for: the device's count, or AQ_NUM_CUS when the caller runs this process's streams on a
 // subset of the CUs (hipExtStreamCreateWithCUMask: bench.py --cu-split gives each of the two batches in flight half of the chip).
-// Read once per device, so set the variable before the first launch.
+// Read once per device, so set the variable before the first launch.  Results do not depend on the count, bit for bit (which workgroup
+// computes a tile changes nothing): tests/test_gpu_cu_counts.py runs every launcher that calls this at 1, 2, 3 and 13 CUs against the device's own.
 hipError_t aq_cus(int* cus);
 // Raises fn's dynamic-LDS limit to max_dyn_lds (once per device and kernel).
 hipError_t aq_kernel_lds(const void* fn, int max_dyn_lds);
