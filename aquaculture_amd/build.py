@@ -41,6 +41,7 @@ SOURCES = [
     ("blank_geom.hip", []),                      # --blank-geom: connected components of the non-blank mask, the largest one and its outer edges
     ("facilities.hip", ["-ffp-contract=off"]),   # --facilities: DBSCAN of the detections' centroids; the fp64 distance test exactly as written (no fma)
     ("land_filter.hip", ["-ffp-contract=off"]),  # --land-filter: boxes against the land polygons' segments; the fp64 orientation determinant exactly as written (no fma)
+    ("land_images.hip", ["-ffp-contract=off"]),  # --land-images: image rectangles against the same segments; the fp64 squared distances and their one division exactly as written (no fma)
     ("evaluate.hip", ["-ffp-contract=off"]),     # --evaluate: member confidences over the facilities' neighbour search (the same fp64 distance test) and the box joins
     ("eval_subsets.hip", ["-ffp-contract=off"]), # --evaluate-kfold: the same two steps for up to 32 subsets (folds) of one point set per call, one bit of a mask word each
     ("model_errors.hip", ["-ffp-contract=off"]), # --model-errors: the best-overlap join (inter = two subtractions and one product) and the moments in one written order (no fma)

@@ -18,41 +18,16 @@
 //   flags    one wavefront per box; its 64 lanes stride over the run; the hit bit is a ballot (no more hit tests once it is set), the
 //            crossing count the sum of the ballots' popcounts over the run of band(y0)
 // No atomics at all and nothing that depends on order: two calls give the same bytes.
-#include "aq_common.h"
+#include "land_bands.h"                                                         // the table, the gather launch, start_of, orient: shared with land_images.hip
 
 namespace {
 
 struct LandParams {
-    const double* seg;         // [E][4]
-    const int* entry_seg;      // [entries]: segment of every entry, band by band
-    const int* band_start;     // [nbands + 1]
+    LandBands t;
     const double* boxes;       // [N][4]
-    double4* eseg;             // scratch [entries]: coordinates by entry
     unsigned char* flags;      // out [N]
-    long long entries;
-    int E, N, nbands;
-    double Y0, h;
+    int N;
 };
-
-__device__ __forceinline__ double orient(double ax, double ay, double bx, double by, double cx, double cy) {
-    return (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);
-}
-
-__global__ __launch_bounds__(256) void land_gather_kernel(const LandParams p) {
-    const long long i = blockIdx.x * 256LL + threadIdx.x;
-    if (i >= p.entries) return;
-    const int s = p.entry_seg[i];
-    const double nan = __builtin_nan("");
-    double4 v = {nan, nan, nan, nan};                                           // an entry that is no segment meets nothing and crosses nothing
-    if ((unsigned)s < (unsigned)p.E) v = *(const double4*)(p.seg + 4LL * s);
-    p.eseg[i] = v;
-}
-
-// first entry of band b, kept inside [0, entries] whatever the table holds
-__device__ __forceinline__ long long start_of(const LandParams& p, int b) {
-    const long long v = p.band_start[b];
-    return v < 0 ? 0 : v > p.entries ? p.entries : v;
-}
 
 __global__ __launch_bounds__(256) void land_flags_kernel(const LandParams p) {
     const long long box = blockIdx.x * 4LL + (threadIdx.x >> 6);                // one wavefront per box: everything below is uniform in it
@@ -60,23 +35,23 @@ __global__ __launch_bounds__(256) void land_flags_kernel(const LandParams p) {
     const int lane = threadIdx.x & 63;
     const double4 b = *(const double4*)(p.boxes + 4 * box);
     const double x0 = b.x, y0 = b.y, x1 = b.z, y1 = b.w;
-    const double t0 = floor((y0 - p.Y0) / p.h), t1 = floor((y1 - p.Y0) / p.h);
-    if (!(t1 >= 0.0) || !(t0 < (double)p.nbands)) {                             // wholly below or above all bands (or not a number): at sea
+    const double t0 = band_of(p.t, y0), t1 = band_of(p.t, y1);
+    if (!(t1 >= 0.0) || !(t0 < (double)p.t.nbands)) {                           // wholly below or above all bands (or not a number): at sea
         if (lane == 0) p.flags[box] = 0;
         return;
     }
     const int b0 = t0 < 0.0 ? 0 : (int)t0;
-    const int b1 = t1 < (double)p.nbands ? (int)t1 : p.nbands - 1;
-    const long long first = start_of(p, b0);
-    const long long end0 = start_of(p, b0 + 1);                                 // the run of band(y0): the crossing count
-    const long long end = b1 >= b0 ? start_of(p, b1 + 1) : end0;
+    const int b1 = t1 < (double)p.t.nbands ? (int)t1 : p.t.nbands - 1;
+    const long long first = start_of(p.t, b0);
+    const long long end0 = start_of(p.t, b0 + 1);                               // the run of band(y0): the crossing count
+    const long long end = b1 >= b0 ? start_of(p.t, b1 + 1) : end0;
     bool hit = false;
     int crossings = 0;
     for (long long base = first; base < end0; base += 64) {
         const long long e = base + lane;
         bool h_ = false, c_ = false;
         if (e < end0) {
-            const double4 s = p.eseg[e];
+            const double4 s = p.t.eseg[e];
             const double o = orient(s.x, s.y, s.z, s.w, x0, y0);
             const bool up = s.y <= y0;
             c_ = (up != (s.w <= y0)) && (up ? o > 0.0 : o < 0.0);
@@ -93,7 +68,7 @@ __global__ __launch_bounds__(256) void land_flags_kernel(const LandParams p) {
         const long long e = base + lane;
         bool h_ = false;
         if (e < end) {
-            const double4 s = p.eseg[e];
+            const double4 s = p.t.eseg[e];
             if ((s.x <= x1 || s.z <= x1) && (s.x >= x0 || s.z >= x0) && (s.y <= y1 || s.w <= y1) && (s.y >= y0 || s.w >= y0)) {
                 const double o = orient(s.x, s.y, s.z, s.w, x0, y0), o1 = orient(s.x, s.y, s.z, s.w, x1, y0);
                 const double o2 = orient(s.x, s.y, s.z, s.w, x1, y1), o3 = orient(s.x, s.y, s.z, s.w, x0, y1);
@@ -136,10 +111,10 @@ extern "C" int aq_land_filter_f64(const double* seg_dev, long long E, const int3
     const size_t need = aq_land_scratch_bytes(entries);
     AQ_REQUIRE(scratch_bytes >= need, "land filter: %zu bytes of scratch, %zu needed (aq_land_scratch_bytes)", scratch_bytes, need);
     LandParams p = {};
-    p.seg = seg_dev; p.entry_seg = entry_seg_dev; p.band_start = band_start_dev; p.boxes = boxes_dev;
-    p.eseg = (double4*)scratch_dev; p.flags = flags_dev;
-    p.entries = entries; p.E = (int)E; p.N = (int)N; p.nbands = nbands; p.Y0 = Y0; p.h = h;
-    hipLaunchKernelGGL(land_gather_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, st, p);
+    p.t.seg = seg_dev; p.t.entry_seg = entry_seg_dev; p.t.band_start = band_start_dev; p.boxes = boxes_dev;
+    p.t.eseg = (double4*)scratch_dev; p.flags = flags_dev;
+    p.t.entries = entries; p.t.E = (int)E; p.N = (int)N; p.t.nbands = nbands; p.t.Y0 = Y0; p.t.h = h;
+    hipLaunchKernelGGL(land_gather_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, st, p.t);
     AQ_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(land_flags_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, p);
     AQ_CHECK_HIP(hipGetLastError());

@@ -138,6 +138,8 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "box-against-polygon test on the GPU, and write what is left as the reference's ocean_detections.geojson; with "
                         "--facilities the ocean detections are clustered, as the reference does; needs --geocode-bboxes")
     p.add_argument("--ocean-out", default=None, metavar="GEOJSON", help="where --land-filter writes (default <save_dir>/ocean_detections.geojson)")
+    from .land_images import add_options as _land_images_options
+    _land_images_options(p)
     p.add_argument("--dedup-overlaps", nargs="?", const="", default=None, metavar="DIR",
                    help="right after the geocoding and before the land filter, count every cage once where the download boxes of the "
                         "--geocode-bboxes file overlap (the reference's deduplicate_download_boxes and deduplicate_gdf_with_bboxes, "
@@ -219,6 +221,12 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if opt.land_filter is not None and not opt.geocode_bboxes:
         p.error("--land-filter filters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if opt.land_images is not None and (opt.land_filter is None or not opt.geocode_bboxes):
+        p.error(LAND_IMAGES_NEED_LAND)
+    if opt.land_images is not None and opt.tile_scenes and not opt.evaluate_kfold_images:
+        p.error(LAND_IMAGES_SCENES_NEED_IMAGES)
+    if opt.land_images is not None and not (opt.land_images_indent > 0 and opt.land_images_indent < float("inf")):
+        p.error(f"--land-images-indent {opt.land_images_indent}: a positive number of metres")
     if opt.dedup_overlaps is not None and not opt.geocode_bboxes:
         p.error(DEDUP_OVERLAPS_NEEDS_GEOCODE)
     if opt.evaluate is not None and not opt.geocode_bboxes:
@@ -254,6 +262,7 @@ NEAR_SITES_NEED_TONNAGE = "--tonnage-near-sites estimates the production near th
 KFOLD_NEEDS_EVALUATE = "--evaluate-kfold cross-validates the tuning grid of --evaluate: it needs --evaluate TRUTH_GEOJSON"
 KFOLD_SCENES_NEED_IMAGES = ("--evaluate-kfold with --tile-scenes: the tiles cut from the scenes are not listed anywhere after the sweep (a tile without "
                             "a detection leaves no label file), so the image table needs --evaluate-kfold-images FILE (the tile names, one per line)")
+from .land_images import NEEDS_LAND as LAND_IMAGES_NEED_LAND, SCENES_NEED_IMAGES as LAND_IMAGES_SCENES_NEED_IMAGES      # noqa: E402
 DEDUP_OVERLAPS_NEEDS_GEOCODE = "--dedup-overlaps needs --geocode-bboxes CSV: the download boxes whose overlaps it resolves (and --save-txt --save-conf)"
 MODEL_ERRORS_NEED_GEOCODE = "--model-errors joins geocoded detections to the labels: it needs --geocode-bboxes CSV (and --save-txt --save-conf)"
 MODEL_ERRORS_OR_FILE = "the model errors of --tonnage come from --model-errors or from --tonnage-errors, not from both"
@@ -289,7 +298,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         evaluate_kfold_test=0.1, tonnage=None, tonnage_factors=None, tonnage_errors=None, tonnage_depths=None, tonnage_default_depth=4.84,
         tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, bathymetry=None, bathymetry_statistic="bathy_min", dedup_years=None,
         dedup_selection="random", dedup_seed=0, model_errors=None, model_errors_conf=None, model_errors_out=None, tonnage_missing=None,
-        tonnage_near_sites=None, dedup_overlaps=None, facility_sites=None, facility_sites_truth=None, facility_sites_out=None, log=print,
+        tonnage_near_sites=None, dedup_overlaps=None, facility_sites=None, facility_sites_truth=None, facility_sites_out=None, land_images=None,
+        land_images_indent=5.0, log=print,
         **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb_checked, jpeg_slots_to_rgb, JPEG_WS_MAX, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
@@ -316,6 +326,13 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         raise ValueError("--facilities clusters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if land_filter is not None and not geocode_bboxes:
         raise ValueError("--land-filter filters geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
+    if land_images is not None and (land_filter is None or not geocode_bboxes):
+        raise ValueError(LAND_IMAGES_NEED_LAND)
+    if land_images is not None and tile_scenes and not evaluate_kfold_images:
+        raise ValueError(LAND_IMAGES_SCENES_NEED_IMAGES)
+    if land_images is not None:
+        from .land_images import _check_indent
+        _check_indent(land_images_indent)
     if dedup_overlaps is not None and not geocode_bboxes:
         raise ValueError(DEDUP_OVERLAPS_NEEDS_GEOCODE)
     if model_errors is not None and not geocode_bboxes:
@@ -1155,6 +1172,21 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 ocean_path = ocean_out or str(save_dir / "ocean_detections.geojson")
                 n_ocean = aqland.write_ocean_geojson(ocean_path, table["stems"], table, ocean)
                 log(f"{n_ocean} of {ocean.shape[0]} detections at sea ({segs.shape[0]} land edges) in {ocean_path} in {time.perf_counter() - t_l:.2f}s")
+            on_land = None
+            if land_images is not None:
+                # the images that hold only land (reference src/utils.py:46-69, mark_land_images), over the image list --evaluate-kfold
+                # makes its table of: the source's listing, or with --tile-scenes the list --evaluate-kfold-images gives
+                from . import evaluate as aqeval, land_images as aqli
+                t_i = time.perf_counter()
+                swept_li = None
+                if not tile_scenes:
+                    from .dataloader import list_images
+                    swept_li = sorted({aqeval._stem(f_) for f_ in list_images(source)})
+                li_out = land_images or str(save_dir / aqli.CSV_FILE)
+                li = aqli.land_images_from_names(aqeval.land_image_names(table, None, evaluate_kfold_images, swept_li), geocode_bboxes, segs, li_out,
+                                                 land_images_indent)
+                on_land = [s_ for s_, l_ in zip(li["stems"], li["on_land"]) if l_]
+                log(f"{aqli.describe(li)} in {li_out} in {time.perf_counter() - t_i:.2f}s")
             dd = None
             hw = None
             if facilities is not None or tonnage is not None or dedup_years is not None or model_errors is not None:
@@ -1219,7 +1251,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                     kf = aqeval.kfold_from_options(table, evaluate, ev_out, grids, (facilities_conf, facilities_eps, facilities_min_cages), ocean,
                                                    aqeval.read_image_list(evaluate_images) if evaluate_images else None, evaluate_kfold,
                                                    evaluate_kfold_images, evaluate_known_sites, evaluate_kfold_seed, evaluate_kfold_test,
-                                                   geocode_bboxes, names=swept, dedup_overlaps=geocode_bboxes if dedup_overlaps is not None else None)
+                                                   geocode_bboxes, names=swept, dedup_overlaps=geocode_bboxes if dedup_overlaps is not None else None,
+                                                   land=on_land)
                     log(f"{aqkfold.describe(kf)} in {ev_out} in {time.perf_counter() - t_k:.2f}s")
             computed_errors = None
             if model_errors is not None:

@@ -78,6 +78,7 @@ EXPORTS = (
     "aq_blank_geom_scratch_bytes", "aq_blank_components_u8", "aq_blank_ring_edges_u8",
     "aq_facility_scratch_bytes", "aq_facility_dbscan_f64",
     "aq_land_scratch_bytes", "aq_land_filter_f64",
+    "aq_land_images_scratch_bytes", "aq_land_images_f64",
     "aq_eval_scratch_bytes", "aq_eval_member_conf_f64", "aq_box_match_f64",
     "aq_eval_subsets_scratch_bytes", "aq_eval_member_conf_subsets_f64", "aq_box_match_subsets_scratch_bytes", "aq_box_match_subsets_f64",
     "aq_model_error_match_f64", "aq_model_error_moments_f64",
@@ -151,6 +152,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_land_scratch_bytes.argtypes = [C.c_longlong]
     lib.aq_land_scratch_bytes.restype = sz
     lib.aq_land_filter_f64.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp, i32, C.c_double, C.c_double, vp, C.c_longlong, vp, sz, vp, vp]
+    lib.aq_land_images_scratch_bytes.argtypes = [C.c_longlong]
+    lib.aq_land_images_scratch_bytes.restype = sz
+    lib.aq_land_images_f64.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp, i32, C.c_double, C.c_double, vp, C.c_longlong, C.c_double, vp, sz, vp, vp, vp]
     lib.aq_eval_scratch_bytes.argtypes = [C.c_longlong, i32]
     lib.aq_eval_scratch_bytes.restype = sz
     lib.aq_eval_member_conf_f64.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, C.c_double, i32, vp, sz, vp, vp]
@@ -2102,6 +2106,48 @@ def land_flags(boxes: torch.Tensor, segs: torch.Tensor, band_height: Optional[fl
     for t_ in (boxes, segs, entry_seg, band_start, scratch, flags):
         t_.record_stream(torch.cuda.current_stream())
     return flags
+
+
+def land_images(rects: torch.Tensor, segs: torch.Tensor, indent: float, band_height: Optional[float] = None,
+                times: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """aq_land_images_f64 on the current stream: rects float64 CUDA [N, 4] (x0, y0, x1, y1; x0 <= x1, y0 <= y1), segs float64 CUDA [E, 4] (as
+    land_flags takes them), indent > 0 in metres -> (flags uint8 CUDA [N], dist2 float64 CUDA [N]): dist2 = the squared distance from the
+    rectangle to the nearest land edge, capped at (2 indent)^2; bit 0 = dist2 < indent^2, bit 1 = the corner (x0, y0) is inside the land;
+    2 = the image lies wholly on land, at least `indent` from the coast (land.land_images_numpy gives the same bytes and doubles).  The band
+    table is land_band_table's, as for land_flags; neither output depends on its band height.  times = as for land_flags."""
+    _require_gpu()
+    lib = load_library()
+    assert rects.is_cuda and segs.is_cuda and rects.dtype == torch.float64 and segs.dtype == torch.float64
+    assert rects.ndim == 2 and rects.shape[1] == 4 and segs.ndim == 2 and segs.shape[1] == 4
+    indent = float(indent)
+    if not (indent > 0 and np.isfinite(indent)):
+        raise ValueError(f"land images: indent = {indent} (it has to be positive and finite)")
+    rects, segs = rects.contiguous(), segs.contiguous()
+    N, E = rects.shape[0], segs.shape[0]
+    flags = torch.empty(N, dtype=torch.uint8, device=rects.device)
+    dist2 = torch.empty(N, dtype=torch.float64, device=rects.device)
+    if N == 0 or E == 0:
+        _check(lib.aq_land_images_f64(None, E, None, 0, None, 1, 0.0, 1.0, None, N, indent, None, 0, flags.data_ptr(), dist2.data_ptr(), _stream_ptr()))
+        for t_ in (flags, dist2):
+            t_.record_stream(torch.cuda.current_stream())
+        return flags, dist2
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
+    if ev:
+        ev[0].record()
+    entry_seg, band_start, nbands, Y0, h = land_band_table(segs, band_height)
+    entries = entry_seg.shape[0]
+    scratch = torch.empty(int(lib.aq_land_images_scratch_bytes(entries)), dtype=torch.uint8, device=rects.device)
+    if ev:
+        ev[1].record()
+    _check(lib.aq_land_images_f64(segs.data_ptr(), E, entry_seg.data_ptr(), entries, band_start.data_ptr(), nbands, Y0, h, rects.data_ptr(), N, indent,
+                                  scratch.data_ptr(), scratch.numel(), flags.data_ptr(), dist2.data_ptr(), _stream_ptr()))
+    if ev:
+        ev[2].record()
+        ev[2].synchronize()
+        times.update(table_ms=ev[0].elapsed_time(ev[1]), kernel_ms=ev[1].elapsed_time(ev[2]), entries=entries, nbands=nbands, band_height=h)
+    for t_ in (rects, segs, entry_seg, band_start, scratch, flags, dist2):
+        t_.record_stream(torch.cuda.current_stream())
+    return flags, dist2
 
 
 def stem_conv_nhwc(tiles_u8: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, act: bool = True, precision: str = "bf16") -> torch.Tensor:

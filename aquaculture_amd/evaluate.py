@@ -33,10 +33,12 @@ Pinned against scikit-learn's DBSCAN per combination plus a brute-force join (th
   * the reference's get_tp tests ``r['index_key']`` for truth, so a match with row 0 of the key table never counts; that slip is not
     reproduced: row 0 matches like any other;
   * the reference drops the detections of images that lie wholly on land ("surely_land"); here the land filter's ocean rows are used when
-    given (``keep``), box by box;
+    given (``keep``), box by box, and they hold no detection of such an image: its box lies inside the image's rectangle, that inside the
+    land (``--land-images``, land_images.py, marks those images);
   * ``images`` (``--evaluate-images``) restricts detections and labels to a list of images, which is how the reference applies a fold; its
     stratified folds themselves -- the image table, the hold-out, the folds, the winners on the test images -- are ``--evaluate-kfold``
-    (kfold.py, whose docstring lists what is not reproduced there: the land stratum among others).
+    (kfold.py, whose docstring lists what is not reproduced there); with ``--land-images`` the images wholly on land leave its image table
+    before the splits are drawn and form the stratum ``land``, as in the reference.
 """
 from __future__ import annotations
 
@@ -506,9 +508,10 @@ def check_kfold_options(n_splits, test_frac) -> None:
 
 def kfold_from_options(table, truth_path: str, out_dir: str, grids, op, keep, images, n_splits: int, kfold_images: Optional[str], known_sites: Optional[str],
                        seed: int, test_frac: float, wanted_bboxes_csv: Optional[str], names: Optional[Sequence[str]] = None, cpu: bool = False,
-                       dedup_overlaps: Optional[str] = None) -> dict:
+                       dedup_overlaps: Optional[str] = None, land: Optional[Sequence[str]] = None) -> dict:
     """The cross-validation as both command lines run it: names = the images of the table when --evaluate-kfold-images gives none (None: those
-    with a detection or a label).  dedup_overlaps = the download-box file: the labels pass through overlaps.filter_truth first."""
+    with a detection or a label).  dedup_overlaps = the download-box file: the labels pass through overlaps.filter_truth first.  land = the
+    images wholly on land (--land-images), which kfold.kfold takes out of the table."""
     from . import kfold as aqkfold
     from . import overlaps
     if kfold_images:
@@ -518,7 +521,18 @@ def kfold_from_options(table, truth_path: str, out_dir: str, grids, op, keep, im
         raise ValueError("--evaluate-known-sites needs the images' rectangles: --geocode-bboxes CSV")
     rects = aqkfold.tile_rects(wanted_bboxes_csv) if sites is not None else None
     return aqkfold.kfold(table, overlaps.filter_truth(load_truth_geojson(truth_path), dedup_overlaps, cpu=cpu), out_dir, n_splits, names=names, rects=rects, sites=sites, seed=seed, test_frac=test_frac,
-                         conf_grid=grids[0], eps_grid=grids[1], min_grid=grids[2], op=op, keep=keep, images=images, cpu=cpu)
+                         conf_grid=grids[0], eps_grid=grids[1], min_grid=grids[2], op=op, keep=keep, images=images, cpu=cpu, land=land)
+
+
+def land_image_names(table, truth_path: Optional[str], kfold_images: Optional[str], names: Optional[Sequence[str]] = None) -> List[str]:
+    """The image list of --land-images, which is the one --evaluate-kfold makes its table of: --evaluate-kfold-images when given, else
+    `names` (the sweep's listing), else the images of the detection table and of the truth, sorted by stem."""
+    if kfold_images:
+        return read_image_list(kfold_images)
+    if names is not None:
+        return list(names)
+    truth = load_truth_geojson(truth_path)["image"] if truth_path else []
+    return sorted({_stem(s) for s in table["stems"]} | {_stem(s) for s in truth})
 
 
 def grids_from_options(conf: Optional[str], eps: Optional[str], min_cages: Optional[str]):
@@ -536,8 +550,13 @@ def main(argv: Optional[List[str]] = None) -> int:
     p.add_argument("--cpu", action="store_true", help="the numpy / scipy restatement instead of the GPU")
     add_options(p)
     facilities.add_options(p)
+    from . import land_images
+    land_images.add_options(p)
     opt = p.parse_args(argv)
+    if opt.land_images is not None and opt.land is None:
+        p.error(land_images.NEEDS_LAND.replace("--land-filter", "--land"))
     try:
+        land_images._check_indent(opt.land_images_indent)
         grids = grids_from_options(opt.evaluate_conf, opt.evaluate_eps, opt.evaluate_min_cages)
         check_kfold_options(opt.evaluate_kfold, opt.evaluate_kfold_test)
     except ValueError as e:
@@ -552,11 +571,17 @@ def main(argv: Optional[List[str]] = None) -> int:
     s = evaluate_table(table, opt.truth, out_dir, *grids, op=(opt.facilities_conf, opt.facilities_eps, opt.facilities_min_cages),
                        keep=keep, images=images, cpu=opt.cpu)
     print(describe(s) + f" in {out_dir}")
+    on_land = None
+    if opt.land_images is not None:
+        li = land_images.land_images_from_names(land_image_names(table, opt.truth, opt.evaluate_kfold_images), opt.geocode_bboxes, opt.land,
+                                                opt.land_images or os.path.join(out_dir, land_images.CSV_FILE), opt.land_images_indent, cpu=opt.cpu)
+        on_land = [s_ for s_, l in zip(li["stems"], li["on_land"]) if l]
+        print(f"{land_images.describe(li)} in {opt.land_images or os.path.join(out_dir, land_images.CSV_FILE)}")
     if opt.evaluate_kfold is not None:
         from . import kfold as aqkfold
         k = kfold_from_options(table, opt.truth, out_dir, grids, (opt.facilities_conf, opt.facilities_eps, opt.facilities_min_cages), keep, images,
                                opt.evaluate_kfold, opt.evaluate_kfold_images, opt.evaluate_known_sites, opt.evaluate_kfold_seed, opt.evaluate_kfold_test,
-                               opt.geocode_bboxes, cpu=opt.cpu)
+                               opt.geocode_bboxes, cpu=opt.cpu, land=on_land)
         print(aqkfold.describe(k) + f" in {out_dir}")
     return 0
 

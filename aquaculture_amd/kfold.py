@@ -29,8 +29,10 @@ images set aside (test_set_performance).  Here:
 
 Pinned against scikit-learn's splitters (index for index), pandas.cut, and the reference's procedure done literally per fold (scikit-learn's
 DBSCAN per combination and year, brute-force joins restricted to the fold).  NOT pinned, and what differs (see also evaluate.py's list):
-  * the land stratum is not formed: the reference removes the images that lie within the land polygon shrunk by 5 m before it splits, which
-    needs a polygon buffer this project does not have; ``--evaluate-kfold-images`` (a list without them) is how such images are left out;
+  * the land stratum is formed only with ``--land-images`` (land_images.py: the images whose rectangles lie within the land shrunk by 5 m,
+    by rectangle-to-edge distances, no polygon buffer): kfold(land=...) takes those images out of the image table before the splits are drawn,
+    in the order of the rest, as the reference does, and lists them with bucket and split ``land``; without the flag no image is taken out
+    and ``--evaluate-kfold-images`` (a list without them) is how such images are left out.  What that rule does not pin is in land_images.py;
   * the reference filters the f_score winner's test members by the PRODUCT winner's confidence (get_fold_performance, last get_stats_total
     call); here each metric uses its own threshold;
   * the ``index_key`` row-0 slip of get_tp stays unreproduced and the overlap de-duplication unapplied, as in evaluate.py;
@@ -53,6 +55,7 @@ CONF_BINS = np.array([0.0, 0.3, 0.5, 0.8, 1.0])
 INTERVALS = tuple(f"({a}, {b}]" for a, b in zip(CONF_BINS[:-1].tolist(), CONF_BINS[1:].tolist()))     # as pandas prints them: "(0.0, 0.3]"
 NO_DET_IN, NO_DET_OUT = "No detection, in known area", "No detection, outside known area"
 STRATA = INTERVALS + (NO_DET_IN, NO_DET_OUT)
+LAND = "land"                                               # bucket and split of an image wholly on land (kfold(land=...)): in no split
 SITE_HALF_SIDE = 1000.0                                     # metres in EPSG:3857, as the reference's '1km_box'
 MAX_SUBSETS = 32
 RESULTS_FILE, IMAGES_FILE, JSON_FILE = "kfold_results.csv", "kfold_images.csv", "kfold.json"
@@ -144,11 +147,15 @@ def image_table(names: Sequence[str], det_image: Sequence[str], det_conf, lab_im
             "bucket": buckets(top, known), "det_row": det_row, "lab_row": lab_row}
 
 
-def strata_table(images: Dict[str, np.ndarray]) -> List[dict]:
-    """Per stratum, in STRATA's order: images, detections, labels (the reference's get_bucket_info_table, whose sample is every image here)."""
+def strata_table(images: Dict[str, np.ndarray], land: Optional[Dict[str, np.ndarray]] = None) -> List[dict]:
+    """Per stratum, in STRATA's order: images, detections, labels (the reference's get_bucket_info_table, whose sample is every image here).
+    land = the image table of the images wholly on land: one more row, ``land``."""
     b = images["bucket"]
-    return [{"bucket": name, "images": int((b == k).sum()), "detections": int(images["n_detections"][b == k].sum()),
+    rows = [{"bucket": name, "images": int((b == k).sum()), "detections": int(images["n_detections"][b == k].sum()),
              "labels": int(images["n_labels"][b == k].sum())} for k, name in enumerate(STRATA)]
+    if land is not None:
+        rows.append({"bucket": LAND, "images": int(land["image"].shape[0]), "detections": int(land["n_detections"].sum()), "labels": int(land["n_labels"].sum())})
+    return rows
 
 
 # ---- scikit-learn's two splitters ----
@@ -550,17 +557,29 @@ def split_names(split) -> List[str]:
     return ["test" if s < 0 else f"fold{int(s)}" for s in np.asarray(split).tolist()]
 
 
-def write_images_csv(path: str, images: Dict[str, np.ndarray], split) -> int:
-    """kfold_images.csv: one line per image of the table, in its order; split = ``test`` (set aside) or ``fold<k>`` (tested in fold k)."""
+def _image_line(images: Dict[str, np.ndarray], k: int, bucket: str, split: str) -> list:
+    y = int(images["year"][k])
+    return [images["image"][k], "" if y < 0 else str(y), _cell(images["n_detections"][k]), _cell(float(images["det_conf"][k])),
+            _cell(images["n_labels"][k]), _cell(bool(images["in_known_area"][k])), bucket, split]
+
+
+def write_images_csv(path: str, images: Dict[str, np.ndarray], split, land: Optional[Dict[str, np.ndarray]] = None) -> int:
+    """kfold_images.csv: one line per image of the table, in its order; split = ``test`` (set aside) or ``fold<k>`` (tested in fold k).
+    land = the image table of the images wholly on land, with ``at``: the line each of them comes before (their place in the list of all
+    images); their bucket and split are ``land``."""
     names = split_names(split)
+    at = np.asarray(land["at"], np.int64) if land is not None else np.zeros(0, np.int64)
+    j = 0
     with open(path, "w", newline="") as f:
         w = csv.writer(f, lineterminator="\n")
         w.writerow(IMAGE_COLUMNS)
-        for k in range(len(names)):
-            y = int(images["year"][k])
-            w.writerow([images["image"][k], "" if y < 0 else str(y), _cell(images["n_detections"][k]), _cell(float(images["det_conf"][k])),
-                        _cell(images["n_labels"][k]), _cell(bool(images["in_known_area"][k])), STRATA[int(images["bucket"][k])], names[k]])
-    return len(names)
+        for k in range(len(names) + 1):
+            while j < at.shape[0] and at[j] == k:
+                w.writerow(_image_line(land, j, LAND, LAND))
+                j += 1
+            if k < len(names):
+                w.writerow(_image_line(images, k, STRATA[int(images["bucket"][k])], names[k]))
+    return len(names) + int(at.shape[0])
 
 
 def read_images_csv(path: str) -> Dict[str, list]:
@@ -574,9 +593,10 @@ def read_images_csv(path: str) -> Dict[str, list]:
     return out
 
 
-def summary(images: Dict[str, np.ndarray], split, result: dict, params: dict, device: str) -> dict:
+def summary(images: Dict[str, np.ndarray], split, result: dict, params: dict, device: str, land: Optional[Dict[str, np.ndarray]] = None) -> dict:
     """What kfold.json holds: the parameters, the strata, mean and sd (ddof = 1) of the test precision and recall per metric over the folds that
-    have a value, the hold-out operating point, the device."""
+    have a value, the hold-out operating point, the device.  land = the image table of the images wholly on land (kfold(land=...)): a ``land``
+    row in the strata and their number as ``land_images``; n_images stays the number of images the splits were drawn over."""
     ev = _ev()
     clean = lambda d: {k: (clean(v) if isinstance(v, dict) else ev._json_num(v)) for k, v in d.items()}
     stats = {}
@@ -587,19 +607,24 @@ def summary(images: Dict[str, np.ndarray], split, result: dict, params: dict, de
             stats[metric][c] = {"folds": int(v.shape[0]), "mean": float(v.mean()) if v.shape[0] else None,
                                 "sd": float(v.std(ddof=1)) if v.shape[0] > 1 else None}
     split = np.asarray(split)
-    return {"parameters": params, "n_images": int(split.shape[0]), "n_train_images": int((split >= 0).sum()), "n_test_images": int((split < 0).sum()),
-            "strata": strata_table(images), "folds": stats, "holdout": None if result["holdout"] is None else clean(result["holdout"]), "device": device}
+    out = {"parameters": params, "n_images": int(split.shape[0]), "n_train_images": int((split >= 0).sum()), "n_test_images": int((split < 0).sum()),
+           "strata": strata_table(images, land), "folds": stats, "holdout": None if result["holdout"] is None else clean(result["holdout"]), "device": device}
+    if land is not None:
+        out["land_images"] = int(land["image"].shape[0])
+    return out
 
 
 def kfold(table: Dict[str, np.ndarray], truth: Dict[str, np.ndarray], out_dir: str, n_splits: int = 5, names: Optional[Sequence[str]] = None,
           rects=None, sites=None, seed: int = 1, test_frac: float = 0.1, conf_grid=None, eps_grid=None, min_grid=None,
           op: Tuple[float, float, int] = (0.5, 10.0, 5), keep=None, images: Optional[Sequence[str]] = None, cpu: bool = False,
-          device: Optional[str] = None, times: Optional[dict] = None) -> dict:
+          device: Optional[str] = None, times: Optional[dict] = None, land: Optional[Sequence[str]] = None) -> dict:
     """evaluate.inputs(table, truth, keep, images), the image table over `names` (default: the images of the detection table -- those with a
     label file -- and of the truth, sorted by stem; `images` restricts either; rects = their rectangles, or a function of the stem, needed
     with sites), the splits, cross_validate() and the three files in
     out_dir: kfold_results.csv, kfold_images.csv, kfold.json -> summary().  device = what kfold.json records as the device (default: "cpu" with
-    cpu, the GPU's name otherwise)."""
+    cpu, the GPU's name otherwise).  land = the images wholly on land (names or stems; land_images.py), None without ``--land-images``: they
+    leave `names` before the image table is made, the order of the rest kept, so the hold-out permutation and the folds run over the ocean
+    images only, as the reference's do; kfold_images.csv lists them where they stood, with bucket and split ``land``."""
     ev = _ev()
     conf_grid = ev.DEFAULT_CONF if conf_grid is None else conf_grid
     eps_grid = ev.DEFAULT_EPS if eps_grid is None else eps_grid
@@ -612,8 +637,29 @@ def kfold(table: Dict[str, np.ndarray], truth: Dict[str, np.ndarray], out_dir: s
     if images is not None:
         wanted = {ev._stem(s) for s in images}
         names = [s for s in names if ev._stem(s) in wanted]
-    if callable(rects):
-        rects = np.asarray([rects(ev._stem(s)) for s in names], np.float64).reshape(-1, 4)
+    rect_of = rects if callable(rects) else None
+    if rect_of is None and rects is not None:
+        rects = np.asarray(rects, np.float64).reshape(-1, 4)
+        if rects.shape[0] != len(names):
+            raise ValueError(f"kfold: {rects.shape[0]} rectangles for {len(names)} images")
+    land_imgs = None
+    if land is not None:
+        # Their detections and labels get no table row and so no subset word: they take part in no fold and not in the hold-out.  (Under
+        # --land-filter they were gone already: a detection's box lies inside its image's rectangle, that inside the land, so the land
+        # filter's byte for it is not 0 and the ocean rows hold none of them.)
+        on = {ev._stem(s) for s in land}
+        is_land = np.asarray([ev._stem(s) in on for s in names], bool).reshape(-1)
+        land_names = [s for s, l in zip(names, is_land) if l]
+        names = [s for s, l in zip(names, is_land) if not l]
+        land_rects = None
+        if rect_of is None and rects is not None:
+            land_rects, rects = rects[is_land], rects[~is_land]
+        elif rect_of is not None:
+            land_rects = np.asarray([rect_of(ev._stem(s)) for s in land_names], np.float64).reshape(-1, 4)
+        land_imgs = image_table(land_names, det_image, data["det"]["conf"], lab_image, land_rects, sites)
+        land_imgs["at"] = (np.nonzero(is_land)[0] - np.arange(len(land_names))).astype(np.int64)      # the ocean image each one stood before
+    if rect_of is not None:
+        rects = np.asarray([rect_of(ev._stem(s)) for s in names], np.float64).reshape(-1, 4)
     imgs = image_table(names, det_image, data["det"]["conf"], lab_image, rects, sites)
     split = split_images(imgs["bucket"], n_splits, seed, test_frac)
     result = cross_validate(data, imgs, split, n_splits, conf_grid, eps_grid, min_grid, op=op, cpu=cpu, times=times)
@@ -629,8 +675,8 @@ def kfold(table: Dict[str, np.ndarray], truth: Dict[str, np.ndarray], out_dir: s
     t0 = time.perf_counter()
     os.makedirs(out_dir, exist_ok=True)
     write_results_csv(os.path.join(out_dir, RESULTS_FILE), result["rows"])
-    write_images_csv(os.path.join(out_dir, IMAGES_FILE), imgs, split)
-    s = summary(imgs, split, result, params, device)
+    write_images_csv(os.path.join(out_dir, IMAGES_FILE), imgs, split, land_imgs)
+    s = summary(imgs, split, result, params, device, land_imgs)
     with open(os.path.join(out_dir, JSON_FILE), "w") as f:
         json.dump(s, f, indent=1)
     if times is not None:

@@ -1,4 +1,5 @@
 """The land filter (``detect.py --land-filter``, ``python -m aquaculture_amd.land``): ocean_detections.geojson from detections.geojson.
+(``python -m aquaculture_amd.land --images FILE`` is the images' counterpart, land_images.py: which images lie wholly on land.)
 
 reference src/process_yolo/geocode_results.py:200-218 (remove_land_detections): ``detections.sjoin(french_land, how='inner')`` with the
 default predicate ``intersects`` drops every detection whose box intersects the land polygon; what is left is saved with ``index=True`` as
@@ -181,9 +182,23 @@ def main(argv: Optional[List[str]] = None) -> int:
     p.add_argument("--labels", required=True, metavar="DIR", help="label files written by detect.py --save-txt --save-conf")
     p.add_argument("--geocode-bboxes", required=True, metavar="CSV", help="reference data/wanted_bboxes.csv")
     p.add_argument("--land", required=True, metavar="GEOJSON", help="the land polygons (the reference's france_final_land_filter.shp as GeoJSON)")
-    p.add_argument("--out", default=None, metavar="GEOJSON", help="default <labels>/../ocean_detections.geojson")
+    p.add_argument("--out", default=None, metavar="GEOJSON", help="default <labels>/../ocean_detections.geojson; with --images the directory of its two files")
     p.add_argument("--cpu", action="store_true", help="flags from the numpy restatement instead of the GPU")
+    p.add_argument("--images", default=None, metavar="FILE",
+                   help="instead of the detections: mark the images of FILE (names, one per line) whose rectangles lie wholly on land, at least "
+                        "--land-images-indent metres from the coast (detect.py --land-images), and write land_images.csv and land_images.json")
+    p.add_argument("--land-images-indent", type=float, default=5.0, metavar="R", help="how far the land is shrunk, in EPSG:3857 metres (the reference: 5)")
     opt = p.parse_args(argv)
+    if opt.images is not None:
+        from . import evaluate, land_images
+        out_dir = opt.out or os.path.dirname(os.path.abspath(opt.labels.rstrip("/")))
+        try:
+            res = land_images.land_images_from_names(evaluate.read_image_list(opt.images), opt.geocode_bboxes, opt.land,
+                                                     os.path.join(out_dir, land_images.CSV_FILE), opt.land_images_indent, cpu=opt.cpu)
+        except ValueError as e:
+            p.error(str(e))
+        print(f"{land_images.describe(res)} in {out_dir}")
+        return 0
     out = opt.out or os.path.join(os.path.dirname(os.path.abspath(opt.labels.rstrip("/"))), "ocean_detections.geojson")
     table = geocode.geocode_label_dir(opt.labels, opt.geocode_bboxes)
     segs = load_land_geojson(opt.land)

@@ -734,6 +734,23 @@ int aq_land_filter_f64(const double* seg_dev, long long E, const int32_t* entry_
                        int nbands, double Y0, double h, const double* boxes_dev, long long N, void* scratch_dev, size_t scratch_bytes,
                        uint8_t* flags_dev, void* stream);
 
+/* --land-images: which of N image rectangles (x0, y0, x1, y1; x0 <= x1, y0 <= y1) lie wholly on land, at least `indent` metres from the
+ * coast (reference src/utils.py:46-69, mark_land_images: `within` the land shrunk by buffer(-5)), against the same segments through the same
+ * band table as aq_land_filter_f64.  Per rectangle dist2_dev = the squared distance to the nearest land edge -- 0 for an edge that meets
+ * the closed rectangle (the land filter's bit-0 predicate), else the minimum of the four corners' squared distances to the segment and the
+ * two segment ends' to the rectangle, every expression as the head comment of csrc/land_images.hip writes it -- over the segments of the
+ * bands floor((y0 - 3 indent - Y0) / h) .. floor((y1 + 3 indent - Y0) / h), capped at (2 indent)^2, so that it does not depend on the band
+ * height; and one byte: bit 0 = dist2 < indent^2, bit 1 = the land filter's corner parity for (x0, y0).  The image is on land when the
+ * byte is 2.  A rectangle wholly above or below all bands, or with a coordinate that is not a number, gets byte 0 and dist2 = (2 indent)^2. */
+/* Scratch: 32 bytes per entry (the segments' coordinates in entry order); 0 for entries <= 0 or entries >= 2^31. */
+size_t aq_land_images_scratch_bytes(long long entries);
+/* On `stream`; the call initialises its scratch, allocates nothing and uses no atomics, so two calls give the same bytes.  N = 0 does nothing;
+ * E = 0 (or entries = 0) gives byte 0 and dist2 = (2 indent)^2 everywhere.  Refused before anything is launched, both outputs untouched: what
+ * aq_land_filter_f64 refuses, an indent that is not positive and finite, dist2_dev null or not 8-byte aligned. */
+int aq_land_images_f64(const double* seg_dev, long long E, const int32_t* entry_seg_dev, long long entries, const int32_t* band_start_dev,
+                       int nbands, double Y0, double h, const double* rects_dev, long long N, double indent, void* scratch_dev,
+                       size_t scratch_bytes, uint8_t* flags_dev, double* dist2_dev, void* stream);
+
 /* ---- --tonnage (tonnage.hip): the bootstrap of the facilities' live-weight production per image pass (reference src/utils_tonnage.py:28-127,
  * compute_facility_tonnage_estimates, with :330-458, sample_model_errors).  Everything fp64; the only floating-point operations are + - x /
  * sqrt, comparisons and selections (no fma, no libm), so aquaculture_amd.tonnage.simulate_numpy gives the same bytes.
