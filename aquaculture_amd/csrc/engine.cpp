@@ -917,6 +917,7 @@ extern "C" int aq_engine_create(const aq_model_desc* d, int device, aq_engine** 
     AQ_REQUIRE(d && out, "engine_create: null pointer");
     AQ_REQUIRE(d->n_ops > 0 && d->n_tensors > 0 && d->ops && d->tensors, "engine_create: empty plan");
     AQ_REQUIRE(d->nl == 3 && d->na >= 1 && d->na <= 8 && d->nc >= 1, "engine_create: unsupported head nl=%d na=%d nc=%d", d->nl, d->na, d->nc);
+    AQ_REQUIRE(d->nc <= 128, "engine_create: nc = %d, the NMS class filter covers at most 128 classes", d->nc);
     AQ_REQUIRE(d->precision == AQ_BF16 || d->precision == AQ_FP32 || d->precision == AQ_BF16_W8 || d->precision == AQ_F16X3,
                "engine_create: bad precision %d", d->precision);
     {   // One device per process (one process per GPU is how every entry point of this package runs).  The launch-time state of the

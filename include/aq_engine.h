@@ -100,7 +100,8 @@ const char* aq_last_error(void);
 int aq_version(void);
 
 /* ---- engine (S1 + S2) ---------------------------------------------------------------- */
-/* Copies + packs the weights to the device (the only allocation the engine ever does). */
+/* Copies + packs the weights to the device (the only allocation the engine ever does).  nl = 3, 1 <= na <= 8 and 1 <= nc <= 128 (the two
+   64-bit words of the NMS class filter); anything else is AQ_ERR_INVALID and no engine. */
 int aq_engine_create(const aq_model_desc* desc, int device_ordinal, aq_engine** out);
 void aq_engine_destroy(aq_engine* e);
 /* Bytes of caller-provided workspace needed for batches up to max_batch of HxW tiles.  Refuses (AQ_ERR_INVALID, nothing allocated) a batch

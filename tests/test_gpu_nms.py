@@ -14,19 +14,29 @@ NC = 5
 
 
 def _pred(boxes_xywh, obj, cls_conf, nc=NC):
-    """cls_conf: rows written for five classes, cut to the first nc."""
+    """cls_conf: rows written for five classes, cut to the first nc -- or, for more classes than columns, a dict {class: scores of the
+    rows} (the other classes score 0), or rows of fewer than nc columns (the classes past them score 0)."""
     n = len(boxes_xywh)
     p = np.zeros((1, n, 5 + nc), np.float32)
     p[0, :, :4] = boxes_xywh
     p[0, :, 4] = obj
-    p[0, :, 5:] = np.asarray(cls_conf, np.float32)[:, :nc]
+    if isinstance(cls_conf, dict):
+        for c, v in cls_conf.items():
+            assert 0 <= c < nc
+            p[0, :, 5 + c] = v
+        return p
+    rows = np.asarray(cls_conf, np.float32)[:, :nc]
+    p[0, :, 5:5 + rows.shape[1]] = rows
     return p
 
 
-def _run(pred, conf=0.25, iou=0.45, max_det=1000, agnostic=False, classes=None):
+def _run(pred, conf=0.25, iou=0.45, max_det=1000, agnostic=False, classes=None, precheck=None):
+    """precheck(ref): what the caller requires of the oracle's result alone, asserted before anything is launched."""
     from aquaculture_amd import engine
     from oracle import yolov5_oracle as O
     ref = O.non_max_suppression(pred, conf, iou, max_det, agnostic=agnostic, classes=classes)
+    if precheck is not None:
+        precheck(ref)
     dets, counts = engine.nms(torch.from_numpy(pred).cuda().contiguous(), pred.shape[2] - 5, conf, iou, max_det, agnostic=agnostic, classes=classes)
     dets, counts = dets.cpu().numpy(), counts.cpu().numpy()
     for b, r in enumerate(ref):
@@ -145,12 +155,12 @@ def test_random_dense_matches_oracle_other_class_counts(lib, n, seed, nc):
     _random_dense(nc, n, seed)
 
 
-def _random_dense(nc, n, seed):
+def _random_dense(nc, n, seed, precheck=None):
     rng = np.random.default_rng(seed)
     p = _random_pred(rng, n, B=2, nc=nc)
     p[..., 4] = rng.uniform(0.5, 1.0, p.shape[:2])
     p[..., 5:] = rng.uniform(0.6, 1.0, p.shape[:2] + (nc,))
-    r = _run(p)
+    r = _run(p, precheck=precheck)
     assert all(x.shape[0] > 10 for x in r)
 
 
@@ -196,7 +206,7 @@ def test_large_tiles_take_the_4096_candidate_bit_matrix_other_class_counts(lib, 
     _large_tile(nc, n_cand)
 
 
-def _large_tile(nc, n_cand):
+def _large_tile(nc, n_cand, precheck=None):
     rng = np.random.default_rng(n_cand)
     N = 100800
     p = _random_pred(rng, N, spread=1240.0, nc=nc)
@@ -204,16 +214,17 @@ def _large_tile(nc, n_cand):
     idx = rng.choice(N, n_cand, replace=False)
     p[0, idx, 4] = rng.uniform(0.5, 1.0, n_cand)              # ... but n_cand rows
     p[0, idx, 5:] = rng.uniform(0.6, 1.0, (n_cand, nc))
-    r = _run(p, max_det=1000)[0]
+    r = _run(p, max_det=1000, precheck=precheck)[0]
     assert r.shape[0] > 100
 
 
 # ---- the unfused decode (aq_detect_decode) away from nc = 5 ---------------------------------------------------------------------------
-def _decode(lib, heads, H, W, nc, na, anchors_px, strides, conf, cap):
-    """aq_detect_decode on fp32 head maps [B, ny, nx, 32]: (pred [B, N, no], counts [B], cand [B, cap + guard], rows [B, cap + guard, no]);
+def _decode(lib, heads, H, W, nc, na, anchors_px, strides, conf, cap, head_ld=32):
+    """aq_detect_decode on fp32 head maps [B, ny, nx, head_ld]: (pred [B, N, no], counts [B], cand [B, cap + guard], rows [B, cap + guard, no]);
     the guard slots behind an image's cap are part of the next image's -- the buffers are allocated with a sentinel tail instead."""
     from aquaculture_amd import engine
     B, no = heads[0].shape[0], nc + 5
+    assert all(h.shape[3] == head_ld and h.is_contiguous() for h in heads)
     N = sum(na * h.shape[1] * h.shape[2] for h in heads)
     pred = torch.full((B, N, no), -7.0, dtype=torch.float32, device="cuda")
     counts = torch.full((B + 64,), -7, dtype=torch.int32, device="cuda")
@@ -222,7 +233,7 @@ def _decode(lib, heads, H, W, nc, na, anchors_px, strides, conf, cap):
     hp = (C.c_void_p * 3)(*[h.data_ptr() for h in heads])
     anch = (C.c_float * (3 * na * 2))(*[float(v) for lvl in anchors_px for a in lvl for v in a])
     st = (C.c_float * 3)(*[float(s) for s in strides])
-    engine._check(lib.aq_detect_decode(hp, 32, B, H, W, nc, na, anch, st, pred.data_ptr(), conf, cand.data_ptr(), rows.data_ptr(), counts.data_ptr(),
+    engine._check(lib.aq_detect_decode(hp, head_ld, B, H, W, nc, na, anch, st, pred.data_ptr(), conf, cand.data_ptr(), rows.data_ptr(), counts.data_ptr(),
                                        cap, engine._stream_ptr()))
     torch.cuda.synchronize()
     assert (counts[B:] == -7).all() and (cand[B * cap:] == -7).all() and (rows[B * cap * no:] == -7.0).all()
@@ -234,13 +245,19 @@ def test_detect_decode_at_four_and_one_classes(lib, nc, small_cap):
     """Random fp32 head maps of 32 channels whose channels past na * no hold garbage, 64 x 96 px (levels 8 x 12, 4 x 6, 2 x 3), B = 3: the
     full pred against the oracle's Detect decode to fp32 rounding (1e-6 of the largest value); the compact list names exactly the rows with obj > conf_thres (all of them, or the
     first cap when there are more), its rows are bitwise the pred rows they name, its counters are exact."""
+    _detect_decode_case(lib, nc, small_cap)
+
+
+def _detect_decode_case(lib, nc, small_cap, head_ld=32):
+    """The procedure of test_detect_decode_at_four_and_one_classes on head maps of head_ld channels (tests/test_gpu_many_classes.py runs it
+    at the widths of 6 to 128 classes)."""
     from aquaculture_amd import checkpoint
     from oracle import yolov5_oracle as O
     ck = checkpoint.synthetic_checkpoint("yolov5m", 5)
     B, H, W, na, no, conf = 3, 64, 96, 3, nc + 5, 0.25
     g = torch.Generator().manual_seed(40 + nc)
-    heads = [torch.randn(B, H // s, W // s, 32, generator=g) * 1.5 for s in (8, 16, 32)]
-    assert all((h[..., na * no:] != 0).all() for h in heads)
+    heads = [torch.randn(B, H // s, W // s, head_ld, generator=g) * 1.5 for s in (8, 16, 32)]
+    assert na * no < head_ld and all((h[..., na * no:] != 0).all() for h in heads)
     m = O.OracleModel({}, nc, ck.anchors, ck.stride, ck.bn_eps)
     want = _oracle_decode(m, [h[..., :na * no] for h in heads])
     N = want.shape[1]
@@ -248,20 +265,9 @@ def test_detect_decode_at_four_and_one_classes(lib, nc, small_cap):
     assert int(passing.min()) > 20
     cap = int(passing.max()) // 2 if small_cap else N
     pred, counts, cand, rows = _decode(lib, [h.cuda().contiguous() for h in heads], H, W, nc, na, ck.anchor_grid_px().numpy().tolist(), ck.stride,
-                                       conf, cap)
+                                       conf, cap, head_ld)
     assert pred.shape == want.shape == (B, 3 * (96 + 24 + 6), no)
-    # the criterion of tests/test_gpu_augment.py::test_detect_decode_aug_matches_descaled_oracle: the oracle's sigmoid is torch's vectorised
-    # CPU exp, the kernel's is the device expf -- both correctly rounded to within an ulp, not the same function, so the two decodes agree
-    # to fp32 rounding and not in every bit (measured on MI355X: 403 of 10,206 values differ at nc = 4, 229 of 6,804 at nc = 1, by a few
-    # units in the last place -- at most 9.2e-5 px on a box side)
-    diff = (pred - want).abs()
-    print(f"detect_decode nc {nc}: {int((diff > 0).sum())} of {diff.numel()} values differ from the oracle's, max |d| {diff.max().item():.3e} "
-          f"(bound {1e-6 * max(1.0, want.abs().max().item()):.3e})")
-    assert diff.max().item() <= 1e-6 * max(1.0, want.abs().max().item())
-    # ... and value by value: each sigmoid is exp (1 ulp) + an add and a divide (half an ulp each), so two of them are at most 4 ulp apart
-    # (2.4e-7 below 1); wh squares it (twice the relative error, two more roundings: 12 ulp), xy adds at most 2 * stride * 2.4e-7 <= 1e-5 px
-    assert diff[..., 4:].max().item() <= 4 * 2.0 ** -24
-    assert (diff[..., :4] <= 12 * 2.0 ** -23 * want[..., :4].abs() + 1e-5).all()
+    _assert_decode_bounds(pred, want, f"detect_decode nc {nc}")
     assert torch.equal(pred[..., 4] > conf, want[..., 4] > conf)
     assert counts.tolist() == passing.tolist()
     for b in range(B):
@@ -271,6 +277,24 @@ def test_detect_decode_at_four_and_one_classes(lib, nc, small_cap):
         assert len(set(got.tolist())) == stored and (set(got.tolist()) == ok if not small_cap else set(got.tolist()) < ok)
         assert torch.equal(rows[b, :stored], pred[b, got.long()])
         assert (cand[b, stored:] == -7).all() and (rows[b, stored:] == -7.0).all()
+
+
+def _assert_decode_bounds(pred, want, label):
+    """A decoded pred against the oracle's Detect decode of the same head maps; returns (largest |d|, its bound)."""
+    # the criterion of tests/test_gpu_augment.py::test_detect_decode_aug_matches_descaled_oracle: the oracle's sigmoid is torch's vectorised
+    # CPU exp, the kernel's is the device expf -- both correctly rounded to within an ulp, not the same function, so the two decodes agree
+    # to fp32 rounding and not in every bit (measured on MI355X: 403 of 10,206 values differ at nc = 4, 229 of 6,804 at nc = 1, by a few
+    # units in the last place -- at most 9.2e-5 px on a box side)
+    diff = (pred - want).abs()
+    bound = 1e-6 * max(1.0, want.abs().max().item())
+    print(f"{label}: {int((diff > 0).sum())} of {diff.numel()} values differ from the oracle's, max |d| {diff.max().item():.3e} "
+          f"(bound {bound:.3e}), max |d conf| {diff[..., 4:].max().item():.3e} (bound {4 * 2.0 ** -24:.3e})")
+    assert diff.max().item() <= bound
+    # ... and value by value: each sigmoid is exp (1 ulp) + an add and a divide (half an ulp each), so two of them are at most 4 ulp apart
+    # (2.4e-7 below 1); wh squares it (twice the relative error, two more roundings: 12 ulp), xy adds at most 2 * stride * 2.4e-7 <= 1e-5 px
+    assert diff[..., 4:].max().item() <= 4 * 2.0 ** -24
+    assert (diff[..., :4] <= 12 * 2.0 ** -23 * want[..., :4].abs() + 1e-5).all()
+    return diff.max().item(), bound
 
 
 def _oracle_decode(m, heads_nhwc):
