@@ -46,6 +46,7 @@ SOURCES = [
     ("eval_subsets.hip", ["-ffp-contract=off"]), # --evaluate-kfold: the same two steps for up to 32 subsets (folds) of one point set per call, one bit of a mask word each
     ("model_errors.hip", ["-ffp-contract=off"]), # --model-errors: the best-overlap join (inter = two subtractions and one product) and the moments in one written order (no fma)
     ("tonnage.hip", ["-ffp-contract=off"]),      # --tonnage: the production bootstrap; fp64 in + - x / sqrt only, every product and sum rounded as written (no fma)
+    ("population.hip", ["-ffp-contract=off"]),   # --performance: the Bernoulli samples of the population bound; tonnage's generator (philox.h), integer counts of fp64 comparisons
     ("depth.hip", ["-ffp-contract=off"]),        # --bathymetry: depth-raster cells under the facilities' cages; fp64 cell ranges and one written order of the sum (no fma)
     ("dedup.hip", ["-ffp-contract=off"]),        # --dedup-years: even-odd fill of the non-blank rings, slot-set words of the cages, the n! area sums in one written order
     ("coverage.hip", ["-ffp-contract=off"]),     # --tonnage-missing: boxes against the union of a pass's image regions; the fp64 band expression exactly as the host's (no fma)

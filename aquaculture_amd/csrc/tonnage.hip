@@ -15,25 +15,12 @@
 //             else x = sqrt(-2 alog(y)), x0 = x - alog(x) / x, z = 1 / x, x1 = (z P(z)) / Q(z) with (P1, Q1) for x < 8, else (P2, Q2);
 //             x0 - x1, negated unless y was mirrored.  Polynomials by Horner from the first coefficient.
 #include "aq_common.h"
+#include "philox.h"    // philox_uniform: the generator and the 53-bit uniform of the head comment, shared with population.hip
 
 namespace {
 
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
 constexpr int TON_MAX_ATTEMPTS = 64;
 enum { SLOT_ERROR = 0, SLOT_AREA = 1, SLOT_BERNOULLI = 2, SLOT_DEPTH_A = 3, SLOT_DEPTH_B = 4, SLOT_STOCKING = 5, SLOT_HARVEST = 6 };
-
-__device__ inline double philox_uniform(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)PHILOX_M0 * c0, p1 = (uint64_t)PHILOX_M1 * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += PHILOX_W0; k1 += PHILOX_W1;
-    }
-    const uint64_t x = (((uint64_t)c1 << 32) | c0) >> 11;
-    const double u = ((double)x + 0.5) * 0x1p-53;
-    return u < 1.0 ? u : 0x1.fffffffffffffp-1;
-}
 
 // x positive and finite (every caller's is)
 __device__ inline double alog(double x) {

@@ -190,6 +190,15 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                         "--facilities (by pass), --bathymetry and --tonnage see the survivors only; needs --geocode-bboxes, implies --blank-geom")
     from .dedup import add_options as _dedup_options
     _dedup_options(p)
+    p.add_argument("--performance", nargs="?", const="", default=None, metavar="DIR",
+                   help="after the sweep and --evaluate, the numbers behind the reference's accuracy section (src/Results/ModelPerformance.py, "
+                        "get_bucket_info_table, src/Results/upper_bound_calculation.R): precision and recall against the confidence threshold for "
+                        "the raw detections, those outside the images wholly on land (--land-images) and those DBSCAN clusters once at "
+                        "--performance-eps / -min-cages; the strata table with the labels extrapolated per stratum; and the Monte-Carlo upper "
+                        "bound on the cage population, its Bernoulli samples drawn on the GPU; writes performance_curves.csv, "
+                        "performance_strata.csv and performance.json (default <save_dir>); needs --evaluate and --geocode-bboxes")
+    from .performance import add_options as _performance_options
+    _performance_options(p)
     opt = p.parse_args(argv)
     if opt.dedup_years is not None and not opt.geocode_bboxes:
         p.error(DEDUP_NEEDS_GEOCODE)
@@ -241,6 +250,16 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error(KFOLD_NEEDS_EVALUATE)
     if opt.evaluate_kfold is not None and opt.tile_scenes and not opt.evaluate_kfold_images:
         p.error(KFOLD_SCENES_NEED_IMAGES)
+    if opt.performance is not None and (opt.evaluate is None or not opt.geocode_bboxes):
+        p.error(PERFORMANCE_NEEDS_EVALUATE)
+    if opt.performance is not None and opt.tile_scenes and not opt.evaluate_kfold_images:
+        p.error(PERFORMANCE_SCENES_NEED_IMAGES)
+    if opt.performance is not None:
+        from .performance import check_options as _check_performance
+        try:
+            _check_performance(opt.performance_thresholds, opt.performance_eps, opt.performance_min_cages, opt.performance_rates, opt.performance_K)
+        except ValueError as e:
+            p.error(str(e))
     if opt.evaluate is not None:
         from .evaluate import check_kfold_options, grids_from_options
         try:
@@ -263,6 +282,7 @@ KFOLD_NEEDS_EVALUATE = "--evaluate-kfold cross-validates the tuning grid of --ev
 KFOLD_SCENES_NEED_IMAGES = ("--evaluate-kfold with --tile-scenes: the tiles cut from the scenes are not listed anywhere after the sweep (a tile without "
                             "a detection leaves no label file), so the image table needs --evaluate-kfold-images FILE (the tile names, one per line)")
 from .land_images import NEEDS_LAND as LAND_IMAGES_NEED_LAND, SCENES_NEED_IMAGES as LAND_IMAGES_SCENES_NEED_IMAGES      # noqa: E402
+from .performance import NEEDS_EVALUATE as PERFORMANCE_NEEDS_EVALUATE, SCENES_NEED_IMAGES as PERFORMANCE_SCENES_NEED_IMAGES      # noqa: E402
 DEDUP_OVERLAPS_NEEDS_GEOCODE = "--dedup-overlaps needs --geocode-bboxes CSV: the download boxes whose overlaps it resolves (and --save-txt --save-conf)"
 MODEL_ERRORS_NEED_GEOCODE = "--model-errors joins geocoded detections to the labels: it needs --geocode-bboxes CSV (and --save-txt --save-conf)"
 MODEL_ERRORS_OR_FILE = "the model errors of --tonnage come from --model-errors or from --tonnage-errors, not from both"
@@ -299,7 +319,8 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
         tonnage_min_depth=1.0, tonnage_K=10000, tonnage_seed=0, tonnage_mix=0.5, bathymetry=None, bathymetry_statistic="bathy_min", dedup_years=None,
         dedup_selection="random", dedup_seed=0, model_errors=None, model_errors_conf=None, model_errors_out=None, tonnage_missing=None,
         tonnage_near_sites=None, dedup_overlaps=None, facility_sites=None, facility_sites_truth=None, facility_sites_out=None, land_images=None,
-        land_images_indent=5.0, log=print,
+        land_images_indent=5.0, performance=None, performance_sample=None, performance_thresholds=100, performance_eps=50.0,
+        performance_min_cages=5, performance_rates=None, performance_K=10000, performance_seed=0, performance_cages_per_image=5.0, log=print,
         **unsupported):
     from .engine import Engine, format_label_rows, write_label_files, jpeg_idct_rgb_checked, jpeg_slots_to_rgb, JPEG_WS_MAX, letterbox_device, letterbox_scene_tiles   # raises if the HIP library or the GPU is missing: there is no fallback
 
@@ -348,6 +369,14 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
     if evaluate_kfold is not None:
         from .evaluate import check_kfold_options
         check_kfold_options(evaluate_kfold, evaluate_kfold_test)
+    if performance is not None and (evaluate is None or not geocode_bboxes):
+        raise ValueError(PERFORMANCE_NEEDS_EVALUATE)
+    if performance is not None and tile_scenes and not evaluate_kfold_images:
+        raise ValueError(PERFORMANCE_SCENES_NEED_IMAGES)
+    if performance is not None:
+        from .performance import settings_from_options as _performance_settings
+        performance_settings = _performance_settings(performance_thresholds, performance_eps, performance_min_cages, performance_rates, performance_K,
+                                                     performance_seed, performance_cages_per_image)
     if tonnage is not None and not geocode_bboxes:
         raise ValueError("--tonnage estimates from geocoded detections: it needs --geocode-bboxes CSV (and --save-txt --save-conf)")
     if tonnage is not None and not tonnage_factors:
@@ -1153,6 +1182,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
             table = geocode.geocode_label_dir(labels_dir, geocode_bboxes, out)
             log(f"{table['image'].shape[0]} detections geocoded to {out} in {time.perf_counter() - t_g:.2f}s")
             ocean = None
+            unique = None                                  # --dedup-overlaps' survivors alone: what --performance's first curve sees
             if dedup_overlaps is not None:
                 # the reference's next statement (geocode_results.py:256-262): every cage once where the download boxes overlap.  The
                 # survivors are the one keep mask of every later step; detections.geojson stays as it is
@@ -1160,7 +1190,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 t_o = time.perf_counter()
                 ov_out = dedup_overlaps or str(save_dir)
                 ov = aqover.dedup_from_table(table, geocode_bboxes, ov_out)
-                ocean = ov["keep"]
+                ocean = unique = ov["keep"]
                 log(f"dedup overlaps: {aqover.describe(ov['summary'])} in {ov_out} in {time.perf_counter() - t_o:.2f}s")
             if land_filter is not None:
                 # the step between them (reference geocode_results.py:200-218, :267-271): detections.geojson stays as it is
@@ -1254,6 +1284,20 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                                                    geocode_bboxes, names=swept, dedup_overlaps=geocode_bboxes if dedup_overlaps is not None else None,
                                                    land=on_land)
                     log(f"{aqkfold.describe(kf)} in {ev_out} in {time.perf_counter() - t_k:.2f}s")
+                if performance is not None:
+                    # the accuracy section (reference src/Results/ModelPerformance.py, get_bucket_info_table, upper_bound_calculation.R) on
+                    # the same table and labels: the detections before any land step, the image list of --land-images and --evaluate-kfold
+                    from . import performance as aqperf
+                    t_p = time.perf_counter()
+                    swept_p = None
+                    if not tile_scenes:
+                        from .dataloader import list_images
+                        swept_p = sorted({aqeval._stem(f_) for f_ in list_images(source)})
+                    pf_out = performance or str(save_dir)
+                    pf = aqperf.performance_from_options(table, evaluate, pf_out, geocode_bboxes, names=swept_p, kfold_images=evaluate_kfold_images,
+                                                         sample_file=performance_sample, known_sites=evaluate_known_sites, land=on_land, keep=unique,
+                                                         dedup_overlaps=geocode_bboxes if dedup_overlaps is not None else None, **performance_settings)
+                    log(f"{aqperf.describe(pf)} in {pf_out} in {time.perf_counter() - t_p:.2f}s")
             computed_errors = None
             if model_errors is not None:
                 # the model's cage-area error per pass and type (reference src/utils_tonnage.py:130-203) from the same table and the labels

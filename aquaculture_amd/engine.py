@@ -83,6 +83,7 @@ EXPORTS = (
     "aq_eval_subsets_scratch_bytes", "aq_eval_member_conf_subsets_f64", "aq_box_match_subsets_scratch_bytes", "aq_box_match_subsets_f64",
     "aq_model_error_match_f64", "aq_model_error_moments_f64",
     "aq_tonnage_simulate_f64", "aq_tonnage_reduce_f64", "aq_tonnage_ndtri_f64", "aq_tonnage_uniform_f64",
+    "aq_bernoulli_counts_i32",
     "aq_depth_ranges_f64", "aq_depth_stats_f64",
     "aq_dedup_fill_u32", "aq_dedup_sets_u32", "aq_dedup_select_f64",
     "aq_coverage_first_i32",
@@ -172,6 +173,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_tonnage_reduce_f64.argtypes = [vp, C.c_longlong, C.c_longlong, vp, i32, vp, vp, vp]
     lib.aq_tonnage_ndtri_f64.argtypes = [vp, C.c_longlong, vp, vp]
     lib.aq_tonnage_uniform_f64.argtypes = [C.c_ulonglong, vp, C.c_longlong, vp, vp]
+    lib.aq_bernoulli_counts_i32.argtypes = [C.c_ulonglong, C.c_longlong, C.c_longlong, C.c_longlong, vp, vp, i32, vp, vp]
     lib.aq_depth_ranges_f64.argtypes = [vp, C.c_longlong, vp, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp]
     lib.aq_depth_stats_f64.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp, vp, vp, vp, vp, i32, i32, C.c_double, vp, C.c_longlong, vp, vp, vp]
     lib.aq_engine_set_tuned_table.argtypes = [vp, i32, i32, i32, C.POINTER(i32), i32]
@@ -1659,6 +1661,31 @@ def tonnage_uniform(seed: int, counters: torch.Tensor) -> torch.Tensor:
     n = int(counters.shape[0])
     out = torch.empty(n, dtype=torch.float64, device=counters.device)
     _check(load_library().aq_tonnage_uniform_f64(int(seed), counters.data_ptr() if n else None, n, out.data_ptr() if n else None, _stream_ptr()))
+    return out
+
+
+# ---- --performance: aq_bernoulli_counts_i32 (the samples behind the population bound) ----
+
+BERNOULLI_MAX_RATES = 16
+
+
+def bernoulli_counts(seed: int, k0: int, K: int, S: int, rates, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """aq_bernoulli_counts_i32 on the current stream: int32 CUDA [K, R], row k the number of the S draws of simulation k0 + k that fall below
+    each of the R rates (a sequence of doubles in [0, 1], at most 16); performance.counts_numpy gives the same bytes.  out = an int32 CUDA
+    [K, R] tensor to write into (contiguous)."""
+    _require_gpu()
+    lib = load_library()
+    rates_h = np.ascontiguousarray(np.asarray(rates, np.float64).reshape(-1))
+    K, R = int(K), int(rates_h.shape[0])
+    if K < 0:
+        raise ValueError(f"population: {K} simulations")
+    if out is None:
+        out = torch.empty((K, R), dtype=torch.int32, device="cuda")
+    elif not (out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (K, R) and out.is_contiguous()):
+        raise ValueError(f"population: a contiguous CUDA int32 tensor of shape {(K, R)} is needed, not {out.dtype} {tuple(out.shape)} on {out.device}")
+    rates_d = torch.from_numpy(rates_h).to(out.device)
+    _check(lib.aq_bernoulli_counts_i32(int(seed), int(k0), K, int(S), rates_d.data_ptr() if R else None, rates_h.ctypes.data if R else None, R,
+                                       out.data_ptr() if out.numel() else None, _stream_ptr()))
     return out
 
 

@@ -800,6 +800,20 @@ int aq_tonnage_reduce_f64(const double* ton_dev, long long K_chunk, long long F,
 int aq_tonnage_ndtri_f64(const double* p_dev, long long n, double* out_dev, void* stream);
 int aq_tonnage_uniform_f64(unsigned long long seed, const uint32_t* counters_dev, long long n, double* out_dev, void* stream);
 
+/* ---- --performance (population.hip): the samples behind the upper bound on the cage population (reference
+ * src/Results/upper_bound_calculation.R: if a fraction r of a stratum's images held cages, how many positives would a sample of S of them
+ * hold?).  For the simulations k0 <= k < k0 + K, on `stream`, one launch:
+ *   counts_dev[k - k0][i] ([K][R] int32, caller-held) = #{j < S : u(k, j) < rates[i]}, the comparison in fp64,
+ *   u(k, j) = the generator of --tonnage (Philox4x32-10, key = the low and the high word of `seed`) at counter (k, j >> 1, 16, 0): of its four
+ *   words (w0, w1, w2, w3) an even j takes (w1 : w0) and an odd j (w3 : w2), through the same 53-bit rule ((x >> 11) + 0.5) 2^-53, capped
+ *   below 1.  Slot 16 is none of the bootstrap's (0 .. 6).  Every rate is compared with the same uniforms, so a row never decreases where
+ *   the rates increase.  performance.counts_numpy gives the same bytes.
+ * rates_dev / rates_host = the R rates on the device and on the host (the same values; the host copy is the one that is checked).
+ * Refused before any launch: R outside 1 .. 16, S outside 1 .. 2^31 - 1, K < 0, k0 < 0, k0 + K > 2^32 (k is one counter word), a rate
+ * that is NaN or outside [0, 1], a null pointer.  K = 0 does nothing.  One wavefront per simulation, no atomics. */
+int aq_bernoulli_counts_i32(unsigned long long seed, long long k0, long long K, long long S, const double* rates_dev, const double* rates_host,
+                            int R, int32_t* counts_dev, void* stream);
+
 /* ---- --bathymetry (depth.hip): min, max, sum and count of the depth raster's cells under every facility (reference
  * src/utils_tonnage.py:591-665, add_facility_depth: rasterstats.zonal_stats(all_touched=True) over the union of a facility's circle and square
  * cages).  raster_dev: float32 [nrows][ncols], row 0 the northernmost; cell (r, c) is the half-open square [x0 + c dx, x0 + (c + 1) dx) x
