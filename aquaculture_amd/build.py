@@ -52,6 +52,7 @@ SOURCES = [
     ("coverage.hip", ["-ffp-contract=off"]),     # --tonnage-missing: boxes against the union of a pass's image regions; the fp64 band expression exactly as the host's (no fma)
     ("overlaps.hip", ["-ffp-contract=off"]),     # --dedup-overlaps: earlier boxes that overlap a download box, detections against their box's uncovered cells; the fp64 area sum in one written order (no fma)
     ("facility_sites.hip", ["-ffp-contract=off"]), # --facility-sites: facility rectangles from their cages, box joins that count / list their matches; comparisons and selections only
+    ("val.hip", ["-ffp-contract=off"]),          # yolov5/val.py: multi-label row expansion, label matching (fp32 IoU as written), the AP scans and interpolation in fp64 (no fma)
     ("engine.cpp", ["-x", "hip"]),
 ]
 # -packed-fp32-ops: no v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 in compiled kernels.  The SiLU epilogues run beside other waves' MFMAs (two

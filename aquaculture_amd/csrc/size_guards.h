@@ -139,4 +139,8 @@ inline bool overlap_bands_fit(ll nbands) { return nbands >= 1 && nbands + 1 < (1
 // line in oracle/guards.py: tests/test_gpu_facility_sites.py walks the edge through the launchers' refusals)
 inline bool facility_sites_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }
 
+// ---- val.hip ----  (images, (row, class) pairs, labels and detections of a call are 31-bit indices; the row arrays [B][M][5 + nc] are
+// indexed in 64 bits; like dedup's, no line in oracle/guards.py: tests/test_gpu_val.py walks the launchers' refusals)
+inline bool val_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }
+
 }  // namespace sg

@@ -106,6 +106,28 @@ def check_img_size(imgsz, s=32):
     return [max(math.ceil(x / s) * s, 0) for x in imgsz]
 
 
+def size_parts(sizes: Sequence[Tuple[int, int]]) -> Tuple[List[int], List[int]]:
+    """How a sweep orders images of mixed sizes (detect.py and val.py): the positions of the images of the most common size, in order, then
+    the positions of all others ordered by (size, position), so that equal sizes batch together."""
+    common = max(set(sizes), key=sizes.count)
+    main = [i for i, sz in enumerate(sizes) if sz == common]
+    odd = sorted((i for i, sz in enumerate(sizes) if sz != common), key=lambda i: (sizes[i], i))
+    return main, odd
+
+
+def split_decodable(sub: "LoadImages", jpeg_decode: str, scan=None) -> bool:
+    """Whether a part of one image size takes the split JPEG decode (entropy decoding in the workers, the rest on the GPU) under
+    ``--jpeg-decode`` auto / split / gpu: every file a baseline 4:2:0 JPEG (``scan`` = the result of scan_split_decodable when the caller
+    has it).  ``split`` refuses a part that does not qualify (``gpu``: the caller does, detect.py)."""
+    scan = sub.scan_split_decodable() if scan is None else scan
+    split = all(r is not None for r in scan)
+    if jpeg_decode == "split" and not split:
+        bad = [sub.files[i] for i, r in enumerate(scan) if r is None]
+        raise ValueError(f"--jpeg-decode split: {len(bad)} of {len(scan)} images are not baseline 4:2:0 JPEGs the split decoder reads "
+                         f"(use auto or host): {', '.join(bad[:3])}{' ...' if len(bad) > 3 else ''}")
+    return split
+
+
 def read_rgb(path: str) -> np.ndarray:
     from PIL import Image
     with Image.open(path) as im:
@@ -117,11 +139,12 @@ class LoadImages:
     keeps images ``i % world == rank`` (strided tile shard, one process per GPU)."""
 
     def __init__(self, source: str, img_size=640, stride=32, auto=True, shard: Tuple[int, int] = (0, 1), workers: int = 8,
-                 raw: bool = False, skip_stems=None):
+                 raw: bool = False, skip_stems=None, files: Optional[Sequence[str]] = None):
         """``raw``: yield the decoded image as is (the caller letterboxes on the device).  ``skip_stems``: tiles a previous run of
-        the sweep has finished (manifest.DoneManifest); they keep their place in the global numbering and are simply not loaded."""
+        the sweep has finished (manifest.DoneManifest); they keep their place in the global numbering and are simply not loaded.
+        ``files``: the image list itself, in the caller's order, instead of ``source`` (val.py: a split of a dataset yaml)."""
         self.raw = raw
-        files = list_images(source)
+        files = list_images(source) if files is None else list(files)
         self.total = len(files)
         rank, world = shard
         self.indices = list(range(rank, len(files), world))

@@ -28,7 +28,7 @@ import torch
 from . import dist as aqdist
 from . import postprocess
 from .checkpoint import load_checkpoint
-from .dataloader import LoadImages, check_img_size
+from .dataloader import LoadImages, check_img_size, size_parts, split_decodable
 
 UNSUPPORTED = ("view_img", "visualize", "update", "dnn")
 
@@ -909,9 +909,7 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                         sizes, all_split[0] = split_sizes, True
                 if sizes is None:
                     sizes = dataset.scan_sizes()
-                common = max(set(sizes), key=sizes.count)
-                main = [i for i, sz in enumerate(sizes) if sz == common]
-                odd = [i for i, sz in enumerate(sizes) if sz != common]
+                main, odd = size_parts(sizes)
             except Exception as e:                       # unreadable header: let the generic path report the file
                 log(f"note: header scan failed ({e}); using the generic loader")
                 main, odd = [], list(range(len(dataset)))
@@ -919,18 +917,13 @@ def run(weights, source, imgsz=(640, 640), conf_thres=0.25, iou_thres=0.45, max_
                 parts.append((dataset.subset(main), True))
             if odd:
                 log(f"note: {len(odd)} of {len(dataset)} images differ in size from the rest; they take the generic loader")
-                parts.append((dataset.subset(sorted(odd, key=lambda i: (sizes[i] if main else (0, 0), i))), False))
+                parts.append((dataset.subset(odd), False))
         for sub, fast in parts:
             if fast:
                 # split JPEG decode (Huffman on the host, the rest on the GPU) when every file of this part is a baseline 4:2:0 JPEG
                 split = False
                 if jpeg_decode != "host" and not decode_threads:
-                    scan = None if all_split[0] else sub.scan_split_decodable()
-                    split = all_split[0] or all(r is not None for r in scan)
-                    if jpeg_decode == "split" and not split:
-                        bad = [sub.files[i] for i, r in enumerate(scan) if r is None]
-                        raise ValueError(f"--jpeg-decode split: {len(bad)} of {len(scan)} images are not baseline 4:2:0 JPEGs the split decoder reads "
-                                         f"(use auto or host): {', '.join(bad[:3])}{' ...' if len(bad) > 3 else ''}")
+                    split = all_split[0] or split_decodable(sub, jpeg_decode)
                 if jpeg_decode == "gpu" and not split:
                     raise ValueError("--jpeg-decode gpu needs baseline 4:2:0 JPEGs throughout (use auto or host)")
                 use_gpu = jpeg_decode == "gpu" or (jpeg_decode == "auto" and split and len(sub) >= int(os.environ.get("AQ_JPEG_GPU_AUTO_MIN", 32768)))

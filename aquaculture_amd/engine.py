@@ -89,6 +89,7 @@ EXPORTS = (
     "aq_coverage_first_i32",
     "aq_overlap_partners_f64", "aq_overlap_clip_f64",
     "aq_facility_bounds_f64", "aq_box_join_count_i32", "aq_box_join_list_i32",
+    "aq_val_expand_scratch_bytes", "aq_val_expand_rows_f32", "aq_val_match", "aq_val_score_chunk", "aq_val_scores_scratch_bytes", "aq_val_scores_f64",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -250,6 +251,14 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_facility_bounds_f64.argtypes = [vp, vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp]
     lib.aq_box_join_count_i32.argtypes = [vp, vp, C.c_longlong, vp, vp, vp, vp, C.c_longlong, C.c_longlong, vp, vp, vp]
     lib.aq_box_join_list_i32.argtypes = [vp, vp, C.c_longlong, vp, vp, vp, vp, C.c_longlong, C.c_longlong, vp, vp, vp, C.c_longlong, vp]
+    lib.aq_val_expand_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.aq_val_expand_scratch_bytes.restype = sz
+    lib.aq_val_expand_rows_f32.argtypes = [vp, i32, i32, i32, f32, i32, vp, sz, vp, vp, vp]
+    lib.aq_val_match.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp, vp, C.c_longlong, vp, vp]
+    lib.aq_val_score_chunk.argtypes = []
+    lib.aq_val_scores_scratch_bytes.argtypes = [C.c_longlong, C.c_longlong]
+    lib.aq_val_scores_scratch_bytes.restype = sz
+    lib.aq_val_scores_f64.argtypes = [vp, vp, C.c_longlong, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, sz, vp, vp, vp, vp, vp]
     lib.aq_augment_geometry.argtypes = [i32, i32, i32, vp, C.POINTER(i32)]
     lib.aq_augment_taps.argtypes = [i32, i32, i32, vp]
     lib.aq_stem_conv_scaled.argtypes = [vp, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]
@@ -2044,6 +2053,126 @@ def box_join_list(qbox: torch.Tensor, qgroup: torch.Tensor, kbox: Optional[torch
     for t_ in (qbox, qgroup, keys["box"], keys["kid"], keys["start"], offset, out):
         t_.record_stream(torch.cuda.current_stream())
     return offset_h, out
+
+
+# ---- yolov5/val.py: aq_val_expand_rows_f32, aq_val_match, aq_val_scores_f64 (mAP against YOLO labels) ----
+
+VAL_NMS_ROWS = 131071                      # aq_nms takes fewer than 131072 rows per image
+
+
+def _val_tensor(name: str, t_: torch.Tensor, dt, shape) -> None:
+    if not t_.is_cuda or t_.dtype != dt or not t_.is_contiguous() or t_.ndim != len(shape) or any(a != b for a, b in zip(t_.shape, shape)):
+        raise ValueError(f"val: {name} has to be a contiguous CUDA {dt} tensor of shape {shape}, not {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+
+
+def val_expand_rows(pred: torch.Tensor, conf_thres: float, M: Optional[int] = None, rows: Optional[torch.Tensor] = None,
+                    counts: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """aq_val_expand_rows_f32 on the current stream: pred float32 CUDA [B, N, 5 + nc] -> (rows float32 CUDA [B, M, 5 + nc], counts int32 CUDA
+    [B]): upstream's multi_label candidates, one row per (source row, class) that passes, in that order, for ``nms`` in full-rows mode; M
+    defaults to min(N nc, 131071).  counts holds the rows emitted per image whatever M is; when one exceeds M, rows is not written at all.
+    val.expand_rows_numpy gives the same bytes."""
+    _require_gpu()
+    lib = load_library()
+    if pred.dim() != 3 or pred.shape[2] < 6:
+        raise ValueError("val: pred has to be [B, N, 5 + nc] with nc >= 1")
+    B, N, no = (int(v) for v in pred.shape)
+    nc = no - 5
+    _val_tensor("pred", pred, torch.float32, (B, N, no))
+    M = min(N * nc, VAL_NMS_ROWS) if M is None else int(M)
+    if rows is None:
+        rows = torch.empty((B, max(M, 0), no), dtype=torch.float32, device=pred.device)
+    if counts is None:
+        counts = torch.empty((B,), dtype=torch.int32, device=pred.device)
+    _val_tensor("rows", rows, torch.float32, (B, M, no))
+    _val_tensor("counts", counts, torch.int32, (B,))
+    need = int(lib.aq_val_expand_scratch_bytes(B, N, nc))
+    if scratch is None or scratch.numel() < need:
+        scratch = torch.empty(max(need, 4), dtype=torch.uint8, device=pred.device)
+    _check(lib.aq_val_expand_rows_f32(pred.data_ptr(), B, N, nc, float(conf_thres), M, scratch.data_ptr(), scratch.numel(),
+                                      rows.data_ptr() if rows.numel() else None, counts.data_ptr(), _stream_ptr()))
+    for t_ in (pred, rows, counts, scratch):
+        t_.record_stream(torch.cuda.current_stream())
+    return rows, counts
+
+
+def val_match(dets: torch.Tensor, counts: torch.Tensor, label_box: torch.Tensor, label_cls: torch.Tensor, label_start: torch.Tensor,
+              label_start_host: np.ndarray, geom: torch.Tensor, iouv: np.ndarray, out_conf: torch.Tensor, out_cls: torch.Tensor,
+              out_bits: torch.Tensor, total: torch.Tensor, scratch: Optional[torch.Tensor] = None) -> None:
+    """aq_val_match on the current stream: dets float32 CUDA [B, max_det, 6] and counts int32 CUDA [B] as ``nms`` returns them; label_box
+    float32 CUDA [L, 4] (original pixels), label_cls int32 CUDA [L], label_start int32 CUDA [B + 1] and its host copy; geom float32 CUDA
+    [B, 5] = (pad x, pad y, gain, w0, h0); iouv float32 [10] in host memory.  Appends the batch's detections to out_conf float32, out_cls
+    int32 and out_bits int16 (the uint16 words) CUDA [cap] at total int64 CUDA [1], which it advances.  val.match_numpy gives the same values."""
+    _require_gpu()
+    if dets.dim() != 3 or dets.shape[2] != 6:
+        raise ValueError("val: dets has to be [B, max_det, 6]")
+    B, max_det = int(dets.shape[0]), int(dets.shape[1])
+    L, cap = int(label_box.shape[0]), int(out_conf.shape[0])
+    for name, t_, dt, shape in (("dets", dets, torch.float32, (B, max_det, 6)), ("counts", counts, torch.int32, (B,)),
+                                ("label_box", label_box, torch.float32, (L, 4)), ("label_cls", label_cls, torch.int32, (L,)),
+                                ("label_start", label_start, torch.int32, (B + 1,)), ("geom", geom, torch.float32, (B, 5)),
+                                ("out_conf", out_conf, torch.float32, (cap,)), ("out_cls", out_cls, torch.int32, (cap,)),
+                                ("out_bits", out_bits, torch.int16, (cap,)), ("total", total, torch.int64, (1,))):
+        _val_tensor(name, t_, dt, shape)
+    ls = np.ascontiguousarray(label_start_host, dtype=np.int32)
+    iou = np.ascontiguousarray(iouv, dtype=np.float32)
+    if ls.shape != (B + 1,) or iou.shape != (10,):
+        raise ValueError("val: label_start_host has to hold B + 1 starts and iouv ten thresholds")
+    if scratch is None or scratch.numel() < 10 * L:
+        scratch = torch.empty(max(10 * L, 1), dtype=torch.int32, device=dets.device)
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    _check(load_library().aq_val_match(ptr(dets), ptr(counts), B, max_det, ptr(label_box), ptr(label_cls), label_start.data_ptr(), ls.ctypes.data, L,
+                                       ptr(geom), iou.ctypes.data, scratch.data_ptr(), ptr(out_conf), ptr(out_cls), ptr(out_bits), cap, total.data_ptr(),
+                                       _stream_ptr()))
+    for t_ in (dets, counts, label_box, label_cls, label_start, geom, out_conf, out_cls, out_bits, total, scratch):
+        t_.record_stream(torch.cuda.current_stream())
+
+
+def val_score_runs(run_range: np.ndarray) -> np.ndarray:
+    """run_chunk0 int32 [C + 1] of aq_val_scores_f64: the exclusive scan of the runs' chunk counts."""
+    ch = int(load_library().aq_val_score_chunk())
+    rr = np.asarray(run_range, dtype=np.int64).reshape(-1, 2)
+    out = np.zeros(rr.shape[0] + 1, np.int64)
+    np.cumsum((rr[:, 1] - rr[:, 0] + ch - 1) // ch, out=out[1:])
+    if out[-1] >= 1 << 31:
+        raise ValueError("val: more than 2^31 chunks")
+    return out.astype(np.int32)
+
+
+def val_scores(bits: torch.Tensor, conf: torch.Tensor, run_range: np.ndarray, n_l: np.ndarray, x: np.ndarray, px: np.ndarray,
+               times: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """aq_val_scores_f64 on the current stream: bits int16 CUDA [n] (the uint16 words) and conf float32 CUDA [n], sorted by (class,
+    -confidence, index); run_range int64 [C, 2] and n_l int32 [C] in host memory: the run and the label count of every class that has
+    labels; x float64 [nx] and px float64 [npx] in host memory -> (ap [C, 10], p [C, npx], r [C, npx], pr [C, npx]) float64 CUDA.
+    val.scores_numpy gives the same bytes.  times = a dict that receives "scores_ms"."""
+    _require_gpu()
+    lib = load_library()
+    n = int(bits.shape[0])
+    _val_tensor("bits", bits, torch.int16, (n,))
+    _val_tensor("conf", conf, torch.float32, (n,))
+    dev = bits.device
+    rr = np.ascontiguousarray(run_range, dtype=np.int64).reshape(-1, 2)
+    C_ = int(rr.shape[0])
+    nl = np.ascontiguousarray(n_l, dtype=np.int32)
+    xs, pxs = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(px, dtype=np.float64)
+    if nl.shape != (C_,):
+        raise ValueError("val: n_l has to hold one label count per run")
+    rc0 = val_score_runs(rr)
+    up = lambda a: torch.from_numpy(a).to(dev) if a.size else torch.empty(0, dtype=torch.from_numpy(a).dtype, device=dev)
+    rr_d, nl_d, rc0_d, x_d, px_d = up(rr), up(nl), up(rc0), up(xs), up(pxs)
+    need = int(lib.aq_val_scores_scratch_bytes(n, int(rc0[-1])))
+    scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    ap = torch.empty((C_, 10), dtype=torch.float64, device=dev)
+    p, r, pr = (torch.empty((C_, pxs.shape[0]), dtype=torch.float64, device=dev) for _ in range(3))
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    ph = _Phases(times)
+    ph.mark()
+    _check(lib.aq_val_scores_f64(ptr(bits), ptr(conf), n, ptr(rr_d), rr.ctypes.data, ptr(nl_d), rc0_d.data_ptr(), rc0.ctypes.data, C_,
+                                 x_d.data_ptr(), int(xs.shape[0]), px_d.data_ptr(), int(pxs.shape[0]), scratch.data_ptr(), scratch.numel(),
+                                 ptr(ap), ptr(p), ptr(r), ptr(pr), _stream_ptr()))
+    ph.done("scores_ms")
+    for t_ in (bits, conf, rr_d, nl_d, rc0_d, x_d, px_d, scratch, ap, p, r, pr):
+        t_.record_stream(torch.cuda.current_stream())
+    return ap, p, r, pr
 
 
 # ---- --land-filter: aq_land_filter_f64 (detection boxes against the segments of the land polygons) ----

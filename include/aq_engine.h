@@ -1018,6 +1018,53 @@ int aq_box_join_list_i32(const double* qbox_dev, const int32_t* qgroup_dev, long
                          const int32_t* group_start_dev, const int32_t* group_start_host, long long N, long long G,
                          const long long* offset_dev, const long long* offset_host, int32_t* list_dev, long long total, void* stream);
 
+/* ---- yolov5/val.py: mAP against YOLO labels (csrc/val.hip) ----
+ * Upstream's second entry point on trained weights [UPSTREAM val.py run(), process_batch; utils/metrics.py ap_per_class, compute_ap, box_iou;
+ * utils/general.py non_max_suppression(multi_label=True)].  Every launcher runs on `stream`, allocates nothing and stores with plain vector
+ * stores; products, sums and quotients are rounded once each, as written (no fma), so aquaculture_amd.val's numpy restatements
+ * (expand_rows_numpy, match_numpy, scores_numpy) give the same bytes.  Refused before anything is launched: a count outside its range, a
+ * null pointer, an unaligned array, starts or runs that decrease or leave their array, a scratch that is too small.
+ *
+ * aq_val_expand_rows_f32: pred_dev [B][N][5 + nc] (what aq_engine_forward_raw writes) -> rows_dev [B][M][5 + nc] for aq_nms_opts in full-rows
+ * mode: one row per (source row r, class j) with obj > conf_thres and obj * cls_j > conf_thres (one fp32 product), in ascending (r, j),
+ * carrying the source row's box and obj, cls_j in column 5 + j and zeros in the other class columns.  count_dev [B] = the rows emitted per
+ * image, whatever M is.  Rows count[b] .. M - 1 get obj = 0 and no other store.  If any image emits more than M rows, rows_dev is not
+ * written at all.  1 <= M <= N * nc < 2^31, B <= 65535.  scratch_dev: aq_val_expand_scratch_bytes(B, N, nc), 4-byte aligned. */
+size_t aq_val_expand_scratch_bytes(int B, int N, int nc);
+int aq_val_expand_rows_f32(const float* pred_dev, int B, int N, int nc, float conf_thres, int M, void* scratch_dev, size_t scratch_bytes,
+                           float* rows_dev, int32_t* count_dev, void* stream);
+/* aq_val_match: dets_dev [B][max_det] and counts_dev [B] as aq_nms_opts wrote them (network pixels, descending confidence; a count is read
+ * as min(max(count, 0), max_det)); image b's labels are label_start[b] .. label_start[b + 1] - 1 (int32 [B + 1]) of label_box_dev [L][4]
+ * fp32 (x1, y1, x2, y2 in original pixels, 16-byte aligned) and label_cls_dev [L] int32; geom_dev [B][5] fp32 = (pad x, pad y, gain, w0,
+ * h0).  Per detection: v = (v - pad) / gain, clipped to [0, w0] or [0, h0] (scale_boxes, no rounding); iou = inter / (area_label + area_det
+ * - inter + 1e-7) with inter = clamp(min(x2) - max(x1), 0) * clamp(min(y2) - max(y1), 0), all fp32 in that order; its best label is the
+ * label of its class with the largest iou, the higher index among equal ones; bit i of its word is set iff iou >= iouv_host[i] and no
+ * detection of lower index has the same best label and reaches iouv_host[i] (i < 10).  Image b's detection d goes to position
+ * total_dev[0] + sum of the counts of the images before b + d of conf_out_dev (fp32), cls_out_dev (int32) and bits_out_dev (uint16), when that
+ * position is below cap; a second launch adds the batch's detections to total_dev[0] (int64, 8-byte aligned).  scratch_dev: 10 L int32.
+ * One wavefront per image.  B = 0 does nothing. */
+int aq_val_match(const aq_det* dets_dev, const int32_t* counts_dev, int B, int max_det, const float* label_box_dev,
+                 const int32_t* label_cls_dev, const int32_t* label_start_dev, const int32_t* label_start_host, long long L,
+                 const float* geom_dev, const float* iouv_host, int32_t* scratch_dev, float* conf_out_dev, int32_t* cls_out_dev,
+                 uint16_t* bits_out_dev, long long cap, long long* total_dev, void* stream);
+/* aq_val_scores_f64: bits_dev [n] uint16 and conf_dev [n] fp32 sorted by (class ascending, confidence descending, detection index
+ * ascending); run c of C (one per class that has labels, ascending) is the elements run_range[c][0] .. run_range[c][1] - 1 (int64 [C][2]),
+ * n_l_dev [C] int32 its number of labels, run_chunk0 [C + 1] int32 the exclusive scan of ceil(run length / aq_val_score_chunk()).  With
+ * tpc_k the inclusive integer sum of bit j over the run, recall_k = tpc_k / (n_l + 1e-16), precision_k = tpc_k / (k + 1) in fp64:
+ * ap_dev [C][10] = the trapezoid sum, added in ascending x one term (x[k + 1] - x[k]) * (y[k + 1] + y[k]) / 2 at a time, of y = interp(x,
+ * [0, recall.., 1], [1, precision.., 0] under its running maximum from the right) on x_dev [nx] (nx <= 128); for threshold 0, on px_dev
+ * [npx]: r_dev [C][npx] = interp(-px, -conf, recall, left = 0), p_dev = interp(-px, -conf, precision, left = 1), pr_dev = interp(px, mrec,
+ * mpre).  interp is np.interp's rule: j = the last index with xp[j] <= x; fp[j] when j is the last index or xp[j] == x, else
+ * (fp[j + 1] - fp[j]) / (xp[j + 1] - xp[j]) * (x - xp[j]) + fp[j].  An empty run gives zeros throughout.  scratch_dev:
+ * aq_val_scores_scratch_bytes(n, run_chunk0[C]) = 120 bytes per detection + 240 per chunk, 8-byte aligned.  C = 0 does nothing. */
+int aq_val_score_chunk(void);
+size_t aq_val_scores_scratch_bytes(long long n, long long nchunks);
+int aq_val_scores_f64(const uint16_t* bits_dev, const float* conf_dev, long long n, const long long* run_range_dev,
+                      const long long* run_range_host, const int32_t* n_l_dev, const int32_t* run_chunk0_dev,
+                      const int32_t* run_chunk0_host, int C, const double* x_dev, int nx, const double* px_dev, int npx,
+                      void* scratch_dev, size_t scratch_bytes, double* ap_dev, double* p_dev, double* r_dev, double* pr_dev,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,151 @@
+#!/usr/bin/env python3
+"""What the three device steps of yolov5/val.py cost on one MI355X.  Each figure: the median of `--repeats` (default
+5) timed calls after two warm-ups, with minimum and maximum, by HIP events around the call on the current stream.
+
+  expand    aq_val_expand_rows_f32 at 25,200 rows x 5 classes, batch 32 (the default val.py batch at 640 px), on a synthetic pred in which
+            `--share` (default 0.02) of the rows have obj above the threshold, every class of such a row passing
+  match     aq_val_match at 32 images x 300 detections x 20 labels, the detections scattered around the labels
+  scores    aq_val_scores_f64 (val.score_gpu: torch's two stable sorts, then the launcher) at 10^7 detections over 5 classes, against
+            val.score_cpu -- the numpy restatement -- on the same host, once; the two results have to be the same bytes
+
+With `--map DATA.yaml --weights W.pt`: val.py on that split under fp32, f16x3, bf16, fp8 and fp8w, mAP beside the sweep's images/s.
+
+    python tools/bench_val.py [--repeats 5] [--share 0.02] [--detections 10000000] [--no-cpu] [--map DATA.yaml --weights W.pt] [--out result.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def spread(v):
+    return {"median": statistics.median(v), "min": min(v), "max": max(v), "values": list(v)}
+
+
+def timed(fn, repeats):
+    import torch
+    for _ in range(2):
+        fn()
+    out = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return spread(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--share", type=float, default=0.02)
+    ap.add_argument("--detections", type=int, default=10_000_000)
+    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--map", default=None, metavar="DATA.yaml")
+    ap.add_argument("--weights", default=None)
+    ap.add_argument("--out", default=None)
+    opt = ap.parse_args()
+    import numpy as np
+    import torch
+    from aquaculture_amd import engine, val
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+    res = {"device": torch.cuda.get_device_name(dev), "repeats": opt.repeats}
+
+    # expand
+    B, N, nc = 32, 25200, 5
+    pred = rng.random((B, N, 5 + nc)).astype(np.float32)
+    pred[..., 4] = np.where(rng.random((B, N)) < opt.share, 0.5, 0.0005)
+    pred[..., 5:] = 0.5
+    pred_d = torch.from_numpy(pred).to(dev)
+    M = min(N * nc, engine.VAL_NMS_ROWS)
+    rows = torch.empty((B, M, 5 + nc), dtype=torch.float32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    scratch = torch.empty(engine.load_library().aq_val_expand_scratch_bytes(B, N, nc), dtype=torch.uint8, device=dev)
+    res["expand_ms"] = timed(lambda: engine.val_expand_rows(pred_d, 0.001, M, rows, counts, scratch), opt.repeats)
+    res["expand"] = {"B": B, "N": N, "nc": nc, "share": opt.share, "rows_emitted_per_image": float(counts.float().mean())}
+
+    # match
+    Bm, D, L = 32, 300, 20
+    lb = np.concatenate([rng.integers(0, 5, (Bm * L, 1)), rng.random((Bm * L, 2)) * 0.8 + 0.1, rng.random((Bm * L, 2)) * 0.1 + 0.02], 1).astype(np.float32)
+    lbox = val.label_boxes(lb, 1024, 1024).reshape(Bm, L, 4)
+    pick = rng.integers(0, L, (Bm, D))
+    dets = np.zeros((Bm, D, 6), np.float32)
+    geom = val.letterbox_geom((640, 640), (1024, 1024))
+    dets[..., :4] = (np.take_along_axis(lbox, pick[..., None].repeat(4, 2), 1) + rng.normal(0, 4, (Bm, D, 4))) * geom[2]
+    dets[..., 4] = np.sort(rng.random((Bm, D)), 1)[:, ::-1]
+    dets[..., 5] = np.take_along_axis(lb[:, 0].reshape(Bm, L), pick, 1)
+    dets_d, cnt_d = torch.from_numpy(dets).to(dev), torch.full((Bm,), D, dtype=torch.int32, device=dev)
+    stats = val._DeviceStats(Bm * D, dev)
+    boxes, classes, geoms = [lbox[b] for b in range(Bm)], [lb[:, 0].reshape(Bm, L)[b] for b in range(Bm)], np.tile(geom, (Bm, 1))
+    start = np.arange(Bm + 1, dtype=np.int32) * L
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    lbox_d, lcls_d, start_d, geom_d = up(lbox.reshape(-1, 4)), up(lb[:, 0].astype(np.int32)), up(start), up(geoms)
+    sc = torch.empty(10 * Bm * L, dtype=torch.int32, device=dev)
+
+    def match():
+        stats.total.zero_()
+        engine.val_match(dets_d, cnt_d, lbox_d, lcls_d, start_d, start, geom_d, val.IOUV, stats.conf, stats.cls, stats.bits, stats.total, sc)
+    res["match_ms"] = timed(match, opt.repeats)
+    res["match"] = {"B": Bm, "detections": D, "labels": L, "correct_at_0.5": int((stats.bits[:Bm * D] & 1).sum())}
+
+    # scores
+    n = opt.detections
+    conf = rng.random(n).astype(np.float32)
+    cls = rng.integers(0, 5, n).astype(np.int32)
+    bits = np.where(rng.random(n) < conf, (1 << np.minimum(rng.integers(0, 14, n), 10)) - 1, 0).astype(np.uint16)
+    label_counts = np.full(5, n // 8, np.int64)
+    conf_d, cls_d, bits_d = up(conf), up(cls), up(bits.view(np.int16))
+    kernel = []
+
+    def scores():
+        t = {}
+        out = val.score_gpu(conf_d, cls_d, bits_d, label_counts, times=t)
+        kernel.append(t["scores_ms"])
+        return out
+    for _ in range(2):
+        scores()
+    kernel.clear()
+    wall = []
+    for _ in range(opt.repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = scores()
+        wall.append((time.perf_counter() - t0) * 1e3)
+    res["scores_kernels_ms"] = spread(kernel)
+    res["scores_with_sort_and_copies_ms"] = spread(wall)
+    res["scores"] = {"detections": n, "classes": 5, "scratch_bytes": int(engine.load_library().aq_val_scores_scratch_bytes(n, int(engine.val_score_runs(
+        np.array([[0, n]]))[-1])))}
+    if not opt.no_cpu:
+        t0 = time.perf_counter()
+        want = val.score_cpu(conf, cls, bits, label_counts)
+        res["scores_numpy_ms"] = (time.perf_counter() - t0) * 1e3
+        res["scores_same_bytes"] = all(g.tobytes() == w.tobytes() for g, w in zip(got[2:], want[2:]))
+
+    # the per-precision table
+    if opt.map:
+        table = {}
+        with tempfile.TemporaryDirectory() as tmp:
+            for prec in ("fp32", "f16x3", "bf16", "fp8", "fp8w"):
+                o = val.parse_opt(["--data", opt.map, "--weights", opt.weights, "--precision", prec, "--project", tmp, "--name", prec, "--quiet"])
+                s = val.run(o, log=lambda *_: None)
+                meta = json.load(open(os.path.join(tmp, prec, "val.json")))
+                table[prec] = {"P": s["mp"], "R": s["mr"], "mAP50": s["map50"], "mAP50-95": s["map"], "images_per_s": meta["images_per_s"],
+                               "images": meta["images"], "detections": meta["detections"]}
+        res["precisions"] = table
+    print(json.dumps(res, indent=1))
+    if opt.out:
+        with open(opt.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
