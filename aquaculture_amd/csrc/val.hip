@@ -1,7 +1,8 @@
 // yolov5/val.py: the three device steps behind upstream's mAP table ([UPSTREAM val.py run(), process_batch; utils/metrics.py ap_per_class,
 // compute_ap, box_iou]).  Built with -ffp-contract=off: every product, sum and quotient below is rounded once, as written,
 // so each output is bit-identical to its numpy restatement in aquaculture_amd/val.py.  Nothing is allocated, everything runs on the caller's
-// stream, every store is a plain vector store; the only atomics are integer minima (order-free) in the matcher.
+// stream, every store is a plain vector store; the only atomics are integer minima in the matcher and integer maxima and sums in the confusion
+// step (vector atomics, all order-free).
 //
 // aq_val_expand_rows_f32: upstream's multi_label branch of non_max_suppression as rows the existing NMS takes.  pred [B][N][5 + nc] ->
 //   rows [B][M][5 + nc]: one row per (source row r, class j) with obj > conf and obj * cls_j > conf (one fp32 product), in (r, j) ascending
@@ -19,6 +20,15 @@
 //   the minimum of (its best label, i) is the detection itself.  The minima live in LDS for up to 512 labels, else in the image's slice of
 //   the caller's scratch.  Confidence, class and bits are appended at total + the counts of the images before; a one-lane launch then adds
 //   the batch's count to total.
+//
+// aq_val_confusion: [UPSTREAM utils/metrics.py ConfusionMatrix.process_batch] as the closed rule of DESIGN.md section 28, on aq_val_match's
+//   inputs, scale_box and label_iou, one wavefront per image.  Pass 1: lane l takes the detections l, l + 64, ...; one with conf above the
+//   threshold walks the labels and raises the 64-bit key (iou bits << 32) | detection of its best label of any class -- the largest IoU above
+//   the threshold, the higher index among equals -- with an integer atomicMax (IoUs above a positive threshold order as their bit patterns);
+//   its best label goes to scratch [B][max_det].  Pass 2: lane l takes the labels l, l + 64, ...: a non-zero key names the detection the label
+//   keeps, matrix[its class][label class] += 1, else matrix[nc][label class] += 1.  Pass 3, only when the image has a kept pair: a detection
+//   that takes part and is in no label's key adds matrix[its class][nc] += 1.  The keys live in LDS for up to 512 labels, else in the
+//   image's slice of the scratch.  The increments are 64-bit integer vector atomics; maxima and sums do not depend on scheduling.
 //
 // aq_val_scores_f64: ap_per_class after the host's stable sort by (class, -confidence, index).  Every class with labels is a run of the
 //   sorted arrays, cut into chunks of 2048 (256 threads x 8 consecutive elements); all launches but the last have one workgroup per (chunk,
@@ -154,21 +164,35 @@ struct MatchParams {
     float iouv[10];
 };
 
+// scale_boxes for one detection: subtract the pad, divide by the gain, clip to the original image (x1, y1, x2, y2 in .x .y .z .w)
+__device__ __forceinline__ float4 scale_box(const aq_det& t, float padx, float pady, float gain, float w0, float h0) {
+    float4 d;
+    d.x = fminf(fmaxf((t.x1 - padx) / gain, 0.0f), w0);
+    d.y = fminf(fmaxf((t.y1 - pady) / gain, 0.0f), h0);
+    d.z = fminf(fmaxf((t.x2 - padx) / gain, 0.0f), w0);
+    d.w = fminf(fmaxf((t.y2 - pady) / gain, 0.0f), h0);
+    return d;
+}
+
+// box_iou of a label g and a detection d of area area_d = (d.z - d.x) * (d.w - d.y): inter / (area_l + area_d - inter + 1e-7), in that order
+__device__ __forceinline__ float label_iou(const float4 g, const float4 d, float area_d) {
+    const float area_l = (g.z - g.x) * (g.w - g.y);
+    float iw = fminf(g.z, d.z) - fmaxf(g.x, d.x);
+    float ih = fminf(g.w, d.w) - fmaxf(g.y, d.y);
+    iw = iw > 0.0f ? iw : 0.0f;
+    ih = ih > 0.0f ? ih : 0.0f;
+    const float inter = iw * ih;
+    return inter / (area_l + area_d - inter + 1e-7f);
+}
+
 // the detection's best label: same class, largest IoU, the higher index among equal IoUs; -1 without a label of its class
-__device__ __forceinline__ int best_label(const MatchParams& p, int ls, int le, float x1, float y1, float x2, float y2, int cls, float* best_iou) {
-    const float area_d = (x2 - x1) * (y2 - y1);
+__device__ __forceinline__ int best_label(const MatchParams& p, int ls, int le, const float4 d, int cls, float* best_iou) {
+    const float area_d = (d.z - d.x) * (d.w - d.y);
     int best = -1;
     float bi = 0.0f;
     for (int l = ls; l < le; ++l) {
         if (p.lcls[l] != cls) continue;
-        const float4 g = p.lbox[l];
-        const float area_l = (g.z - g.x) * (g.w - g.y);
-        float iw = fminf(g.z, x2) - fmaxf(g.x, x1);
-        float ih = fminf(g.w, y2) - fmaxf(g.y, y1);
-        iw = iw > 0.0f ? iw : 0.0f;
-        ih = ih > 0.0f ? ih : 0.0f;
-        const float inter = iw * ih;
-        const float iou = inter / (area_l + area_d - inter + 1e-7f);
+        const float iou = label_iou(p.lbox[l], d, area_d);
         if (best < 0 || iou >= bi) { best = l; bi = iou; }
     }
     *best_iou = bi;
@@ -192,12 +216,9 @@ __global__ __launch_bounds__(64) void match_kernel(const MatchParams p) {
     for (int pass = 0; pass < 2; ++pass) {
         for (int d = lane; d < cnt; d += 64) {
             const aq_det t = p.dets[(long long)b * p.max_det + d];
-            // scale_boxes: subtract the pad, divide by the gain, clip to the original image
-            const float x1 = fminf(fmaxf((t.x1 - padx) / gain, 0.0f), w0), y1 = fminf(fmaxf((t.y1 - pady) / gain, 0.0f), h0);
-            const float x2 = fminf(fmaxf((t.x2 - padx) / gain, 0.0f), w0), y2 = fminf(fmaxf((t.y2 - pady) / gain, 0.0f), h0);
             const int cls = (int)t.cls;
             float iou;
-            const int l = best_label(p, ls, le, x1, y1, x2, y2, cls, &iou);
+            const int l = best_label(p, ls, le, scale_box(t, padx, pady, gain, w0, h0), cls, &iou);
             if (pass == 0) {
                 if (l >= 0)
                     for (int i = 0; i < 10; ++i)
@@ -224,6 +245,106 @@ __global__ __launch_bounds__(64) void match_advance_kernel(const MatchParams p) 
     for (int i = threadIdx.x; i < p.B; i += 64) s += min(max(p.counts[i], 0), p.max_det);
     s = wave_sum_i64(s);
     if (threadIdx.x == 0) p.total[0] += s;
+}
+
+// -------------------------------------------------------------- confusion ---------------------------------------------------------------
+constexpr int kNotTakingPart = -2;     // best[d] of a detection at or below the confidence threshold; -1 = takes part, no label above the IoU
+
+struct ConfusionParams {
+    const aq_det* dets;        // [B][max_det]
+    const int* counts;         // [B]
+    const float4* lbox;        // [L]
+    const int* lcls;           // [L]
+    const int* lstart;         // [B + 1]
+    const float* geom;         // [B][5]
+    unsigned long long* keys;  // scratch [L]: (iou bits << 32) | detection, 0 = no detection
+    int* best;                 // scratch [B][max_det]
+    unsigned long long* matrix;   // [(nc + 1)][(nc + 1)], [predicted][true]; added to
+    int* image;                // out [B][4]
+    int* flag;                 // [1]: set to 1 when a class outside [0, nc) is met, never cleared
+    int B, max_det, L, nc;
+    float conf, iou;
+};
+
+__device__ __forceinline__ unsigned long long key_load(const unsigned long long* k) {
+    return __hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (the keys were raised by atomics: read them where those landed)
+}
+
+__global__ __launch_bounds__(64) void confusion_kernel(const ConfusionParams p) {
+    __shared__ unsigned long long lds_key[kMatchLdsLabels];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int cnt = min(max(p.counts[b], 0), p.max_det);
+    const int ls = min(max(p.lstart[b], 0), p.L);
+    const int le = min(max(p.lstart[b + 1], ls), p.L);
+    const int nl = le - ls;
+    unsigned long long* keys = nl <= kMatchLdsLabels ? lds_key : p.keys + ls;
+    for (int i = lane; i < nl; i += 64) keys[i] = 0ULL;
+    __syncthreads();
+    const float padx = p.geom[b * 5 + 0], pady = p.geom[b * 5 + 1], gain = p.geom[b * 5 + 2], w0 = p.geom[b * 5 + 3], h0 = p.geom[b * 5 + 4];
+    const aq_det* dets = p.dets + (long long)b * p.max_det;
+    int* best = p.best + (long long)b * p.max_det;
+    const float ncf = (float)p.nc;
+    // pass 1: every detection that takes part finds its best label of any class and raises that label's key
+    int part = 0, bad = 0;
+    for (int d = lane; d < cnt; d += 64) {
+        const aq_det t = dets[d];
+        if (!(t.cls >= 0.0f && t.cls < ncf)) bad = 1;
+        int l = kNotTakingPart;
+        if (t.conf > p.conf) {
+            ++part;
+            l = -1;
+            const float4 box = scale_box(t, padx, pady, gain, w0, h0);
+            const float area_d = (box.z - box.x) * (box.w - box.y);
+            float bi = 0.0f;
+            for (int k = ls; k < le; ++k) {
+                const float iou = label_iou(p.lbox[k], box, area_d);
+                if (iou > p.iou && iou >= bi) { l = k; bi = iou; }
+            }
+            if (l >= 0) atomicMax(&keys[l - ls], ((unsigned long long)__float_as_uint(bi) << 32) | (unsigned)d);
+        }
+        best[d] = l;
+    }
+    for (int i = lane; i < nl; i += 64) {
+        const int gc = p.lcls[ls + i];
+        if (gc < 0 || gc >= p.nc) bad = 1;
+    }
+    part = wave_sum_i32(part);
+    bad = wave_sum_i32(bad);
+    __syncthreads();
+    if (bad) {                                                                  // (uniform) a class outside [0, nc): the image adds nothing
+        if (lane == 0) {
+            p.flag[0] = 1;
+            p.image[b * 4 + 0] = nl; p.image[b * 4 + 1] = 0; p.image[b * 4 + 2] = 0; p.image[b * 4 + 3] = 0;
+        }
+        return;
+    }
+    // pass 2: every label's kept detection and its matrix entry
+    const long long n1 = (long long)p.nc + 1;
+    int kept = 0, same = 0;
+    for (int i = lane; i < nl; i += 64) {
+        const unsigned long long key = key_load(&keys[i]);
+        const int gc = p.lcls[ls + i];
+        int row = p.nc;
+        if (key) {
+            row = (int)dets[min((int)(unsigned)key, cnt - 1)].cls;              // (the low word is a detection below cnt whose class pass 1 found in range)
+            ++kept;
+            same += row == gc;
+        }
+        atomicAdd(&p.matrix[row * n1 + gc], 1ULL);
+    }
+    kept = wave_sum_i32(kept);
+    same = wave_sum_i32(same);
+    // pass 3: with a kept pair in the image, every detection that takes part and that no label keeps is a background entry
+    if (kept > 0)
+        for (int d = lane; d < cnt; d += 64) {
+            const int l = best[d];                                              // (this lane's own store of pass 1)
+            if (l == kNotTakingPart) continue;
+            if (l >= 0 && (unsigned)key_load(&keys[l - ls]) == (unsigned)d) continue;
+            atomicAdd(&p.matrix[(int)dets[d].cls * n1 + p.nc], 1ULL);
+        }
+    if (lane == 0) {
+        p.image[b * 4 + 0] = nl; p.image[b * 4 + 1] = part; p.image[b * 4 + 2] = kept; p.image[b * 4 + 3] = same;
+    }
 }
 
 // ---------------------------------------------------------------- scores ----------------------------------------------------------------
@@ -534,6 +655,49 @@ extern "C" int aq_val_match(const aq_det* dets_dev, const int32_t* counts_dev, i
     for (int i = 0; i < 10; ++i) p.iouv[i] = iouv_host[i];
     hipLaunchKernelGGL(match_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, p);
     hipLaunchKernelGGL(match_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, p);
+    AQ_CHECK_HIP(hipGetLastError());
+    return AQ_OK;
+}
+
+extern "C" size_t aq_val_confusion_scratch_bytes(int B, int max_det, long long L) {
+    if (B < 0 || max_det < 1 || !sg::val_count_fits((long long)B * max_det) || !sg::val_count_fits(L)) return 0;
+    return (size_t)L * sizeof(unsigned long long) + align8((size_t)B * max_det * sizeof(int));
+}
+
+extern "C" int aq_val_confusion(const aq_det* dets_dev, const int32_t* counts_dev, int B, int max_det, const float* label_box_dev,
+                                const int32_t* label_cls_dev, const int32_t* label_cls_host, const int32_t* label_start_dev,
+                                const int32_t* label_start_host, long long L, const float* geom_dev, int nc, float conf, float iou,
+                                void* scratch_dev, size_t scratch_bytes, long long* matrix_dev, int32_t* image_dev, int32_t* flag_dev,
+                                void* stream) {
+    AQ_REQUIRE(B >= 0 && B <= 65535 && max_det >= 1 && sg::val_count_fits((long long)B * max_det) && sg::val_count_fits(L),
+               "val confusion: %d images (0 to 65535), max_det %d, %lld labels (below 2^31)", B, max_det, L);
+    AQ_REQUIRE(nc >= 1 && nc <= 65535, "val confusion: %d classes (1 to 65535)", nc);
+    AQ_REQUIRE(std::isfinite(conf) && std::isfinite(iou) && iou > 0.0f,
+               "val confusion: confidence threshold %g (finite), IoU threshold %g (finite, above 0)", conf, iou);
+    if (B == 0) return AQ_OK;
+    AQ_REQUIRE(label_start_host, "val confusion: null pointer (the host copy of the label starts)");
+    for (int b = 0; b <= B; ++b)
+        AQ_REQUIRE(label_start_host[b] >= 0 && label_start_host[b] <= L && (b == 0 || label_start_host[b] >= label_start_host[b - 1]),
+                   "val confusion: label start %d is %d (sorted, inside [0, %lld])", b, label_start_host[b], L);
+    if (label_cls_host)
+        for (long long l = 0; l < L; ++l)
+            AQ_REQUIRE(label_cls_host[l] >= 0 && label_cls_host[l] < nc, "val confusion: label %lld has class %d (0 to %d)", l, label_cls_host[l], nc - 1);
+    AQ_REQUIRE(dets_dev && counts_dev && label_start_dev && geom_dev && matrix_dev && image_dev && flag_dev && scratch_dev &&
+               (L == 0 || (label_box_dev && label_cls_dev)), "val confusion: null pointer");
+    AQ_REQUIRE(((uintptr_t)dets_dev & 3) == 0 && ((uintptr_t)counts_dev & 3) == 0 && ((uintptr_t)label_box_dev & 15) == 0 &&
+               ((uintptr_t)label_cls_dev & 3) == 0 && ((uintptr_t)label_start_dev & 3) == 0 && ((uintptr_t)geom_dev & 3) == 0 &&
+               ((uintptr_t)scratch_dev & 7) == 0 && ((uintptr_t)matrix_dev & 7) == 0 && ((uintptr_t)image_dev & 3) == 0 &&
+               ((uintptr_t)flag_dev & 3) == 0, "val confusion: unaligned array");
+    AQ_REQUIRE(scratch_bytes >= aq_val_confusion_scratch_bytes(B, max_det, L), "val confusion: scratch of %zu bytes, %zu needed", scratch_bytes,
+               aq_val_confusion_scratch_bytes(B, max_det, L));
+    ConfusionParams p = {};
+    p.dets = dets_dev; p.counts = counts_dev; p.lbox = (const float4*)label_box_dev; p.lcls = label_cls_dev; p.lstart = label_start_dev;
+    p.geom = geom_dev;
+    p.keys = (unsigned long long*)scratch_dev;
+    p.best = (int*)((char*)scratch_dev + (size_t)L * sizeof(unsigned long long));
+    p.matrix = (unsigned long long*)matrix_dev; p.image = image_dev; p.flag = flag_dev;
+    p.B = B; p.max_det = max_det; p.L = (int)L; p.nc = nc; p.conf = conf; p.iou = iou;
+    hipLaunchKernelGGL(confusion_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, p);
     AQ_CHECK_HIP(hipGetLastError());
     return AQ_OK;
 }

@@ -90,6 +90,7 @@ EXPORTS = (
     "aq_overlap_partners_f64", "aq_overlap_clip_f64",
     "aq_facility_bounds_f64", "aq_box_join_count_i32", "aq_box_join_list_i32",
     "aq_val_expand_scratch_bytes", "aq_val_expand_rows_f32", "aq_val_match", "aq_val_score_chunk", "aq_val_scores_scratch_bytes", "aq_val_scores_f64",
+    "aq_val_confusion_scratch_bytes", "aq_val_confusion",
     "aq_augment_geometry", "aq_augment_taps", "aq_stem_conv_scaled", "aq_preprocess_s2d_scaled", "aq_head_decode_aug", "aq_detect_decode_aug",
     "aq_engine_workspace_bytes_augment", "aq_engine_infer_augment", "aq_engine_forward_raw_augment", "aq_engine_last_launch_augment",
 )
@@ -255,6 +256,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_val_expand_scratch_bytes.restype = sz
     lib.aq_val_expand_rows_f32.argtypes = [vp, i32, i32, i32, f32, i32, vp, sz, vp, vp, vp]
     lib.aq_val_match.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp, vp, C.c_longlong, vp, vp]
+    lib.aq_val_confusion_scratch_bytes.argtypes = [i32, i32, C.c_longlong]
+    lib.aq_val_confusion_scratch_bytes.restype = sz
+    lib.aq_val_confusion.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, C.c_longlong, vp, i32, f32, f32, vp, sz, vp, vp, vp, vp]
     lib.aq_val_score_chunk.argtypes = []
     lib.aq_val_scores_scratch_bytes.argtypes = [C.c_longlong, C.c_longlong]
     lib.aq_val_scores_scratch_bytes.restype = sz
@@ -2055,7 +2059,7 @@ def box_join_list(qbox: torch.Tensor, qgroup: torch.Tensor, kbox: Optional[torch
     return offset_h, out
 
 
-# ---- yolov5/val.py: aq_val_expand_rows_f32, aq_val_match, aq_val_scores_f64 (mAP against YOLO labels) ----
+# ---- yolov5/val.py: aq_val_expand_rows_f32, aq_val_match, aq_val_confusion, aq_val_scores_f64 (mAP and class confusion against YOLO labels) ----
 
 VAL_NMS_ROWS = 131071                      # aq_nms takes fewer than 131072 rows per image
 
@@ -2125,6 +2129,52 @@ def val_match(dets: torch.Tensor, counts: torch.Tensor, label_box: torch.Tensor,
                                        _stream_ptr()))
     for t_ in (dets, counts, label_box, label_cls, label_start, geom, out_conf, out_cls, out_bits, total, scratch):
         t_.record_stream(torch.cuda.current_stream())
+
+
+def val_confusion(dets: torch.Tensor, counts: torch.Tensor, label_box: torch.Tensor, label_cls: torch.Tensor, label_start: torch.Tensor,
+                  label_start_host: np.ndarray, geom: torch.Tensor, nc: int, conf: float, iou: float, matrix: torch.Tensor,
+                  image: Optional[torch.Tensor] = None, label_cls_host: Optional[np.ndarray] = None, flag: Optional[torch.Tensor] = None,
+                  scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """aq_val_confusion on the current stream: the arguments of val_match up to geom, then nc, the confidence and the IoU threshold.  Adds
+    the batch to matrix int64 CUDA [nc + 1, nc + 1] ([predicted][true], index nc = background) and returns image int32 CUDA [B, 4] =
+    (labels, detections that take part, kept pairs, kept pairs of equal classes).  label_cls_host: the host copy of label_cls, checked
+    against nc before the launch.  flag int32 CUDA [1] (zeroed by the caller) is set when an image holds a class outside [0, nc) and adds
+    nothing; without it the call waits for the kernel and raises.  val.confusion_numpy gives the same values."""
+    _require_gpu()
+    lib = load_library()
+    if dets.dim() != 3 or dets.shape[2] != 6:
+        raise ValueError("val: dets has to be [B, max_det, 6]")
+    B, max_det = int(dets.shape[0]), int(dets.shape[1])
+    L, nc = int(label_box.shape[0]), int(nc)
+    if image is None:
+        image = torch.empty((B, 4), dtype=torch.int32, device=dets.device)
+    own_flag = flag is None
+    if own_flag:
+        flag = torch.zeros(1, dtype=torch.int32, device=dets.device)
+    for name, t_, dt, shape in (("dets", dets, torch.float32, (B, max_det, 6)), ("counts", counts, torch.int32, (B,)),
+                                ("label_box", label_box, torch.float32, (L, 4)), ("label_cls", label_cls, torch.int32, (L,)),
+                                ("label_start", label_start, torch.int32, (B + 1,)), ("geom", geom, torch.float32, (B, 5)),
+                                ("matrix", matrix, torch.int64, (max(nc, 0) + 1, max(nc, 0) + 1)), ("image", image, torch.int32, (B, 4)),
+                                ("flag", flag, torch.int32, (1,))):
+        _val_tensor(name, t_, dt, shape)
+    ls = np.ascontiguousarray(label_start_host, dtype=np.int32)
+    if ls.shape != (B + 1,):
+        raise ValueError("val: label_start_host has to hold B + 1 starts")
+    lc = None if label_cls_host is None else np.ascontiguousarray(label_cls_host, dtype=np.int32)
+    if lc is not None and lc.shape != (L,):
+        raise ValueError("val: label_cls_host has to hold one class per label")
+    need = int(lib.aq_val_confusion_scratch_bytes(B, max_det, L))
+    if scratch is None or scratch.numel() < need:
+        scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dets.device)
+    ptr = lambda t_: t_.data_ptr() if t_.numel() else None
+    _check(lib.aq_val_confusion(ptr(dets), ptr(counts), B, max_det, ptr(label_box), ptr(label_cls), lc.ctypes.data if lc is not None and L else None,
+                                label_start.data_ptr(), ls.ctypes.data, L, ptr(geom), nc, float(conf), float(iou), scratch.data_ptr(),
+                                scratch.numel(), matrix.data_ptr(), ptr(image), flag.data_ptr(), _stream_ptr()))
+    for t_ in (dets, counts, label_box, label_cls, label_start, geom, matrix, image, flag, scratch):
+        t_.record_stream(torch.cuda.current_stream())
+    if own_flag and int(flag.item()):
+        raise RuntimeError(f"val: a detection or label class outside [0, {nc}): the image added nothing to the confusion matrix")
+    return image
 
 
 def val_score_runs(run_range: np.ndarray) -> np.ndarray:

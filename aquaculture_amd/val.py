@@ -9,9 +9,11 @@ verify_image_label]) and what is here:
   * the images go through detect.py's loader and device letterbox, not upstream's rect / pad 0.5 / INTER_AREA loader;
   * ``multi_label`` is a row expansion in front of the engine's NMS (aq_val_expand_rows_f32);
   * detections are matched to labels on the GPU (aq_val_match), in original-image pixels, fp32, without a host round trip;
-  * after the sweep the GPU computes ap_per_class's scans, interpolations and sums (aq_val_scores_f64) on the stably sorted detections.
+  * after the sweep the GPU computes ap_per_class's scans, interpolations and sums (aq_val_scores_f64) on the stably sorted detections;
+  * with ``--confusion-matrix`` the same detections and labels also go through upstream's ConfusionMatrix.process_batch on the GPU
+    (aq_val_confusion): val_confusion.csv, val_confusion_norm.csv, val_images.csv and a ``confusion`` object in val.json.
 
-Every device step has a numpy restatement here (expand_rows_numpy, match_numpy, scores_numpy) that gives the same bytes; ``--cpu`` runs
+Every device step has a numpy restatement here (expand_rows_numpy, match_numpy, confusion_numpy, scores_numpy) that gives the same bytes; ``--cpu`` runs
 them on detections read back from label files: ``python -m aquaculture_amd.val --data DATA.yaml --labels DIR --cpu``.
 """
 from __future__ import annotations
@@ -50,6 +52,12 @@ DEPARTURES = (
     "mAP50-95 of the all row is ap.mean(1).mean(), the mean over classes of each class's mean over the ten thresholds, as upstream computes it",
     "per-class rows are printed when (--verbose or nc < 50) and nc > 1, upstream's full condition",
 )
+CONFUSION_CONF, CONFUSION_IOU = 0.25, 0.45             # [UPSTREAM ConfusionMatrix.__init__] conf, iou_thres
+CONFUSION_TIE_NOTE = ("confusion matrix: among equal IoUs a detection's best label is the one of higher index and a label keeps the detection of "
+                      "higher index (upstream's argsort is not stable and leaves equal IoUs to numpy's sort)")
+CONFUSION_QUIRK_NOTE = ("confusion matrix: in an image without a kept (label, detection) pair the detections add no background counts (upstream's "
+                        "`if n:`), and an image without labels adds nothing whatever was detected on it (upstream's val.py calls process_batch only "
+                        "for images with labels)")
 TABLE_HEADER = ("%22s" + "%11s" * 6) % ("Class", "Images", "Instances", "P", "R", "mAP50", "mAP50-95")
 TABLE_ROW = "%22s" + "%11i" * 2 + "%11.3g" * 4
 NO_LABELS = "WARNING ⚠️ no labels found in %s set, can not compute metrics without labels"
@@ -237,6 +245,58 @@ def match_numpy(lbox: np.ndarray, lcls: np.ndarray, dbox: np.ndarray, dcls: np.n
     return bits
 
 
+def confusion_numpy(lbox: np.ndarray, lcls: np.ndarray, dbox: np.ndarray, dconf: np.ndarray, dcls: np.ndarray, nc: int,
+                    conf: float = CONFUSION_CONF, iou: float = CONFUSION_IOU) -> Tuple[np.ndarray, np.ndarray]:
+    """[UPSTREAM utils/metrics.py ConfusionMatrix.process_batch, called per image with labels] as the closed rule (aq_val_confusion): labels
+    [L, 4] / [L], detections [D, 4] / [D] / [D] in original pixels -> (what the image adds to matrix[predicted][true], int64 [nc + 1,
+    nc + 1], index nc = background; int32 [4] = labels, detections that take part, kept pairs, kept pairs of equal classes).  1. a
+    detection takes part iff its confidence > conf; its best label is the label of any class with the largest IoU among those with IoU >
+    iou, the higher index among equal IoUs.  2. a label keeps, of the detections whose best label it is, the one with the largest IoU, the
+    higher index among equal ones: matrix[its class][label class] += 1; a label that keeps none: matrix[nc][label class] += 1; no
+    fall-back.  3. with at least one kept pair, every detection that takes part and that no label keeps: matrix[its class][nc] += 1;
+    without one the detections add nothing.  4. an image without labels adds nothing."""
+    lcls, dcls = np.asarray(lcls).astype(np.int64).reshape(-1), np.asarray(dcls).astype(np.int64).reshape(-1)
+    dconf = np.asarray(dconf, dtype=F32).reshape(-1)
+    L, D, n1 = lcls.shape[0], dcls.shape[0], int(nc) + 1
+    if ((lcls < 0) | (lcls >= nc)).any() or ((dcls < 0) | (dcls >= nc)).any():
+        raise ValueError(f"val: a detection or label class outside [0, {nc})")
+    m = np.zeros((n1, n1), np.int64)
+    take = dconf > F32(conf)
+    part = int(take.sum())
+    if L == 0:
+        return m, np.array([0, part, 0, 0], np.int32)
+    keeps = np.full(L, -1, np.int64)                                            # the detection every label keeps
+    if part:
+        idx = np.nonzero(take)[0]
+        io = box_iou_numpy(lbox, np.asarray(dbox, dtype=F32).reshape(-1, 4)[idx])
+        masked = np.where(io > F32(iou), io, F32(-1))
+        best = L - 1 - np.argmax(masked[::-1], axis=0)                          # the largest, the highest index among equals
+        has = masked[best, np.arange(part)] > 0
+        idx, best, biou = idx[has], best[has], io[best, np.arange(part)][has]
+        o = np.lexsort((idx, biou))                                             # ascending (IoU, index): of repeated labels the last assignment stays
+        keeps[best[o]] = idx[o]
+    kept = keeps >= 0
+    np.add.at(m, (dcls[keeps[kept]], lcls[kept]), 1)
+    m[nc] += np.bincount(lcls[~kept], minlength=n1)
+    if kept.any():
+        free = take.copy()
+        free[keeps[kept]] = False
+        m[:, nc] += np.bincount(dcls[free], minlength=n1)
+    return m, np.array([L, part, int(kept.sum()), int((dcls[keeps[kept]] == lcls[kept]).sum())], np.int32)
+
+
+def confusion_tp_fp(matrix: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """[UPSTREAM ConfusionMatrix.tp_fp]: tp = the diagonal, fp = the row sums - tp, both without the background entry."""
+    tp = matrix.diagonal()
+    fp = matrix.sum(1) - tp
+    return tp[:-1], fp[:-1]
+
+
+def confusion_normalised(matrix: np.ndarray) -> np.ndarray:
+    """[UPSTREAM ConfusionMatrix.plot, normalize=True]: every column divided by (its sum + 1e-9)."""
+    return matrix / (matrix.sum(0).reshape(1, -1) + 1e-9)
+
+
 def interp_numpy(x: np.ndarray, xp: np.ndarray, fp: np.ndarray, left: float) -> np.ndarray:
     """np.interp's rule, written out (interp_rule of csrc/val.hip): j = the last index with xp[j] <= x; fp[j] when j is the last index or
     xp[j] == x, else (fp[j + 1] - fp[j]) / (xp[j + 1] - xp[j]) * (x - xp[j]) + fp[j]; ``left`` below xp[0], fp[-1] above xp[-1]."""
@@ -354,8 +414,44 @@ def curves_csv(names: Dict[int, str], classes: np.ndarray, p: np.ndarray, r: np.
     return "\n".join(rows) + "\n"
 
 
-def write_outputs(save_dir: str, names, nc: int, seen: int, classes, n_l, ap, p, r, pr, meta: dict, verbose: bool, task: str, log=print) -> dict:
-    """Prints the table and writes val_classes.csv, val_curves.csv and val.json into save_dir."""
+def confusion_csv(names: Dict[int, str], nc: int, matrix: np.ndarray, cell=str) -> str:
+    """matrix[predicted][true]: the header ``predicted, <true class names>, background``, then one row per predicted class and ``background``."""
+    labels = [names[c] for c in range(nc)] + ["background"]
+    rows = [",".join(["predicted"] + labels)]
+    for k, name in enumerate(labels):
+        rows.append(",".join([name] + [cell(v) for v in matrix[k]]))
+    return "\n".join(rows) + "\n"
+
+
+def images_csv(files: Sequence[str], image: np.ndarray) -> str:
+    """Per image in split order: labels, detections that take part, matched (kept pairs), matched_same_class, missed = labels - matched,
+    false = detections - matched when matched > 0, else 0 -- the background counts the matrix holds for the image."""
+    rows = ["image,labels,detections,matched,matched_same_class,missed,false"]
+    for f, (n_l, n_d, n_m, n_s) in zip(files, np.asarray(image, dtype=np.int64).reshape(-1, 4).tolist()):
+        rows.append(",".join([str(f), str(n_l), str(n_d), str(n_m), str(n_s), str(n_l - n_m), str(n_d - n_m if n_m > 0 else 0)]))
+    return "\n".join(rows) + "\n"
+
+
+def write_confusion(save_dir: str, names, nc: int, files: Sequence[str], matrix: np.ndarray, image: np.ndarray, conf: float, iou: float) -> dict:
+    """--confusion-matrix: writes val_confusion.csv, val_confusion_norm.csv and val_images.csv into save_dir -> val.json's ``confusion`` object."""
+    matrix = np.asarray(matrix, dtype=np.int64).reshape(nc + 1, nc + 1)
+    os.makedirs(save_dir, exist_ok=True)
+    with open(os.path.join(save_dir, "val_confusion.csv"), "w") as f:
+        f.write(confusion_csv(names, nc, matrix, lambda v: str(int(v))))
+    with open(os.path.join(save_dir, "val_confusion_norm.csv"), "w") as f:
+        f.write(confusion_csv(names, nc, confusion_normalised(matrix), _num))
+    with open(os.path.join(save_dir, "val_images.csv"), "w") as f:
+        f.write(images_csv(files, image))
+    tp, fp = confusion_tp_fp(matrix)
+    return {"conf": float(conf), "iou": float(iou), "classes": [names[c] for c in range(nc)] + ["background"], "layout": "matrix[predicted][true]",
+            "tp": [int(v) for v in tp], "fp": [int(v) for v in fp], "matrix": [[int(v) for v in row] for row in matrix],
+            "notes": [CONFUSION_TIE_NOTE, CONFUSION_QUIRK_NOTE]}
+
+
+def write_outputs(save_dir: str, names, nc: int, seen: int, classes, n_l, ap, p, r, pr, meta: dict, verbose: bool, task: str, log=print,
+                  confusion: Optional[dict] = None) -> dict:
+    """Prints the table and writes val_classes.csv, val_curves.csv and val.json into save_dir.  confusion = write_confusion's object (with
+    --confusion-matrix): it goes into val.json and its tie rule under the departures."""
     s = summarise(ap, p, r, n_l)
     log(format_table(names, seen, classes, n_l, s, (verbose or nc < 50) and nc > 1 and len(classes) > 0))
     if int(np.sum(n_l)) == 0:
@@ -368,6 +464,9 @@ def write_outputs(save_dir: str, names, nc: int, seen: int, classes, n_l, ap, p,
     meta = dict(meta)
     meta["results"] = {"P": s["mp"], "R": s["mr"], "mAP50": s["map50"], "mAP50-95": s["map"], "f1_index": s["i"]}
     meta["departures"] = list(DEPARTURES)
+    if confusion is not None:
+        meta["confusion"] = confusion
+        meta["departures"].append(CONFUSION_TIE_NOTE)
     with open(os.path.join(save_dir, "val.json"), "w") as f:
         json.dump(meta, f, indent=1, sort_keys=True)
         f.write("\n")
@@ -415,7 +514,8 @@ def _runs(sorted_cls_counts: np.ndarray, label_counts: np.ndarray):
 
 # ------------------------------------------------------------- parse and refuse ------------------------------------------------------------
 def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
-    """Upstream's val.py flags with its defaults, plus --precision, --jpeg-decode, --quiet, --labels and --cpu."""
+    """Upstream's val.py flags with its defaults, plus --precision, --jpeg-decode, --quiet, --labels, --cpu and --confusion-matrix with its
+    two thresholds."""
     root = Path.cwd()
     p = argparse.ArgumentParser(prog="val.py")
     p.add_argument("--data", type=str, required=True, help="dataset.yaml path")
@@ -448,6 +548,10 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
     p.add_argument("--labels", default=None, metavar="DIR",
                    help="score the detections of DIR/<image stem>.txt (cls xc yc w h conf, as --save-txt --save-conf writes them) instead of running the engine")
     p.add_argument("--cpu", action="store_true", help="with --labels: the numpy restatements instead of the GPU kernels (same bytes)")
+    p.add_argument("--confusion-matrix", action="store_true",
+                   help="upstream's class confusion matrix in the same pass: val_confusion.csv, val_confusion_norm.csv, val_images.csv and val.json's confusion object")
+    p.add_argument("--confusion-conf", type=float, default=CONFUSION_CONF, help="with --confusion-matrix: detections above this confidence take part")
+    p.add_argument("--confusion-iou", type=float, default=CONFUSION_IOU, help="with --confusion-matrix: a label and a detection pair above this IoU")
     return p.parse_args(argv)
 
 
@@ -468,6 +572,8 @@ def check_opt(opt: argparse.Namespace) -> None:
         raise SystemExit("val.py needs --weights W.pt (or --labels DIR to score detections that were saved before)")
     if not (0.0 <= opt.conf_thres <= 1.0 and 0.0 <= opt.iou_thres <= 1.0 and opt.max_det >= 1 and opt.batch_size >= 1):
         raise SystemExit("--conf-thres and --iou-thres lie in [0, 1]; --max-det and --batch-size are at least 1")
+    if opt.confusion_matrix and not (np.isfinite(opt.confusion_conf) and np.isfinite(opt.confusion_iou) and opt.confusion_iou > 0.0):
+        raise SystemExit("--confusion-conf and --confusion-iou are finite numbers, --confusion-iou above 0")
 
 
 # ------------------------------------------------------------------ runs -------------------------------------------------------------------
@@ -531,9 +637,9 @@ class _DeviceStats:
         self.total = torch.zeros(1, dtype=torch.int64, device=dev)
         self.iouv = IOUV.copy()
 
-    def match(self, dets, counts, boxes: List[np.ndarray], classes: List[np.ndarray], geom: np.ndarray) -> None:
+    def match(self, dets, counts, boxes: List[np.ndarray], classes: List[np.ndarray], geom: np.ndarray):
         """One batch: dets / counts CUDA as the NMS wrote them; the labels' pixel boxes and classes per image and the geometry table from
-        the host, uploaded here."""
+        the host, uploaded here.  -> the uploaded label arrays as _DeviceConfusion.add takes them."""
         import torch
         from .engine import val_match
         dev = dets.device
@@ -542,14 +648,41 @@ class _DeviceStats:
         lbox = np.concatenate(boxes, 0).astype(F32).reshape(-1, 4) if boxes else np.zeros((0, 4), F32)
         lcls = np.concatenate(classes, 0).astype(np.int32).reshape(-1) if classes else np.zeros(0, np.int32)
         up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.size else torch.empty(a.shape, dtype=dt, device=dev)
-        val_match(dets, counts, up(lbox, torch.float32), up(lcls, torch.int32), torch.from_numpy(start).to(dev), start,
-                  up(np.ascontiguousarray(geom, dtype=F32), torch.float32), self.iouv, self.conf, self.cls, self.bits, self.total)
+        lbox_d, lcls_d, start_d, geom_d = (up(lbox, torch.float32), up(lcls, torch.int32), torch.from_numpy(start).to(dev),
+                                           up(np.ascontiguousarray(geom, dtype=F32), torch.float32))
+        val_match(dets, counts, lbox_d, lcls_d, start_d, start, geom_d, self.iouv, self.conf, self.cls, self.bits, self.total)
+        return lbox_d, lcls_d, lcls, start_d, start, geom_d
 
     def result(self):
         n = int(self.total.item())
         if n > self.conf.shape[0]:
             raise RuntimeError(f"val: {n} detections for arrays of {self.conf.shape[0]}")
         return self.conf[:n], self.cls[:n], self.bits[:n]
+
+
+class _DeviceConfusion:
+    """--confusion-matrix: the matrix aq_val_confusion adds every batch to, the per-image rows in split order and the class flag."""
+
+    def __init__(self, nc: int, conf: float, iou: float, n_images: int, dev):
+        import torch
+        self.nc, self.conf_thres, self.iou_thres = nc, float(conf), float(iou)
+        self.matrix = torch.zeros((nc + 1, nc + 1), dtype=torch.int64, device=dev)
+        self.image = torch.zeros((n_images, 4), dtype=torch.int32, device=dev)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def add(self, dets, counts, uploaded, pos: Sequence[int]) -> None:
+        """One batch, after _DeviceStats.match on the same dets / counts (uploaded = what it returned); pos = the images' places in the split."""
+        import torch
+        from .engine import val_confusion
+        lbox_d, lcls_d, lcls, start_d, start, geom_d = uploaded
+        rows = val_confusion(dets, counts, lbox_d, lcls_d, start_d, start, geom_d, self.nc, self.conf_thres, self.iou_thres, self.matrix,
+                             label_cls_host=lcls, flag=self.flag)
+        self.image[torch.as_tensor(list(pos), dtype=torch.int64, device=rows.device)] = rows
+
+    def result(self) -> Tuple[np.ndarray, np.ndarray]:
+        if int(self.flag.item()):
+            raise RuntimeError(f"val: a detection class outside [0, {self.nc}) reached the confusion matrix")
+        return self.matrix.cpu().numpy(), self.image.cpu().numpy()
 
 
 def _label_counts(split: Split, nc: int) -> np.ndarray:
@@ -563,13 +696,20 @@ def run_saved(opt, data: dict, split: Split, names, nc: int, save_dir: str, log=
     sizes = _image_sizes(split.files, opt.workers)
     label_counts = _label_counts(split, nc)
     n_det = 0
+    want_cm = bool(getattr(opt, "confusion_matrix", False))
+    cm = None                                                                   # (matrix [nc + 1, nc + 1], image rows [images, 4]) with --confusion-matrix
     if opt.cpu:
         confs, clss, bitss = [], [], []
-        for f, lb, (w0, h0) in zip(split.files, split.labels, sizes):
+        if want_cm:
+            cm = (np.zeros((nc + 1, nc + 1), np.int64), np.zeros((len(split.files), 4), np.int32))
+        for k, (f, lb, (w0, h0)) in enumerate(zip(split.files, split.labels, sizes)):
             box, conf, cls = read_detections(opt.labels, f, w0, h0, opt.single_cls)
             confs.append(conf)
             clss.append(cls)
             bitss.append(match_numpy(label_boxes(lb, h0, w0), lb[:, 0], box, cls))
+            if want_cm:
+                delta, cm[1][k] = confusion_numpy(label_boxes(lb, h0, w0), lb[:, 0], box, conf, cls, nc, opt.confusion_conf, opt.confusion_iou)
+                cm[0][...] += delta
         conf = np.concatenate(confs) if confs else np.zeros(0, F32)
         cls = np.concatenate(clss).astype(np.int32) if clss else np.zeros(0, np.int32)
         bits = np.concatenate(bitss) if bitss else np.zeros(0, np.uint16)
@@ -582,6 +722,7 @@ def run_saved(opt, data: dict, split: Split, names, nc: int, save_dir: str, log=
         torch.cuda.set_device(dev)
         per = [read_detections(opt.labels, f, w0, h0, opt.single_cls) for f, (w0, h0) in zip(split.files, sizes)]
         stats = _DeviceStats(sum(d[1].shape[0] for d in per), dev)
+        confusion = _DeviceConfusion(nc, opt.confusion_conf, opt.confusion_iou, len(split.files), dev) if want_cm else None
         B = max(1, opt.batch_size)
         for s0 in range(0, len(per), B):
             part = per[s0:s0 + B]
@@ -592,16 +733,21 @@ def run_saved(opt, data: dict, split: Split, names, nc: int, save_dir: str, log=
                 dets[b, :k, :4], dets[b, :k, 4], dets[b, :k, 5] = box, conf, cls
             counts = np.array([d[1].shape[0] for d in part], np.int32)
             geom = np.array([[0, 0, 1, w0, h0] for (w0, h0) in sizes[s0:s0 + B]], F32)
-            stats.match(torch.from_numpy(dets).to(dev), torch.from_numpy(counts).to(dev),
-                        [label_boxes(lb, h0, w0) for lb, (w0, h0) in zip(split.labels[s0:s0 + B], sizes[s0:s0 + B])],
-                        [lb[:, 0] for lb in split.labels[s0:s0 + B]], geom)
+            dets_d, counts_d = torch.from_numpy(dets).to(dev), torch.from_numpy(counts).to(dev)
+            uploaded = stats.match(dets_d, counts_d, [label_boxes(lb, h0, w0) for lb, (w0, h0) in zip(split.labels[s0:s0 + B], sizes[s0:s0 + B])],
+                                   [lb[:, 0] for lb in split.labels[s0:s0 + B]], geom)
+            if confusion is not None:
+                confusion.add(dets_d, counts_d, uploaded, range(s0, s0 + len(part)))
         conf, cls, bits = stats.result()
+        if confusion is not None:
+            cm = confusion.result()
         n_det = int(conf.shape[0])
         classes, n_l, ap, p, r, pr = score_gpu(conf, cls, bits, label_counts)
         device = torch.cuda.get_device_name(dev)
     meta = _meta(opt, data, split, n_det, device, precision=None)
     meta["detections_from"] = str(opt.labels)
-    return write_outputs(save_dir, names, nc, len(split.files), classes, n_l, ap, p, r, pr, meta, opt.verbose, opt.task, log)
+    obj = write_confusion(save_dir, names, nc, split.files, cm[0], cm[1], opt.confusion_conf, opt.confusion_iou) if cm is not None else None
+    return write_outputs(save_dir, names, nc, len(split.files), classes, n_l, ap, p, r, pr, meta, opt.verbose, opt.task, log, confusion=obj)
 
 
 def _meta(opt, data: dict, split: Split, n_det: int, device: str, precision: Optional[str]) -> dict:
@@ -689,6 +835,8 @@ def run_sweep(opt, data: dict, split: Split, names, nc: int, save_dir: str, log=
     os.makedirs(labels_dir if opt.save_txt else save_dir, exist_ok=True)
     multi_label = ck.nc > 1 and not opt.single_cls                              # [UPSTREAM non_max_suppression] multi_label &= nc > 1
     stats = _DeviceStats(len(split.files) * opt.max_det, dev)
+    confusion = (_DeviceConfusion(nc, opt.confusion_conf, opt.confusion_iou, len(split.files), dev)
+                 if getattr(opt, "confusion_matrix", False) else None)
     no = ck.nc + 5
     n_files = 0
     t0 = time.perf_counter()
@@ -717,7 +865,9 @@ def run_sweep(opt, data: dict, split: Split, names, nc: int, save_dir: str, log=
             dets[:, :, 5] = 0
         geom = np.tile(letterbox_geom((H, W), (h0, w0)), (B, 1))
         lbs = [split.labels[i] for i in pos]
-        stats.match(dets, counts, [label_boxes(lb, h0, w0) for lb in lbs], [lb[:, 0] for lb in lbs], geom)
+        uploaded = stats.match(dets, counts, [label_boxes(lb, h0, w0) for lb in lbs], [lb[:, 0] for lb in lbs], geom)
+        if confusion is not None:                                               # the same dets / counts, where the NMS left them
+            confusion.add(dets, counts, uploaded, pos)
         if opt.save_txt:
             n_files += _save_txt(labels_dir, [split.files[i] for i in pos], dets.cpu().numpy(), counts.cpu().numpy(), geom[0], opt.save_conf,
                                  write_label_files)
@@ -737,7 +887,11 @@ def run_sweep(opt, data: dict, split: Split, names, nc: int, save_dir: str, log=
     meta = _meta(opt, data, split, int(conf.shape[0]), torch.cuda.get_device_name(dev), precision)
     meta["weights"] = str(weights)
     meta["images_per_s"] = n_img / max(t1 - t0, 1e-9)
-    s = write_outputs(save_dir, names, nc, n_img, classes, n_l, ap, p, r, pr, meta, opt.verbose, opt.task, log)
+    obj = None
+    if confusion is not None:
+        matrix, image = confusion.result()
+        obj = write_confusion(save_dir, names, nc, split.files, matrix, image, opt.confusion_conf, opt.confusion_iou)
+    s = write_outputs(save_dir, names, nc, n_img, classes, n_l, ap, p, r, pr, meta, opt.verbose, opt.task, log, confusion=obj)
     if opt.save_txt:
         log(f"{n_files} labels saved to {labels_dir}")
     log(f"Results saved to {save_dir}")

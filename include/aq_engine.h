@@ -1022,7 +1022,7 @@ int aq_box_join_list_i32(const double* qbox_dev, const int32_t* qgroup_dev, long
  * Upstream's second entry point on trained weights [UPSTREAM val.py run(), process_batch; utils/metrics.py ap_per_class, compute_ap, box_iou;
  * utils/general.py non_max_suppression(multi_label=True)].  Every launcher runs on `stream`, allocates nothing and stores with plain vector
  * stores; products, sums and quotients are rounded once each, as written (no fma), so aquaculture_amd.val's numpy restatements
- * (expand_rows_numpy, match_numpy, scores_numpy) give the same bytes.  Refused before anything is launched: a count outside its range, a
+ * (expand_rows_numpy, match_numpy, confusion_numpy, scores_numpy) give the same bytes.  Refused before anything is launched: a count outside its range, a
  * null pointer, an unaligned array, starts or runs that decrease or leave their array, a scratch that is too small.
  *
  * aq_val_expand_rows_f32: pred_dev [B][N][5 + nc] (what aq_engine_forward_raw writes) -> rows_dev [B][M][5 + nc] for aq_nms_opts in full-rows
@@ -1047,6 +1047,28 @@ int aq_val_match(const aq_det* dets_dev, const int32_t* counts_dev, int B, int m
                  const int32_t* label_cls_dev, const int32_t* label_start_dev, const int32_t* label_start_host, long long L,
                  const float* geom_dev, const float* iouv_host, int32_t* scratch_dev, float* conf_out_dev, int32_t* cls_out_dev,
                  uint16_t* bits_out_dev, long long cap, long long* total_dev, void* stream);
+/* aq_val_confusion: upstream's class confusion matrix [UPSTREAM utils/metrics.py ConfusionMatrix.process_batch, as val.py calls it: per
+ * image, only for images with labels] on aq_val_match's inputs -- dets_dev, counts_dev, label_box_dev, label_cls_dev, label_start (device
+ * and host), geom_dev as there, the same scale_boxes step and the same fp32 iou.  Per image: (1) a detection takes part iff its conf >
+ * conf (fp32, strict); its best label is the label of ANY class with the largest iou among those with iou > iou (strict), the higher label
+ * index among equal ious; it may have none.  (2) a label keeps, of the detections whose best label it is, the one with the largest iou,
+ * the higher detection index among equal ones, and adds 1 to matrix[class of that detection][class of the label]; a label that keeps none
+ * adds 1 to matrix[nc][its class]; a detection that loses its best label does not fall back to another.  (3) if the image has at least one
+ * kept pair, every detection that takes part and that no label keeps adds 1 to matrix[its class][nc]; in an image without a kept pair the
+ * detections add nothing (upstream's `if n:`).  (4) an image without labels adds nothing.  matrix_dev: int64 [(nc + 1)][(nc + 1)],
+ * [predicted][true], index nc = background, 8-byte aligned; it is ADDED TO with integer atomics (zero it before the first call; one buffer
+ * serves a sweep).  image_dev: int32 [B][4] = labels of the image, detections that take part, kept pairs, kept pairs of equal classes.
+ * An image that holds a class outside [0, nc) -- any detection below its count, any label -- adds nothing to the matrix, gets (labels, 0,
+ * 0, 0) and stores 1 into flag_dev[0] (int32; never cleared here: zero it once, read it after the sweep).  label_cls_host: the host copy
+ * of label_cls_dev or NULL; when given, a label class outside [0, nc) is refused.  Also refused, before anything is launched and with
+ * every output untouched: nc < 1, conf or iou not finite, iou <= 0.  scratch_dev: aq_val_confusion_scratch_bytes(B, max_det, L) = 8 L +
+ * 4 B max_det (rounded up to 8) bytes, 8-byte aligned: the labels' keys (iou bits << 32 | detection; in LDS up to 512 labels per image),
+ * the detections' best labels.  One wavefront per image, one launch.  B = 0 does nothing. */
+size_t aq_val_confusion_scratch_bytes(int B, int max_det, long long L);
+int aq_val_confusion(const aq_det* dets_dev, const int32_t* counts_dev, int B, int max_det, const float* label_box_dev,
+                     const int32_t* label_cls_dev, const int32_t* label_cls_host, const int32_t* label_start_dev,
+                     const int32_t* label_start_host, long long L, const float* geom_dev, int nc, float conf, float iou,
+                     void* scratch_dev, size_t scratch_bytes, long long* matrix_dev, int32_t* image_dev, int32_t* flag_dev, void* stream);
 /* aq_val_scores_f64: bits_dev [n] uint16 and conf_dev [n] fp32 sorted by (class ascending, confidence descending, detection index
  * ascending); run c of C (one per class that has labels, ascending) is the elements run_range[c][0] .. run_range[c][1] - 1 (int64 [C][2]),
  * n_l_dev [C] int32 its number of labels, run_chunk0 [C + 1] int32 the exclusive scan of ceil(run length / aq_val_score_chunk()).  With

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""What the three device steps of yolov5/val.py cost on one MI355X.  Each figure: the median of `--repeats` (default
+"""What the device steps of yolov5/val.py cost on one MI355X.  Each figure: the median of `--repeats` (default
 5) timed calls after two warm-ups, with minimum and maximum, by HIP events around the call on the current stream.
 
   expand    aq_val_expand_rows_f32 at 25,200 rows x 5 classes, batch 32 (the default val.py batch at 640 px), on a synthetic pred in which
             `--share` (default 0.02) of the rows have obj above the threshold, every class of such a row passing
   match     aq_val_match at 32 images x 300 detections x 20 labels, the detections scattered around the labels
+  confusion aq_val_confusion (--confusion-matrix) on the match step's inputs: 32 images x 300 detections x 20 labels, 5 classes, the default
+            thresholds 0.25 / 0.45; beside the match row, which is its comparison (same inputs, the same shape of kernel)
   scores    aq_val_scores_f64 (val.score_gpu: torch's two stable sorts, then the launcher) at 10^7 detections over 5 classes, against
             val.score_cpu -- the numpy restatement -- on the same host, once; the two results have to be the same bytes
 
@@ -96,6 +98,22 @@ def main():
         engine.val_match(dets_d, cnt_d, lbox_d, lcls_d, start_d, start, geom_d, val.IOUV, stats.conf, stats.cls, stats.bits, stats.total, sc)
     res["match_ms"] = timed(match, opt.repeats)
     res["match"] = {"B": Bm, "detections": D, "labels": L, "correct_at_0.5": int((stats.bits[:Bm * D] & 1).sum())}
+
+    # confusion: the match step's inputs
+    cm = torch.zeros((6, 6), dtype=torch.int64, device=dev)
+    rows_c = torch.empty((Bm, 4), dtype=torch.int32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    sc_c = torch.empty(engine.load_library().aq_val_confusion_scratch_bytes(Bm, D, Bm * L), dtype=torch.uint8, device=dev)
+    lcls_h = lb[:, 0].astype(np.int32)
+
+    def confusion():
+        engine.val_confusion(dets_d, cnt_d, lbox_d, lcls_d, start_d, start, geom_d, 5, val.CONFUSION_CONF, val.CONFUSION_IOU, cm, image=rows_c,
+                             label_cls_host=lcls_h, flag=flag, scratch=sc_c)
+    res["confusion_ms"] = timed(confusion, opt.repeats)
+    cm.zero_()
+    confusion()
+    res["confusion"] = {"B": Bm, "detections": D, "labels": L, "classes": 5, "taking_part": int(rows_c[:, 1].sum()), "kept_pairs": int(rows_c[:, 2].sum()),
+                        "kept_pairs_of_equal_classes": int(rows_c[:, 3].sum()), "matrix_sum": int(cm.sum()), "class_flag": int(flag.item())}
 
     # scores
     n = opt.detections
