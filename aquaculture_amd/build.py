@@ -37,6 +37,7 @@ SOURCES = [
     ("jpeg_huff.hip", []),                       # GPU entropy decode (round 4): the Huffman stage, one lane per restart segment
     ("crop_jpeg.hip", []),                       # --save-crop: the encoder's pixel half (colour conversion, FDCT, quantisation); Huffman coding and files on the host; whole frames in 4:2:0 for the annotated images
     ("annotate.hip", []),                        # boxes and labels drawn on a copy of the batch's images (upstream's Pillow-branch box_label)
+    ("mosaic.hip", []),                          # val.py --plots: the mosaic of a batch's first images, paste and fixed-point bilinear resize in one launch
     ("blank_stats.hip", []),                     # --blank-key: grey-level extrema, blank rows and columns, non-blank pixels of every source image
     ("blank_geom.hip", []),                      # --blank-geom: connected components of the non-blank mask, the largest one and its outer edges
     ("facilities.hip", ["-ffp-contract=off"]),   # --facilities: DBSCAN of the detections' centroids; the fp64 distance test exactly as written (no fma)

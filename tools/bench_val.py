@@ -12,7 +12,14 @@
 
 With `--map DATA.yaml --weights W.pt`: val.py on that split under fp32, f16x3, bf16, fp8 and fp8w, mAP beside the sweep's images/s.
 
+With `--plots` only the --plots leg runs, at 640 px and 16 images, 8 labels and 40 detections per image:
+  mosaic, annotate, coefs   the aq_val_mosaic_u8 launch, the two aq_annotate_u8 launches and the aq_image_jpeg_coefs_q(75) launch over both frames
+  plot_batch                the whole val_plots.plot_batch on the host clock (primitives, uploads, launches, read-back, Huffman coding, two files)
+  pillow                    the same two files made on the host: paste, dataloader.resize_linear_u8, ImageDraw, Image.save
+and, with `--map DATA.yaml --weights W.pt`, the fp32 sweep's images/s with and without --plots 3 on that split.
+
     python tools/bench_val.py [--repeats 5] [--share 0.02] [--detections 10000000] [--no-cpu] [--map DATA.yaml --weights W.pt] [--out result.json]
+    python tools/bench_val.py --plots [--repeats 5] [--map DATA.yaml --weights W.pt] [--out result.json]
 """
 import argparse
 import json
@@ -45,6 +52,103 @@ def timed(fn, repeats):
     return spread(out)
 
 
+def pillow_plot(images, geo, paths, targets, names, fname):
+    """plot_images on the host from the uint8 batch: paste, resize, upstream's Annotator calls, Image.save (the comparison of the --plots leg)."""
+    import numpy as np
+    from pathlib import Path
+    from PIL import Image, ImageDraw
+    from aquaculture_amd import annotate, dataloader, postprocess, val_plots
+    H, W, h, w = geo["H"], geo["W"], geo["h"], geo["w"]
+    mosaic = np.full((*geo["src_size"], 3), 255, np.uint8)
+    for i in range(geo["n"]):
+        x, y = geo["src_origins"][i]
+        mosaic[y:y + H, x:x + W] = images[i]
+    if geo["resized"]:
+        mosaic = dataloader.resize_linear_u8(mosaic, geo["size"][1], geo["size"][0])
+    lw, fs = val_plots.annotator_sizes(geo)
+    im = Image.fromarray(mosaic)
+    draw, font = ImageDraw.Draw(im), annotate.load_font(fs)
+    for i in range(geo["n"]):
+        x, y = (int(v) for v in geo["origins"][i])
+        draw.rectangle([x, y, x + w, y + h], None, (255, 255, 255), 2)
+        draw.text([x + 5, y + 5], Path(paths[i]).name[:40], fill=(220, 220, 220), font=font)
+        t = targets[i]
+        for j, box in enumerate(val_plots.cell_boxes(t, geo, i).tolist()):
+            if t.shape[1] == 6 and not t[j, 5] > 0.25:
+                continue
+            colour = tuple(int(v) for v in postprocess.PALETTE[int(t[j, 0]) % 20])
+            label = names[int(t[j, 0])] if t.shape[1] == 5 else f"{names[int(t[j, 0])]} {t[j, 5]:.1f}"
+            draw.rectangle(box, width=lw, outline=colour)
+            tw, th = font.getbbox(label)[2:]
+            outside = box[1] - th >= 0
+            draw.rectangle((box[0], box[1] - th if outside else box[1], box[0] + tw + 1, box[1] + 1 if outside else box[1] + th + 1), fill=colour)
+            draw.text((box[0], box[1] - th if outside else box[1]), label, fill=(255, 255, 255), font=font)
+    im.save(fname)
+
+
+def plots_leg(opt, res):
+    import numpy as np
+    import torch
+    from aquaculture_amd import val, val_plots
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+    B, H, W, L, D = 16, 640, 640, 8, 40
+    names = {i: f"class{i}" for i in range(5)}
+    yy, xx = np.mgrid[0:H, 0:W]
+    images = np.stack([np.stack([(xx + 7 * i) % 256, (yy * 2 + i) % 256, (xx + yy) // 5 % 256], 2) for i in range(B)]).astype(np.uint8)
+    images ^= rng.integers(0, 32, images.shape, dtype=np.uint8)
+    paths = [f"images/tile_{i:04d}.jpg" for i in range(B)]
+    labels = [np.concatenate([rng.integers(0, 5, (L, 1)), rng.random((L, 2)) * 0.8 + 0.1, rng.random((L, 2)) * 0.2 + 0.03], 1).astype(np.float32)
+              for _ in range(B)]
+    dets = np.zeros((B, D, 6), np.float32)
+    c, sz = rng.random((B, D, 2)) * 600 + 20, rng.random((B, D, 2)) * 80 + 10
+    dets[..., :2], dets[..., 2:4], dets[..., 4], dets[..., 5] = c - sz / 2, c + sz / 2, np.sort(rng.random((B, D)), 1)[:, ::-1], rng.integers(0, 5, (B, D))
+    ltg, ptg = val_plots.batch_targets(dets, np.full(B, D), labels, (1024, 1024), (H, W))
+    tiles = torch.from_numpy(images).to(dev)
+    files = ("val_batch0_labels.jpg", "val_batch0_pred.jpg")
+    with tempfile.TemporaryDirectory() as tmp:
+        stages = {"mosaic_ms": [], "annotate_ms": [], "coefs_ms": []}
+        wall = []
+        for k in range(2 + opt.repeats):
+            t = {}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            geo = val_plots.plot_batch(tiles, paths, ltg, ptg, names, tmp, files, times=t)
+            if k >= 2:
+                wall.append((time.perf_counter() - t0) * 1e3)
+                for key in stages:
+                    stages[key].append(t[key])
+        plain = []
+        for k in range(2 + opt.repeats):                                        # without the event synchronisations of the stage timing
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            val_plots.plot_batch(tiles, paths, ltg, ptg, names, tmp, files)
+            if k >= 2:
+                plain.append((time.perf_counter() - t0) * 1e3)
+        host = []
+        for k in range(1 + opt.repeats):
+            t0 = time.perf_counter()
+            for name, tg in zip(files, (ltg, ptg)):
+                pillow_plot(images, geo, paths, tg, names, os.path.join(tmp, "pillow_" + name))
+            if k >= 1:
+                host.append((time.perf_counter() - t0) * 1e3)
+        same = [open(os.path.join(tmp, f), "rb").read() == open(os.path.join(tmp, "pillow_" + f), "rb").read() for f in files]
+        sizes = [os.path.getsize(os.path.join(tmp, f)) for f in files]
+    res["plots"] = {"images": B, "H": H, "W": W, "labels_per_image": L, "detections_per_image": D, "mosaic": list(geo["size"]), "file_bytes": sizes,
+                    "same_bytes_as_pillow": same, "coefs_ms_includes": "the launch, the read-back of the coefficients and its synchronisation"}
+    res["plots_mosaic_ms"], res["plots_annotate_ms"], res["plots_coefs_ms"] = (spread(stages[k]) for k in ("mosaic_ms", "annotate_ms", "coefs_ms"))
+    res["plots_plot_batch_ms"], res["plots_plot_batch_timed_stages_ms"], res["plots_pillow_ms"] = spread(plain), spread(wall), spread(host)
+    if opt.map:
+        sweep = {}
+        with tempfile.TemporaryDirectory() as tmp:
+            for name, extra in (("warm_up", []), ("without", []), ("plots_3", ["--plots", "3"]), ("without_again", []), ("plots_3_again", ["--plots", "3"])):
+                o = val.parse_opt(["--data", opt.map, "--weights", opt.weights, "--project", tmp, "--name", name, "--quiet", *extra])
+                val.run(o, log=lambda *_: None)
+                meta = json.load(open(os.path.join(tmp, name, "val.json")))
+                sweep[name] = {"images_per_s": meta["images_per_s"], "images": meta["images"]}
+        res["plots_sweep"] = sweep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -54,6 +158,7 @@ def main():
     ap.add_argument("--map", default=None, metavar="DATA.yaml")
     ap.add_argument("--weights", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--plots", action="store_true", help="only the --plots leg")
     opt = ap.parse_args()
     import numpy as np
     import torch
@@ -61,6 +166,13 @@ def main():
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(0)
     res = {"device": torch.cuda.get_device_name(dev), "repeats": opt.repeats}
+    if opt.plots:
+        plots_leg(opt, res)
+        print(json.dumps(res, indent=1))
+        if opt.out:
+            with open(opt.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
 
     # expand
     B, N, nc = 32, 25200, 5
